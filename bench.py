@@ -17,9 +17,10 @@ torch.distributed (gloo) is used only for the barrier and the max-over-ranks tim
 before this process has touched a GPU -- and relays rank 0's JSON line; it fails if fewer than N GPUs are visible
 (TPS_BENCH_SHARE_GPU=1 lets ranks share devices: the launcher test on a 1-GPU box).
 
-Two timed regions of K steps each, both bracketed by barrier + device sync (round 4), each REPEATED R times inside the run (round 5:
-R is chosen after the first repeat so that at least 50 ms of GPU work are timed whatever K is -- the driver's `--steps 20` is 0.9 ms of
-it -- and at least 3; `ms_per_step` is the MEDIAN over the repeats, p10 / p90 beside it):
+Two timed regions of EXACTLY K steps each (each after an untimed pass of the same K steps), both bracketed by barrier + device sync
+(round 4); `ms_per_step` is the region's time over K.
+`--min-timed-ms T` repeats each region R times instead (R chosen after the first repeat so that at least T ms of GPU work are timed,
+and at least 3; `ms_per_step` is then the MEDIAN over the repeats, p10 / p90 beside it):
   1. strictly one launch after the other on one context -> the kernel's own duration (HIP events), `roofline`, `single_stream`,
      `value_single_stream`;
   2. the same K steps with consecutive batches on `--streams` (default 2) contexts, each with its own stream, as the file pipeline
@@ -31,6 +32,9 @@ it -- and at least 3; `ms_per_step` is the MEDIAN over the repeats, p10 / p90 be
      the command for a rocprofv3 --stats summary whose average duration is that of an undisturbed launch (scripts/profile.sh adds
      `--no-steady`: the steady-state leg's 4x launches carry the same kernel name).
 `roofline.steady_state` is measured in the run (40 launches of a batch four times the size, ~8 ms) unless `--no-steady`.
+`--dump-outputs DIR` writes what the last step of the `value` region computed (rank 0) as DIR/<name>.npy (float64 / float32): the
+per-read results and step-1 counts of every table pass (of a fixed seeded sample of the reads when all of them would not fit), the
+window sums (and raw rows) of a fixed seeded sample of reads -- at most 64 MB, decided before anything is timed.  The inputs are seeded, so two builds run with the same arguments can be compared output for output.
 `roofline.traffic` and the `roofline.valu` object (instructions per read, lane-instructions per scanned base, VALU busy over one
 launch and over the two-stream region) use the PMC counters of the newest committed profile of the same workload -- counters cannot
 be collected inside a timed run -- and name their source file.
@@ -262,6 +266,75 @@ def gpu_topology():
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SUMS_READS = 256             # window sums of this many reads per table pass (a fixed seeded sample)
+DUMP_RAW_READS = 64               # raw rows of a sub-sample of this many of those reads
+DUMP_RESULT_FIELDS = [f for f in hiplib.RESULT_DTYPE.names if f != "reserved"]
+
+
+def dump_plan(n_reads, table_sizes, prm):
+    """How many reads' per-read results and step-1 counts --dump-outputs writes per table pass: all of them, or -- when that would
+    take the dump past DUMP_LIMIT_BYTES -- as many as fit, a fixed seeded sample that contains the window-row sample.  Bounded from
+    the shapes alone (every read with the most windows a read can have), so every rank decides the same before anything is timed;
+    fails if not even the window-row samples fit."""
+    nw_max = hiplib.window_count(prm.maxlen, prm.window, prm.slide, prm.trimfirst, prm.maxlen)
+    n_sums, n_raw = min(n_reads, DUMP_SUMS_READS), min(n_reads, DUMP_RAW_READS)
+    fixed = per_read = 0
+    for P in table_sizes:
+        per_read += 8 * (len(DUMP_RESULT_FIELDS) + 1) + (2 * P * 4 if prm.flags & hiplib.F_STEP1 else 0)      # (+1: the read's index)
+        if prm.flags & hiplib.F_STORE_SUMS:
+            fixed += n_sums * (8 + nw_max * 4)
+        if prm.flags & hiplib.F_STORE_RAW:
+            fixed += n_raw * (8 + nw_max * P * 4)
+    m = min(n_reads, (DUMP_LIMIT_BYTES - fixed) // per_read)
+    if m < min(n_reads, DUMP_SUMS_READS):
+        raise SystemExit(f"--dump-outputs: the window-row samples alone can take {fixed} bytes, over the {DUMP_LIMIT_BYTES} byte limit")
+    return int(m)
+
+
+def collect_outputs(arrays, prefix, eng, slot, flags, n_result_reads):
+    """What one table pass of a step computed, as a caller of the scan receives it, into `arrays` (name -> array): every field of
+    the per-read results and the step-1 counts (of all reads, or of the `n_result_reads` of a fixed seeded sample, listed in
+    `result_reads`: dump_plan), the window sums / raw rows of a fixed seeded sample of reads (concatenated in sample order; `n_win`
+    of the results splits them).  float64 for the results (`gain`), float32 for the counts (exact: they are far below 2**24; raw
+    rows are widened from their uint8 because the dump is float32 / float64 throughout)."""
+    res = eng.results(slot)
+    n = len(res)
+    perm = np.random.default_rng(0).permutation(n)
+    keep = np.sort(perm[:n_result_reads]) if n_result_reads < n else slice(None)
+    if n_result_reads < n:
+        arrays[prefix + "result_reads"] = keep.astype(np.float64)
+    for field in DUMP_RESULT_FIELDS:
+        arrays[prefix + field] = res[field][keep].astype(np.float64)
+    if flags & hiplib.F_STEP1:
+        cs, ce = eng.batch_trc_counts(slot)
+        arrays[prefix + "trc_counts_start"] = cs[keep].astype(np.float32)
+        arrays[prefix + "trc_counts_end"] = ce[keep].astype(np.float32)
+    sample = np.sort(perm[:DUMP_SUMS_READS])
+    raw_sample = np.sort(perm[:DUMP_RAW_READS]) if flags & hiplib.F_STORE_RAW else perm[:0]
+    if flags & hiplib.F_STORE_SUMS or len(raw_sample):
+        arrays[prefix + "sample_reads"] = sample.astype(np.float64)
+        off = eng.window_offsets(slot)
+    if flags & hiplib.F_STORE_SUMS:
+        sums, _ = eng.window_sums(slot)
+        arrays[prefix + "window_sums_sample"] = np.concatenate([sums[off[i]:off[i + 1]] for i in sample] + [sums[:0]]).astype(np.float32)
+        del sums
+    if len(raw_sample):
+        raw, _ = eng.window_raw(slot)
+        arrays[prefix + "raw_sample_reads"] = raw_sample.astype(np.float64)
+        arrays[prefix + "window_raw_sample"] = np.concatenate([raw[off[i]:off[i + 1]] for i in raw_sample] + [raw[:0]]).astype(np.float32)
+        del raw
+
+
+def save_outputs(out_dir, arrays):
+    """DIR/<name>.npy for every array (dump_plan has kept them under DUMP_LIMIT_BYTES)."""
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, total
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def spawn_ranks(n, argv):
     """`python bench.py --gpus N` without a launcher: start the N ranks as fresh child processes (this process has not
     touched a GPU and never will), one per GPU, rendezvous over 127.0.0.1; relay rank 0's output; non-zero exit if any
@@ -313,7 +386,10 @@ def main():
                     "and the last round of wave slots weigh a quarter; 46 launches, ~8 ms): the command whose rocprofv3 --stats average is "
                     "compared with the live kernel duration leaves it out, its launches carry the same kernel name")
     ap.add_argument("--steady", action="store_true", help=argparse.SUPPRESS)          # (round 4's opt-in switch: the leg is on by default now)
-    ap.add_argument("--min-timed-ms", type=float, default=50.0, help="each timed region is repeated until this much time has been measured (and >= 3 repeats); 0 = one repeat (profiling runs)")
+    ap.add_argument("--min-timed-ms", type=float, default=0.0, help="repeat each timed region until this much time has been measured (and >= 3 repeats); "
+                    "0 (default) = one region of exactly --steps steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="after the timed steps, write what the last timed step computed as "
+                    "DIR/<name>.npy (float64 / float32; window rows of a fixed seeded sample of reads; at most 64 MB)")
     ap.add_argument("--sequential-tables", action="store_true", help="several tables per step (config5): back to back on the one context instead of "
                     "overlapping on one context per table (the A/B switch; batch.SEQUENTIAL_TABLES in the pipeline)")
     ap.add_argument("--prime", type=int, default=256, help="launches before the warm-up (runtime growth steps, clocks)")
@@ -375,6 +451,7 @@ def main():
         prm.flags |= hiplib.F_STORE_RAW
     if args.flags:
         prm.flags = args.flags
+    dump_reads = dump_plan(n_reads, [len(t) for t in tables], prm) if args.dump_outputs else 0
     ref_py = None
     if not args.no_cpu_baseline and world == 1 and not (args.flags or args.n_reads or args.errors or args.k):
         try:                                      # forks a Pool: before anything touches the GPU
@@ -467,10 +544,17 @@ def main():
         step(i % copies)
     import math
 
-    def timed_region(run_steps, sync):
-        """R repeats of EXACTLY args.steps steps, each bracketed by barrier + device sync on both sides and timed as the max over
-        ranks; R = enough for --min-timed-ms of measured time, at least 3 (decided from the first repeat's max-over-ranks time, so
-        every rank takes the same R).  Returns ([seconds of repeat r (max over ranks)], [this rank's seconds])."""
+    def timed_region(run_steps, sync, timed_engines):
+        """One untimed pass of the region's steps (the first pass after the set-up ran slower than the repeats after it: the median
+        over >= 3 repeats used to leave it out, a single timed pass must not contain it), then R repeats
+        of EXACTLY args.steps steps, each bracketed by barrier + device sync on both sides and timed as the max over ranks; R = 1, or
+        with --min-timed-ms enough for that much measured time and at least 3 (decided from the first repeat's max-over-ranks time,
+        so every rank takes the same R).  The kernel timers of `timed_engines` count the timed repeats only.  Returns ([seconds of
+        repeat r (max over ranks)], [this rank's seconds])."""
+        run_steps()
+        sync()
+        for eng in timed_engines:
+            eng.kernel_time_reset()
         glob_t, own_t = [], []
         repeats = 1
         r = 0
@@ -499,9 +583,7 @@ def main():
             step(i % copies)
 
     barrier()
-    for eng in engines:
-        eng.kernel_time_reset()
-    serial_t, serial_own = timed_region(run_serial, sync_all)
+    serial_t, serial_own = timed_region(run_serial, sync_all, engines)
 
     def median_repeat(ts):
         """index of the repeat whose max-over-ranks time is the median (the lower middle one of an even count): the headline is a
@@ -528,7 +610,8 @@ def main():
                 eng.set_patterns(pats)
                 for s in range(copies):
                     eng.share(s, sc, s)
-            for i in range(max(args.warmup, 4 * len(pipe))):
+            # primed like the first context (--prime): the helper's own runtime growth steps must not fall into the timed steps
+            for i in range(max(args.warmup, 4 * len(pipe), args.prime)):
                 pipe[i % len(pipe)].scan(i % copies, prm)
             for eng in pipe:
                 eng.sync()
@@ -545,9 +628,7 @@ def main():
             for i in range(args.steps):
                 pipe[i % len(pipe)].scan(i % copies, prm)
         grp.barrier()
-        for eng in pipe:
-            eng.kernel_time_reset()
-        piped_t, piped_own = timed_region(run_piped, sync_pipe)
+        piped_t, piped_own = timed_region(run_piped, sync_pipe, pipe)
         mid_p = median_repeat(piped_t)
         dt = float(piped_t[mid_p])
         ktp = [eng.kernel_time_ms() for eng in pipe]
@@ -557,6 +638,27 @@ def main():
                      timed_ms_total=float(np.sum(piped_t)) * 1e3,
                      kernel_ms_mean_while_overlapping=sum(x[1] for x in ktp) / max(1, sum(x[0] for x in ktp)))
         dt_rank = float(piped_own[mid_p])
+    if args.dump_outputs and rank == 0:
+        # the last timed step of the region `ms_per_step` comes from: its slot, on the context that scanned it
+        last_slot = (args.steps - 1) % copies
+        dumped = {}
+        if pipe is not None:
+            collect_outputs(dumped, "", pipe[(args.steps - 1) % len(pipe)], last_slot, prm.flags, dump_reads)
+        elif len(tables) == 1:
+            collect_outputs(dumped, "", sc, last_slot, prm.flags, dump_reads)
+        elif concurrent:
+            for kk, eng in zip(ks, engines):
+                collect_outputs(dumped, f"k{kk}_", eng, last_slot, prm.flags, dump_reads)
+        else:
+            # back to back on the one context: it holds the last table's outputs only, so every table pass of the last step is run
+            # again on the same slot -- the same outputs, because a scan is deterministic (same batch, table and parameters)
+            for kk, t in zip(ks, tables):
+                sc.set_patterns(t)
+                sc.scan(last_slot, prm)
+                sc.sync()
+                collect_outputs(dumped, f"k{kk}_", sc, last_slot, prm.flags, dump_reads)
+        save_outputs(args.dump_outputs, dumped)
+        del dumped
     per_rank = grp.gather_objects(dict(rank=rank, device=dev, device_info=sc.device_info(), pci=rank_pci,
                                        cpus=len(os.sched_getaffinity(0)), ms_per_step=dt_rank / args.steps * 1e3,
                                        ms_per_step_single_stream=dt_serial / args.steps * 1e3,
@@ -607,6 +709,10 @@ def main():
     touched_per_read = np.where(passed, np.minimum(lens, tail_span + np.minimum(prm.no_bp, lens - tail_span)), heads)
     touched = int(touched_per_read.sum())
 
+    def region_desc(repeats):
+        return ("one timed region of exactly %d steps" % args.steps) if repeats == 1 else \
+               ("median of %d repeats of exactly %d steps (--min-timed-ms %g)" % (repeats, args.steps, args.min_timed_ms))
+
     if rank == 0:
         total_bases = batch_bases * world * args.steps
         # `value`: bases the path can touch per second (= input bases while reads are no longer than maxlengthtelo: configs 1-3;
@@ -640,11 +746,11 @@ def main():
             "value_single_stream": touched * world * args.steps / dt_serial,
             "single_stream": {"value": touched * world * args.steps / dt_serial, "ms_per_step": s_med, "ms_per_step_p10": s_p10,
                               "ms_per_step_p90": s_p90, "repeats": len(serial_t), "timed_ms_total": float(np.sum(serial_t)) * 1e3},
-            "consistency": ("`value` / `ms_per_step`: median of %d repeats of exactly %d steps with consecutive batches alternating over %d streams -- "
+            "consistency": ("`value` / `ms_per_step`: %s with consecutive batches alternating over %d streams -- "
                             "two launches overlap, so ms_per_step may lie below the kernel's own duration (roofline.kernel_ms_mean, measured on the "
-                            "serialised region = single_stream, where ms_per_step >= kernel_ms_mean holds)" % (piped["repeats"], args.steps, piped["streams"]))
-                           if piped else ("`value` / `ms_per_step`: median of %d repeats of exactly %d steps, %s" %
-                                          (len(serial_t), args.steps, "the step's %d table launches overlapping on %d streams" % (len(tables), len(tables))
+                            "serialised region = single_stream, where ms_per_step >= kernel_ms_mean holds)" % (region_desc(piped["repeats"]), piped["streams"]))
+                           if piped else ("`value` / `ms_per_step`: %s, %s" %
+                                          (region_desc(len(serial_t)), "the step's %d table launches overlapping on %d streams" % (len(tables), len(tables))
                                            if concurrent else "strictly one launch after the other")),
             **({"pipelined_error": pipe_err} if pipe_err else {}),
             "higher_is_better": True,

@@ -8,7 +8,9 @@ What is compared (normalise()): telolengths_all.csv as a row SEQUENCE, the summa
 processing all reads"), and every filtered file by name and content (Topsicle/main.py:52-154, 156-309).
 """
 import gzip
+import hashlib
 import io
+import json
 import os
 
 import numpy as np
@@ -174,3 +176,59 @@ def normalise(out_dir):
         if f.startswith("rawcount_") and f.endswith(".csv"):
             res["rawcount"][f] = open(os.path.join(out_dir, f)).read()
     return res
+
+
+def walk_order(inp):
+    """The input files in the order the CLIs visit them (os.walk of the input directory, main.py:225): relative paths."""
+    if not os.path.isdir(inp):
+        return [os.path.basename(inp)]
+    return [os.path.relpath(os.path.join(root, f), inp) for root, _dirs, files in os.walk(inp) for f in files]
+
+
+def digest(text):
+    """A file's content as it is recorded in the fixtures: its sha256 and length."""
+    return {"sha256": hashlib.sha256(text.encode()).hexdigest(), "bytes": len(text)}
+
+
+def digest_outputs(res):
+    """normalise()'s result with the filtered and raw-count files' contents replaced by their digests (what tests/golden records)."""
+    return dict(res, filtered={f: digest(t) for f, t in res["filtered"].items()}, rawcount={f: digest(t) for f, t in res["rawcount"].items()})
+
+
+def case_digest(case):
+    """sha256 of a case (input files, flags, expected exit): a recorded run is replayed only on the case it was recorded from."""
+    return hashlib.sha256(json.dumps(case, sort_keys=True).encode()).hexdigest()
+
+
+def existing_fasta_case():
+    """Case 131, one file, with the `<name>_trc_over_0.5.fasta` of an earlier run already in the output directory: every record of
+    the input as FASTA (what upstream's step 2 reads; main.py:64-66 uses such a file instead of rewriting it).  Returns (case, name
+    of that file)."""
+    import ref_import
+    case = make_case(131)
+    case["argv"] = ["--pattern", case["argv"][1], "--minSeqLength", "1200", "--threads", "1", "--cutoff", "0.5"]
+    rel = next(iter(case["files"]))
+    name = os.path.splitext(os.path.basename(rel))[0]
+    text = case["files"][rel]
+    recs = [(r.description, str(r.seq)) for r in ref_import._parse(io.StringIO(text), "fastq" if text.startswith("@") else "fasta")]
+    fasta = f"{name}_trc_over_0.5.fasta"
+    case["pre"] = {fasta: "".join(f">{d}\n{s}\n" for d, s in recs)}
+    case["files"] = {rel: text}
+    case["input"] = rel
+    return case, fasta
+
+
+def write_duplicate_ids_fasta(path):
+    """Three records, two of them with one id (malformed input): "dup" (1700 b), "solo" (2600 b), "dup" (3100 b).  Returns the
+    three sequences by key b, a, c."""
+    rng = np.random.default_rng(9)
+    a = make_read(rng, "CCCTAA", 2600, True, False)
+    b = make_read(rng, "CCCTAA", 1700, True, True)
+    c = make_read(rng, "CCCTAA", 3100, True, True)
+    with open(path, "w") as h:
+        h.write(f">dup first\n{b}\n>solo\n{a}\n>dup second\n{c}\n")
+    return {"b": b, "a": a, "c": c}
+
+
+DUP_BOUND_CALLS = [(tail, M) for tail in ("forward", "reverse", None) for M in (20000, 2000, 1500)]     # bound_detect(..., M, 4, tail=tail)
+DIFFERENTIAL_FIRST_SEEDS = (100, 112, 124, 136)      # twelve seeds from each

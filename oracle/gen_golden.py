@@ -14,13 +14,15 @@ Topsicle/allsteps.py unchanged through oracle/ref_import.py and records inputs +
                        odd window/slide/trim values
   cli_<seed>.json      whole runs of the reference's main() on seeded inputs (oracle/cli_cases.py): flags, input files, and the
                        CSV rows / summary log lines / filtered files the run left behind   (main.py:52-154, 156-309)
+  reference_runs.json  more runs of main() (outputs as digests) and of bound_detect, for tests/test_ref_cli_differential.py
   demo_col0.fastq.gz, demo_telolengths_all.csv, demo_run_log.json
                        data files of the reference's demo (inputs / its only result goldens)
 
 Boundaries come from the reference's bound_detect driven by the Binseg restatement
 (ruptures is not installable here) -- they are pinned by the 17 demo values only.
 
-    python oracle/gen_golden.py            # rewrites tests/golden/
+    python oracle/gen_golden.py                      # rewrites tests/golden/
+    python oracle/gen_golden.py reference_runs       # rewrites tests/golden/reference_runs.json only
 """
 import csv
 import hashlib
@@ -299,6 +301,37 @@ def gen_cli():
         print(f"cli_{seed}.json:", 0 if not expected["csv"] else len(expected["csv"]) - 1, "rows,", len(expected["filtered"]), "filtered files,", len(expected["rawcount"]), "raw-count files")
 
 
+def gen_reference_runs(ref):
+    """The runs tests/test_ref_cli_differential.py compares the product with: the reference's main() on the seeded cases of
+    cli_cases.DIFFERENTIAL_FIRST_SEEDS (twelve seeds from each), on cli_cases.existing_fasta_case(), and its bound_detect on the
+    file with duplicate read ids -> reference_runs.json.  Per case: the case's digest, then either the exception the reference
+    raised or its exit code, the order in which it visited the input files and its outputs (normalised, file contents as digests)."""
+    import cli_cases
+
+    def run(case):
+        with tempfile.TemporaryDirectory() as d:
+            inp, out = cli_cases.materialise(case, d)
+            try:
+                code = ref_import.run_reference_main(["-i", inp, "-o", out] + case["argv"])
+            except IndexError as e:
+                return {"case_sha256": cli_cases.case_digest(case), "crashed": repr(e)}
+            return {"case_sha256": cli_cases.case_digest(case), "exit": code, "walk": cli_cases.walk_order(inp),
+                    "expected": cli_cases.digest_outputs(cli_cases.normalise(out))}
+    seeds = {}
+    for first in cli_cases.DIFFERENTIAL_FIRST_SEEDS:
+        for seed in range(first, first + 12):
+            seeds[str(seed)] = run(cli_cases.make_case(seed))
+    existing = run(cli_cases.existing_fasta_case()[0])
+    with tempfile.TemporaryDirectory() as d:
+        fa = os.path.join(d, "dups.fasta")
+        cli_cases.write_duplicate_ids_fasta(fa)
+        dup = [{"tail": tail, "maxlen": M, "want": ref.bound_detect(fa, "dup", "CCCTAA", 100, 6, 100, M, 4, tail=tail)}
+               for tail, M in cli_cases.DUP_BOUND_CALLS]
+    with open(os.path.join(GOLD, "reference_runs.json"), "w") as h:
+        json.dump({"seeds": seeds, "existing_fasta": existing, "duplicate_ids": dup}, h, indent=0, sort_keys=True, default=int)
+    print("reference_runs.json:", len(seeds), "seeded runs,", sum("crashed" in r for r in seeds.values()), "of them crashed in the reference")
+
+
 def main():
     os.makedirs(GOLD, exist_ok=True)
     ref = ref_import.load_reference_allsteps()
@@ -307,8 +340,12 @@ def main():
     gen_synth(ref)
     gen_overview()
     gen_cli()
+    gen_reference_runs(ref)
     print("fixture bytes:", sum(os.path.getsize(os.path.join(GOLD, f)) for f in os.listdir(GOLD)))
 
 
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["reference_runs"]:          # that fixture alone
+        gen_reference_runs(ref_import.load_reference_allsteps())
+    else:
+        main()

@@ -2,7 +2,7 @@
 Many (motif, k, window, slide, trimfirst, maxlen, jump) combinations x reads with errors / N / lower case / both
 strands / odd lengths; step-1 counts, window sums, raw counts and the change-point must all agree."""
 import os, sys, time
-ROOT = os.environ.get('GRAFT_REPO_ROOT', '/root/repo')
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'oracle'))
 import numpy as np
 from topsicle_amd import hiplib, allsteps

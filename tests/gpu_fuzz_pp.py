@@ -2,7 +2,7 @@
 k-mers' own period (chains of overlapping occurrences), raw counts and sums, both tails.  The C oracle is the checker
 (test infrastructure only).  usage: gpu_fuzz_pp.py [N_CASES] [SEED0]"""
 import os, sys, time
-ROOT = os.environ.get('GRAFT_REPO_ROOT', '/root/repo')
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'oracle')); sys.path.insert(0, os.path.join(ROOT, 'tests'))
 import numpy as np
 from topsicle_amd import hiplib

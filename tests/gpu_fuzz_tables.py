@@ -3,7 +3,7 @@ parameters and output flags, batch after batch of random size through batch.scan
 resident batch, all tables launched together -- against the same jobs back to back on the one context
 (batch.SEQUENTIAL_TABLES).  Rows, window sums and raw rows of passing reads must be identical."""
 import os, sys, time
-ROOT = os.environ.get('GRAFT_REPO_ROOT', '/root/repo')
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np
 from topsicle_amd import allsteps, batch, hiplib, synth

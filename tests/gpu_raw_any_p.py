@@ -1,6 +1,6 @@
 """GPU check: raw rows for any number of patterns (odd row lengths leave byte by byte)."""
 import os, sys
-ROOT = os.environ.get('GRAFT_REPO_ROOT', '/root/repo')
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'oracle')); sys.path.insert(0, os.path.join(ROOT, 'tests'))
 import numpy as np
 from topsicle_amd import hiplib

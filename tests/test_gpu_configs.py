@@ -319,6 +319,30 @@ def test_bench_launches_its_own_ranks():
         assert r.returncode != 0 and "GPU(s) visible" in (r.stdout + r.stderr)
 
 
+def test_bench_dumps_the_same_outputs_twice_and_times_exactly_steps(tmp_path):
+    """`bench.py --dump-outputs DIR`: two runs with the same arguments write the same files with identical arrays, float32 / float64
+    only, at most 64 MB in all; the default run times one region of exactly --steps steps.  A config5 run dumps every table pass."""
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"dump{run}"
+        r = _run_bench(["--gpus", "1", "--no-e2e", "--no-steady", "--dump-outputs", str(d)], {})
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        assert out["steps"] == 4 and out["repeats"] == 1 and out["single_stream"]["repeats"] == 1
+        assert out["consistency"].startswith("`value` / `ms_per_step`: one timed region of exactly 4 steps")
+        dumps.append({f: np.load(d / f) for f in sorted(os.listdir(d))})
+    assert list(dumps[0]) == list(dumps[1]) and "bkp.npy" in dumps[0] and "window_sums_sample.npy" in dumps[0]
+    for f, a in dumps[0].items():
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, dumps[1][f]), f
+    assert len(dumps[0]["pass.npy"]) == 2000 and dumps[0]["pass.npy"].sum() > 0
+    assert sum(os.path.getsize(tmp_path / "dump0" / f) for f in dumps[0]) <= 64 << 20
+    d = tmp_path / "dump_config5"
+    r = _run_bench(["--gpus", "1", "--no-e2e", "--dump-outputs", str(d), "--workload", "config5", "--n-reads", "600"], {})
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    names = set(os.listdir(d))
+    assert {f"k{k}_{n}.npy" for k in (4, 5, 6) for n in ("bkp", "window_sums_sample", "window_raw_sample")} <= names
+
+
 @pytest.mark.parametrize("workload,extra", [("config3_per_gpu", ["--n-reads", "1500"]), ("config4_sample", ["--n-reads", "1200"]), ("config5", ["--n-reads", "600"])])
 def test_bench_ranks_on_the_other_workloads(workload, extra):
     """The self-launched multi-rank path with the other BASELINE shapes (HiFi slide 7, 30 kb reads, the three-k raw-count step):
@@ -337,11 +361,12 @@ def test_bench_ranks_on_the_other_workloads(workload, extra):
     assert all(x["kernel_ms_mean"] > 0 for x in out["ranks"])
 
 
-def test_bench_eight_ranks_through_the_drivers_launcher():
-    """The driver's own N = 8 command -- `python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1
-    ... bench.py --gpus 8` -- on this box's ONE GPU (TPS_BENCH_SHARE_GPU=1: the ranks wrap around the visible devices): the
-    eight-rank gloo rendezvous, the barrier-bracketed timing, the max over ranks and the one JSON line with all eight ranks'
-    own numbers.  (What eight GPUs give is the driver's to measure; that the command runs is checked here.)"""
+def test_bench_four_ranks_through_the_drivers_launcher():
+    """The driver's multi-rank command -- `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1
+    ... bench.py --gpus N` -- with N = 4 on this box's ONE GPU (TPS_BENCH_SHARE_GPU=1: the ranks wrap around the visible devices):
+    the four-rank gloo rendezvous, the barrier-bracketed timing, the max over ranks and the one JSON line with all four ranks' own
+    numbers.  Four ranks rather than the driver's eight keep the processes that hold the one GPU (the ranks and this test's own) at
+    five.  (What eight GPUs give is the driver's to measure; that the command runs is checked here.)"""
     import socket
     import subprocess
     import sys
@@ -352,18 +377,18 @@ def test_bench_eight_ranks_through_the_drivers_launcher():
     env = dict(os.environ, TPS_BENCH_PRIME="8", TPS_BENCH_SHARE_GPU="1")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
-                        "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "20", "--warmup", "2",
+    r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr", "127.0.0.1",
+                        "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "4", "--steps", "20", "--warmup", "2",
                         "--resident-copies", "2"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1                                       # rank 0 prints, once
     out = json.loads(lines[0])
-    assert out["n_gpus"] == 8 and out["steps"] == 20 and out["warmup"] == 2 and out["scaling"] == "weak"
-    assert sorted(x["rank"] for x in out["ranks"]) == list(range(8))
+    assert out["n_gpus"] == 4 and out["steps"] == 20 and out["warmup"] == 2 and out["scaling"] == "weak"
+    assert sorted(x["rank"] for x in out["ranks"]) == list(range(4))
     assert all(x["kernel_ms_mean"] > 0 and x["ms_per_step"] > 0 for x in out["ranks"])
     assert abs(out["ms_per_step"] - max(x["ms_per_step"] for x in out["ranks"])) < 1e-9      # the MAX over ranks
     assert "cpu_baseline" not in out and "e2e" not in out        # N = 1 legs only
-    # whole-job value: eight ranks' batches over the slowest rank's time
+    # whole-job value: four ranks' batches over the slowest rank's time
     per_step = out["config"]["reads_per_step_per_gpu"] * out["config"]["read_len"]
-    assert out["input_bases_per_sec"] == pytest.approx(8 * per_step / (out["ms_per_step"] * 1e-3), rel=0.02)
+    assert out["input_bases_per_sec"] == pytest.approx(4 * per_step / (out["ms_per_step"] * 1e-3), rel=0.02)

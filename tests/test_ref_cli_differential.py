@@ -3,19 +3,44 @@ build container (oracle/ref_import.py: Bio / seaborn / ruptures stand-ins, a fun
 inputs and flag sets (oracle/cli_cases.py: 1 - 3 files, fasta / fastq / gz, reads around --minSeqLength and --maxlengthtelo,
 --telophrase / --cutoff lists, --slide, --trimfirst, --windowSize, --read_check, --override, a pre-existing telolengths_all.csv);
 topsicle_amd.main runs the same command on the emulated engines.  Compared: the CSV as a row SEQUENCE, the summary lines of the
-log, the filtered files by name and content, the exit code.  Skips without /root/reference (the GPU box): there the same runs
-are replayed from tests/golden/cli_*.json (test_cli_golden_cases here on the emulation, tests/test_gpu_parity.py on the GPU)."""
-import hashlib
+log, the filtered files by name and content, the exit code.  The reference's side of every run was recorded by oracle/gen_golden.py
+(tests/golden/reference_runs.json: outputs as digests; tests/golden/cli_*.json: whole runs with their inputs, also replayed on the
+GPU), so the tests need nothing outside the repository."""
 import json
 import os
 
 import pytest
 
 import cli_cases
-import ref_import
 from topsicle_amd import main as cli
 
-HAVE_REF = os.path.isdir(ref_import.REFERENCE_ROOT)
+
+@pytest.fixture(scope="module")
+def recorded(gold_dir):
+    """The reference's runs (oracle/gen_golden.py gen_reference_runs)."""
+    return json.load(open(os.path.join(gold_dir, "reference_runs.json")))
+
+
+def recorded_run(rec, case):
+    assert rec["case_sha256"] == cli_cases.case_digest(case), "the case generator changed: re-record with oracle/gen_golden.py"
+    return rec
+
+
+def compare_recorded(rec, inp, b, what):
+    """A recorded run of the reference against the product's run on the same case.  When the product visited the input files in
+    the recorded order (always for one file), everything is compared exactly: the CSV as a row SEQUENCE, the summary lines, every
+    filtered and raw-count file by digest.  Only when this file system walks the input directory in another order does the
+    comparison fall back to compare_replayed (rows per file and k; raw-count contents of one-file runs)."""
+    a = rec["expected"]
+    if cli_cases.walk_order(inp) != rec["walk"]:
+        compare_replayed(a, b, what)
+        return
+    assert a["csv"] == b["csv"], (what, "csv rows")
+    assert a["summary"] == b["summary"], (what, "summary lines")
+    for kind in ("filtered", "rawcount"):
+        assert sorted(a[kind]) == sorted(b[kind]), (what, kind, "file names")
+        for f, d in a[kind].items():
+            assert d == cli_cases.digest(b[kind][f]), (what, f)
 
 
 def run_product(engines, argv):
@@ -28,59 +53,35 @@ def run_product(engines, argv):
     return None
 
 
-def compare(a, b, what):
-    assert a["csv"] == b["csv"], (what, "csv rows")
-    assert a["summary"] == b["summary"], (what, "summary lines")
-    assert sorted(a["filtered"]) == sorted(b["filtered"]), (what, "filtered file names")
-    for f in a["filtered"]:
-        assert a["filtered"][f] == b["filtered"][f], (what, f)
-    assert sorted(a.get("rawcount", {})) == sorted(b.get("rawcount", {})), (what, "raw-count file names")
-    for f in a.get("rawcount", {}):
-        assert a["rawcount"][f] == b["rawcount"][f], (what, f)
-
-
-@pytest.mark.skipif(not HAVE_REF, reason="needs /root/reference (build container only)")
-@pytest.mark.parametrize("first", [100, 112, 124, 136])
-def test_cli_matches_the_reference_main(first, tmp_path, emu_engine_factory):
+@pytest.mark.parametrize("first", cli_cases.DIFFERENTIAL_FIRST_SEEDS)
+def test_cli_matches_the_reference_main(first, tmp_path, emu_engine_factory, recorded):
     """Twelve seeded cases per call.  The reference itself crashes on some inputs the generator can produce -- FASTA input with
     several k: the second k REUSES the first k's `.fasta` (main.py:64-66) and a read that passes only at the second k is not in it,
     so `bound_res[0]` raises IndexError (main.py:131) -- those cases are counted, not compared (the product completes them)."""
     crashed = []
     for seed in range(first, first + 12):
         case = cli_cases.make_case(seed)
-        inp_r, out_r = cli_cases.materialise(case, str(tmp_path / f"ref{seed}"))
-        inp_p, out_p = cli_cases.materialise(case, str(tmp_path / f"prod{seed}"))
-        try:
-            code_r = ref_import.run_reference_main(["-i", inp_r, "-o", out_r] + case["argv"])
-        except IndexError as e:
-            crashed.append((seed, repr(e)))
+        rec = recorded_run(recorded["seeds"][str(seed)], case)
+        if "crashed" in rec:
+            crashed.append((seed, rec["crashed"]))
             continue
+        inp_p, out_p = cli_cases.materialise(case, str(tmp_path / f"prod{seed}"))
         code_p = run_product(emu_engine_factory(), ["-i", inp_p, "-o", out_p] + case["argv"])
-        assert code_r == code_p == case["exit"], (seed, case["argv"], code_r, code_p)
-        compare(cli_cases.normalise(out_r), cli_cases.normalise(out_p), (seed, case["argv"]))
+        assert rec["exit"] == code_p == case["exit"], (seed, case["argv"], rec["exit"], code_p)
+        compare_recorded(rec, inp_p, cli_cases.normalise(out_p), (seed, case["argv"]))
     assert len(crashed) <= 3, crashed
 
 
-@pytest.mark.skipif(not HAVE_REF, reason="needs /root/reference (build container only)")
-def test_existing_fasta_temp_file_is_reused_like_upstream(tmp_path, emu_engine_factory):
+def test_existing_fasta_temp_file_is_reused_like_upstream(tmp_path, emu_engine_factory, recorded):
     """main.py:64-66: a `<name>_trc_over_<cutoff>.fasta` that is already there is used, not rewritten -- also for FASTQ input."""
-    case = cli_cases.make_case(131)
-    case["argv"] = ["--pattern", case["argv"][1], "--minSeqLength", "1200", "--threads", "1", "--cutoff", "0.5"]
-    rel = next(iter(case["files"]))
-    name = os.path.splitext(os.path.basename(rel))[0]
     # the file the first run wrote = every record as FASTA (upstream's step 2 reads ITS records; the product scans the input)
-    text = case["files"][rel]
-    recs = [(r.description, str(r.seq)) for r in ref_import._parse(__import__("io").StringIO(text), "fastq" if text.startswith("@") else "fasta")]
-    case["pre"] = {f"{name}_trc_over_0.5.fasta": "".join(f">{d}\n{s}\n" for d, s in recs)}
-    case["files"] = {rel: text}
-    case["input"] = rel
-    inp_r, out_r = cli_cases.materialise(case, str(tmp_path / "ref"))
+    case, fasta = cli_cases.existing_fasta_case()
+    rec = recorded_run(recorded["existing_fasta"], case)
     inp_p, out_p = cli_cases.materialise(case, str(tmp_path / "prod"))
-    assert ref_import.run_reference_main(["-i", inp_r, "-o", out_r] + case["argv"]) is None
+    assert rec["exit"] is None
     assert run_product(emu_engine_factory(), ["-i", inp_p, "-o", out_p] + case["argv"]) is None
-    a, b = cli_cases.normalise(out_r), cli_cases.normalise(out_p)
-    compare(a, b, "existing fasta")
-    assert a["filtered"][f"{name}_trc_over_0.5.fasta"] == case["pre"][f"{name}_trc_over_0.5.fasta"]
+    compare_recorded(rec, inp_p, cli_cases.normalise(out_p), "existing fasta")
+    assert rec["expected"]["filtered"][fasta] == cli_cases.digest(case["pre"][fasta])
     assert "Using existing file" in open(os.path.join(out_p, "topsicle_run.log")).read()
 
 
@@ -88,7 +89,7 @@ def compare_replayed(a, b, what):
     """A recorded run against a replay on ANOTHER machine: both CLIs list a directory with os.walk, whose order is the file system's
     (the fixtures were recorded in the build container; the GPU box's scratch directory orders the same three names differently).
     So: per (k, file) the row SEQUENCE must be equal, the k's must come in the recorded order, and the files in ONE order for every k
-    -- everything else (summary lines, filtered files) is compared as it is."""
+    -- everything else (summary lines, filtered files) is compared as it is.  Filtered files recorded as digests are compared by digest."""
     def blocks(rows):
         out, order = {}, []
         for r in rows[1:]:
@@ -117,14 +118,14 @@ def compare_replayed(a, b, what):
     assert a["summary"] == b["summary"], (what, "summary lines")
     assert sorted(a["filtered"]) == sorted(b["filtered"]), (what, "filtered file names")
     for f in a["filtered"]:
-        assert a["filtered"][f] == b["filtered"][f], (what, f)
+        want = a["filtered"][f]
+        assert want == (cli_cases.digest(b["filtered"][f]) if isinstance(want, dict) else b["filtered"][f]), (what, f)
     # rawcount_{k}_{i}.csv is numbered per input file (main.py:90, 150): runs over several files leave, under each name, the LAST file's
     # read -- walk order again -- so their contents are compared for one-file runs only (recorded as digests)
     assert sorted(a.get("rawcount", {})) == sorted(b.get("rawcount", {})), (what, "raw-count file names")
     if len({r[0] for r in (a["csv"] or [])[1:]}) <= 1:
         for f, d in a.get("rawcount", {}).items():
-            t = b["rawcount"][f]
-            assert d == {"sha256": hashlib.sha256(t.encode()).hexdigest(), "bytes": len(t)}, (what, f)
+            assert d == cli_cases.digest(b["rawcount"][f]), (what, f)
 
 
 def golden_cases(gold_dir):
@@ -161,33 +162,26 @@ def test_cli_golden_cases_on_gpu(gold_dir, tmp_path):
 
 
 def _dup_file(tmp_path):
-    import numpy as np
-    rng = np.random.default_rng(9)
-    a = cli_cases.make_read(rng, "CCCTAA", 2600, True, False)
-    b = cli_cases.make_read(rng, "CCCTAA", 1700, True, True)
-    c = cli_cases.make_read(rng, "CCCTAA", 3100, True, True)
     fa = tmp_path / "dups.fasta"
-    fa.write_text(f">dup first\n{b}\n>solo\n{a}\n>dup second\n{c}\n")
-    return str(fa), {"b": b, "a": a, "c": c}
+    return str(fa), cli_cases.write_duplicate_ids_fasta(str(fa))
 
 
-@pytest.mark.skipif(not HAVE_REF, reason="needs /root/reference (build container only)")
-def test_duplicate_read_ids_per_read_api_like_upstream(tmp_path):
+def test_duplicate_read_ids_per_read_api_like_upstream(tmp_path, recorded):
     """Two records with one id (malformed input).  Upstream's bound_detect has no `break` and overwrites maxlengthtelo with the
     first matching record's length when that is shorter (allsteps.py:257-264): the second record is clipped by the shortest
     record before it.  The per-read API reproduces that (6 of 6 fuzz differences were this)."""
     from emu_engine import EmuEngine
     from topsicle_amd import allsteps
-    ref = ref_import.load_reference_allsteps()
     fa, _ = _dup_file(tmp_path)
+    calls = recorded["duplicate_ids"]
+    assert [(c["tail"], c["maxlen"]) for c in calls] == cli_cases.DUP_BOUND_CALLS
     allsteps.set_engine(EmuEngine())
     try:
-        for tail in ("forward", "reverse", None):
-            for M in (20000, 2000, 1500):
-                want = ref.bound_detect(fa, "dup", "CCCTAA", 100, 6, 100, M, 4, tail=tail)
-                got = allsteps.bound_detect(fa, "dup", "CCCTAA", 100, 6, 100, M, 4, tail=tail)
-                assert got == want, (tail, M)
-                assert len(got) == (4 if tail is None else 2)
+        for c in calls:
+            tail, M = c["tail"], c["maxlen"]
+            got = allsteps.bound_detect(fa, "dup", "CCCTAA", 100, 6, 100, M, 4, tail=tail)
+            assert [list(r) for r in got] == c["want"], (tail, M)
+            assert len(got) == (4 if tail is None else 2)
     finally:
         allsteps.set_engine(None)
 
