@@ -263,10 +263,17 @@ constexpr int cgcd(int a, int b) { return b == 0 ? a : cgcd(b, a % b); }
 constexpr int clog2(int x) { return x <= 1 ? 0 : 1 + clog2(x / 2); }
 
 // diagnostics: thread 0 stores the shader clock at phase boundaries when ScanArgs::stamps is set
-#if defined(TPS_EMU) || !defined(TPS_STAMPS)
+// (TPS_ISA_MARKS, scripts/isa_budget.py: the same boundaries and the phases of the sums tiles as comments in the ISA -- a static
+// instruction budget per phase; never in the product library)
+#if defined(TPS_ISA_MARKS) && !defined(TPS_EMU)
+#define TPS_STAMP(i) asm volatile(";tps_stamp %0" ::"i"(i))
+#define TPS_ISA_MARK(id) asm volatile(";tps_mark %0" ::"i"(id))
+#elif defined(TPS_EMU) || !defined(TPS_STAMPS)
 #define TPS_STAMP(i) ((void)0)
+#define TPS_ISA_MARK(id) ((void)(id))
 #else
 #define TPS_STAMP(i) do { if (a.stamps && (threadIdx.x & 63u) == 0) a.stamps[r * 16 + (i)] = __builtin_readcyclecounter(); } while (0)
+#define TPS_ISA_MARK(id) ((void)(id))
 #endif
 // ... inside the per-pattern tiles (first tile of a read only): 6 = phase 1 done, 7 = windows done, 11 = rows out, 12 = candidates done
 #if defined(TPS_EMU) || !defined(TPS_STAMPS)
@@ -1399,9 +1406,19 @@ TPS_DEV Lds carve_fused(uint32_t* base, uint32_t* lut, const ScanArgs& a) {
 // XS aliases row[]: the only reader of XS[w] is the lane that then writes row[w].
 // Windows beyond nw_tile (they need blocks of the next tile) are not produced.
 #ifdef TPS_EMU
-inline int& emu_counter(int i) { static int c[8] = {0, 0, 0, 0, 0, 0, 0, 0}; return c[i]; }   // tests: 0 = per-pattern tiles, 1 = windows recounted there, 4 = exact change-point tournaments, 5 = sums tiles of a self-overlap table with chains corrected, 6 = ... without a chain
+inline int& emu_counter(int i) { static int c[8] = {0, 0, 0, 0, 0, 0, 0, 0}; return c[i]; }   // tests: 0 = per-pattern tiles, 1 = windows recounted there, 4 = exact change-point tournaments, 5 = sums tiles of a self-overlap table with chains corrected, 6 = ... without a chain, 3 = sums tiles with the window phase in 16-bit pairs, 7 = sums tiles that store their candidates lane by lane
 #endif
 TPS_DEV uint32_t pack_hi_lo(uint32_t hi_src, uint32_t lo_src) { return perm(hi_src, lo_src, 0x07060100u); }
+// two 16-bit lanes in one word (lane 0 = bits 0 .. 15): lane-wise a - b; a + the low half of b in both
+#ifdef TPS_EMU
+TPS_DEV uint32_t pk_u16_sub(uint32_t a, uint32_t b) { return ((a - b) & 0xFFFFu) | (((a >> 16) - (b >> 16)) << 16); }
+TPS_DEV uint32_t pk_u16_add(uint32_t a, uint32_t b) { return ((a + b) & 0xFFFFu) | (((a >> 16) + b) << 16); }
+#else
+typedef unsigned short tps_u16x2 __attribute__((ext_vector_type(2)));
+TPS_DEV tps_u16x2 as_u16x2(uint32_t v) { return __builtin_bit_cast(tps_u16x2, v); }
+TPS_DEV uint32_t pk_u16_sub(uint32_t a, uint32_t b) { return __builtin_bit_cast(uint32_t, as_u16x2(a) - as_u16x2(b)); }                                          // v_pk_sub_u16
+TPS_DEV uint32_t pk_u16_add(uint32_t a, uint32_t b) { return __builtin_bit_cast(uint32_t, as_u16x2(a) + (tps_u16x2)((unsigned short)b)); }                     // v_pk_add_u16 op_sel_hi:[1,0]
+#endif
 
 // RAW: this instantiation can also produce the per-pattern counts (TPS_F_STORE_RAW); the kernels without it carry
 // no recount code at all unless the table has self-overlapping k-mers.
@@ -1883,10 +1900,15 @@ TPS_DEV void tile_candidates(const TileConst& tc, const Lds& l, int w0, int tile
 #define TPS_STORE_AUX 2
 #endif
 // the lane's 8 window sums -> tile_out[8 lane .. 8 lane + 7] as 16-bit values, windows at or past nw_tile dropped
+// (g_store_sw8p: the same from the 4 words of 16-bit pairs, window 2 i in the low half of word i)
 #ifdef TPS_EMU
 TPS_DEV void g_store_sw8(uint16_t* tile_out, int lane, int nw_tile, const uint32_t* v) {
     for (int i = 0; i < 8; ++i)
         if (8 * lane + i < nw_tile) tile_out[8 * lane + i] = (uint16_t)v[i];
+}
+TPS_DEV void g_store_sw8p(uint16_t* tile_out, int lane, int nw_tile, const uint32_t* p) {
+    for (int i = 0; i < 8; ++i)
+        if (8 * lane + i < nw_tile) tile_out[8 * lane + i] = (uint16_t)(p[i >> 1] >> (16 * (i & 1)));
 }
 #else
 TPS_DEV void g_store_sw8(uint16_t* tile_out, int lane, int nw_tile, const uint32_t* v) {
@@ -1900,6 +1922,13 @@ TPS_DEV void g_store_sw8(uint16_t* tile_out, int lane, int nw_tile, const uint32
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)tile_out, 0, ((nw_tile + 1) & ~1) * 2, 0x00020000);
     v4u t;
     t.x = v[0] | (v[1] << 16); t.y = v[2] | (v[3] << 16); t.z = v[4] | (v[5] << 16); t.w = v[6] | (v[7] << 16);      // (v_lshl_or_b32; every S_w < 2^16)
+    __builtin_amdgcn_raw_buffer_store_b128(t, rs, lane * 16, 0, TPS_STORE_AUX);
+}
+TPS_DEV void g_store_sw8p(uint16_t* tile_out, int lane, int nw_tile, const uint32_t* p) {
+    typedef unsigned int v4u __attribute__((ext_vector_type(4)));
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)tile_out, 0, ((nw_tile + 1) & ~1) * 2, 0x00020000);
+    v4u t;
+    t.x = p[0]; t.y = p[1]; t.z = p[2]; t.w = p[3];
     __builtin_amdgcn_raw_buffer_store_b128(t, rs, lane * 16, 0, TPS_STORE_AUX);
 }
 #endif
@@ -2012,6 +2041,9 @@ TPS_DEV void tile_lc_s(const ScanArgs& a, const TileConst& tc, const Lds& l, int
             if (cur != prev) lds_add(&l.row[w + (w >> LOG2B)], (uint32_t)(cur - prev));
         }
     };
+    // (TPS_ISA_MARKS) phase p of this instantiation: p + 10 S + 1000 (RPT + 1) + 10^5 ROTZ + 10^6 PAIR + 10^7 INV + 10^8 (CD or P16)
+    constexpr int MK = 10 * S + 1000 * (RPT + 1) + 100000 * ROTZ + 1000000 * PAIR + 10000000 * INV + 100000000 * (CD > 0 || P16_);
+    TPS_ISA_MARK(MK + 1);                         // 1: phase 1 (the lanes' blocks, the published words)
     TPS_PHASE {
         const int span = tid;
         const int p0 = delta + span * POS;        // >= 16: fused tiles are staged behind SEQ_LEAD words
@@ -2303,11 +2335,13 @@ TPS_DEV void tile_lc_s(const ScanArgs& a, const TileConst& tc, const Lds& l, int
     }
     TPS_SYNC();
     if (w0 == 0) TPS_STAMP(6);
+    TPS_ISA_MARK(MK + 2);                         // 2: the window phase
     const int rot = ROTZ ? 0 : (q & (B - 1)), dl0 = q >> LOG2B;
     const int brk = B - rot;                      // windows j >= brk end one lane further on
-    uint32_t sw[B], ltot = 0;
+    constexpr bool SWP = CD == 0 && !M16 && ROTZ;     // (round 6) the window phase in 16-bit pairs (below)
+    uint32_t sw[B], swp[B / 2], ltot = 0;           // (SWP) swp[i]: S_w of windows 2 i and 2 i + 1 as the 16-bit pair the store writes
 #ifdef TPS_EMU
-    uint32_t sw_keep[NT][B], tot_keep[NT];
+    uint32_t sw_keep[NT][B], swp_keep[NT][B / 2], tot_keep[NT];
 #endif
     TPS_PHASE {
 #ifdef TPS_EMU
@@ -2337,22 +2371,49 @@ TPS_DEV void tile_lc_s(const ScanArgs& a, const TileConst& tc, const Lds& l, int
             sumb += vb;
         }
         const uint32_t am = pat.all_mask << 16;
+        // (round 6) the absent patterns as ONE three-input NOR: the skipped lanes' OR also carries every bit outside the
+        // pattern mask (the count half, the unused pattern bits), so ~(sfx | e | orw) is already ~m & am (v_bitop3_b32)
+        orw |= ~am;
+        orb |= ~am;
         uint32_t run = 0;
+        if constexpr (SWP) {
+#ifdef TPS_EMU
+            if (tid == 0) ++emu_counter(3);
+#endif
+            // (round 6) the home shape: every window has the same far lane, so two windows' counts go through one packed
+            // 16-bit subtract and add (v_pk_sub / v_pk_add_u16 on the low halves: exact modulo 2^16, as the & 0xFFFF was) and
+            // leave as the 16-bit pair the S_w store writes (g_store_sw8p); the absent patterns go into the low window's half
+            // (S_w < 2^16: no carry into the high one) and the high window's half
+            uint32_t lo_lo = 0x05040100u;             // v_perm_b32 selector: the low halves of two words (set per tile: no SGPR held across the read)
+            TPS_PIN_S(lo_lo);
+            TPS_UNROLL
+            for (int j = 0; j < B; j += 2) {
+                const uint32_t ep = perm(ev[j + 1], ev[j], lo_lo), cp = perm(c0s[j + 1], c0s[j], lo_lo);
+                const uint32_t d = pk_u16_add(pk_u16_sub(ep, cp), sumw);
+                const uint32_t p = (uint32_t)popc(~(sfx[j] | ev[j] | orw)) + d;
+                swp[j >> 1] = p + ((uint32_t)popc(~(sfx[j + 1] | ev[j + 1] | orw)) << 16);
+                sw[j] = swp[j >> 1] & 0xFFFFu;
+                sw[j + 1] = swp[j >> 1] >> 16;
+                run += sw[j] + sw[j + 1];
+            }
+        } else {
         TPS_UNROLL
         for (int j = 0; j < B; ++j) {
             const bool far_ = !ROTZ && j >= brk;
             const uint32_t e = ev[j], fo = far_ ? orb : orw, fs = far_ ? sumb : sumw;
-            const uint32_t m = sfx[j] | e | fo;                 // presence: high halves
             const uint32_t c = (e - c0s[j] + fs) & 0xFFFFu;     // matches: low halves (CD: matches | pairs << 8)
-            sw[j] = (CD > 0 ? (c & 0xFFu) - (c >> 8) : c) + (uint32_t)popc(~m & am);
+            sw[j] = (CD > 0 ? (c & 0xFFu) - (c >> 8) : c) + (uint32_t)popc(~(sfx[j] | e | fo));     // presence: high halves
             run += sw[j];
+        }
         }
         ltot = run;
 #ifdef TPS_EMU
         for (int j = 0; j < B; ++j) sw_keep[tid][j] = sw[j];
+        if (SWP) for (int j = 0; j < B / 2; ++j) swp_keep[tid][j] = swp[j];
         tot_keep[tid] = ltot;
 #endif
     }
+    TPS_ISA_MARK(MK + 3);                         // 3: lane scan, S_w out, prefixes (and the lanes' own candidates)
     if constexpr (CD > 0) {
         // a chain somewhere in the tile: the windows give back what the chains' skipped occurrences added -- the prefix sum of
         // the difference array, lane-contiguous like the windows themselves
@@ -2410,14 +2471,21 @@ TPS_DEV void tile_lc_s(const ScanArgs& a, const TileConst& tc, const Lds& l, int
         lexc = inc - ltot;
     }
 #endif
+    // (round 6) the sums-only tiles with absolute 32-bit candidate sums off chip: every lane stores its own candidates' left
+    // sums right behind its prefixes -- no candidate-strided pass over row[] (the lc16 and LDS-Lc layouts, jump < 4 and the
+    // chain-corrected / 16-bit-table tiles keep that pass)
+    bool lane_cands = false;
+    if constexpr (CD == 0 && !M16) lane_cands = tc.lc_g != 0ull && !tc.lc16 && tc.jump >= 4u;     // (uniform)
     TPS_PHASE {
 #ifdef TPS_EMU
         for (int j = 0; j < B; ++j) sw[j] = sw_keep[tid][j];
+        if (SWP) for (int j = 0; j < B / 2; ++j) swp[j] = swp_keep[tid][j];
         lexc = exc_keep[tid];
 #endif
         const int lane = tid;
 #ifndef TPS_NO_SW_STORE                               /* (diagnostic builds only: what do the S_w stores cost?) */
-        g_store_sw8(tc.sw16 + w0, lane, nw_tile, sw);
+        if constexpr (SWP) g_store_sw8p(tc.sw16 + w0, lane, nw_tile, swp);
+        else g_store_sw8(tc.sw16 + w0, lane, nw_tile, sw);
 #endif
         // what the candidate phase reads: every window's exclusive prefix inside its LANE (padded layout) and every lane's
         // exclusive prefix inside the tile
@@ -2426,9 +2494,24 @@ TPS_DEV void tile_lc_s(const ScanArgs& a, const TileConst& tc, const Lds& l, int
         TPS_UNROLL
         for (int j = 0; j < B; ++j) { pr[j] = run; run += sw[j]; }
         xt_at(lane) = lexc;
+        if (lane_cands) {
+#ifdef TPS_EMU
+            if (tid == 0) ++emu_counter(7);
+#endif
+            // (round 6) the change-point candidates among the lane's own windows, read back from its own row (no barrier): the
+            // first is window f = c jump - (w0 + 8 lane) of the lane, the second f + jump; jump >= 4 leaves no room for a third
+            const uint32_t carry = (uint32_t)s_total + lexc;
+            const uint32_t wl = (uint32_t)(lane * B), wa = (uint32_t)w0 + wl;
+            const uint32_t c = mulhi32(wa + tc.jump - 1u, tc.jump_magic);     // (div_jump without its jump = 1 case)
+            const uint32_t f = c * tc.jump - wa;
+            if (f < (uint32_t)B && wl + f < (uint32_t)nw_tile && c < tc.lc_cap) g32_store(tc.lc_g, c, carry + pr[f]);
+            const uint32_t f2 = f + tc.jump;
+            if (f2 < (uint32_t)B && wl + f2 < (uint32_t)nw_tile && c + 1u < tc.lc_cap) g32_store(tc.lc_g, c + 1u, carry + pr[f2]);
+        }
     }
     TPS_SYNC();
     if (w0 == 0) TPS_STAMP(12);
+    TPS_ISA_MARK(MK + 4);                         // 4: the tile's total
     // the tile's total = the prefix at its first window that is NOT part of it (nw_tile <= 512 - q - 1: a written entry)
     const uint32_t gsum = uniform(l.row[nw_tile + (nw_tile >> LOG2B)] + xt_at(nw_tile >> LOG2B));
     {
@@ -2437,7 +2520,8 @@ TPS_DEV void tile_lc_s(const ScanArgs& a, const TileConst& tc, const Lds& l, int
         const uint32_t c_lo = div_jump((uint32_t)w0 + jump - 1u, tc.jump_magic);
         uint32_t c_hi = div_jump((uint32_t)(w0 + nw_tile) + jump - 1u, tc.jump_magic);
         if (c_hi > tc.lc_cap) c_hi = tc.lc_cap;
-        const int passes = c_hi > c_lo ? (int)((c_hi - c_lo + NT - 1) / NT) : 0;
+        const int passes = (c_hi > c_lo && !lane_cands) ? (int)((c_hi - c_lo + NT - 1) / NT) : 0;     // (lane_cands: stored above)
+        TPS_ISA_MARK(MK + 6);                     // 6: the candidate-strided pass itself
         TPS_PHASE {
             const uint32_t carry = (uint32_t)s_total;
             if (tid == 0) { l.misc[M_INVALID] = 0; l.misc[M_NTIE] = 0; }      // for the next tile's staging
@@ -2463,6 +2547,7 @@ TPS_DEV void tile_lc_s(const ScanArgs& a, const TileConst& tc, const Lds& l, int
         }
     }
     s_total += gsum;
+    TPS_ISA_MARK(MK + 5);                         // 5: tile done
     TPS_SYNC();
     (void)r;
 }
