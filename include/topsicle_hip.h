@@ -76,6 +76,15 @@ typedef struct tps_read_desc {
 } tps_read_desc;
 #define TPS_RD_HAS_INVALID 1u   /* the read holds at least one base that is not acgtACGT (inv is consulted) */
 
+/* Where one read of a nib4 batch (tps_batch_upload_nib4) keeps its bases: BAM's 4-bit codes as stored (SAMv1 4.2.3,
+ * "=ACMGRSVTWYHKDBN" = 0..15, two per byte, high nibble first), from byte `off` (a multiple of 16) of the nibble buffer. */
+typedef struct tps_nib_src {
+    int64_t  off;         /* byte offset of the read's first nibble pair in the nibble buffer; a multiple of 16            */
+    uint32_t flags;       /* TPS_NIB_*                                                                                       */
+    uint32_t reserved;
+} tps_nib_src;
+#define TPS_NIB_REVERSE 1u      /* the record is reverse-strand (BAM flag 0x10): the read is the reverse complement of the codes */
+
 /* Parameters of one scan.  Names follow the reference CLI (Topsicle/main.py:319-334). */
 typedef struct tps_params {
     int32_t no_bp;        /* step-1 tail length; reference hard-codes 1000 (main.py:57)        */
@@ -140,6 +149,14 @@ int  tps_batch_upload(tps_ctx* ctx, int32_t slot, const uint8_t* bases, const in
  * slot) has returned; ordinary memory is copied before the call returns. */
 int  tps_batch_upload_packed(tps_ctx* ctx, int32_t slot, const uint32_t* seq2, const uint16_t* inv,
                              const tps_read_desc* desc, int64_t n_reads, int64_t n_words);
+/* The same for a batch of BAM records (libtopsicle_io.so's tps_reader_next_nib4): nib[nib_bytes] holds each read's 4-bit codes as
+ * stored, src[i] says where and whether the read is reverse-strand, desc[i] is the read's descriptor in the packed layout (word_off,
+ * len, TPS_RD_HAS_INVALID exactly as the packers set it; tps::pack_layout of the lengths).  A read's codes take (len + 1) / 2 bytes,
+ * rounded up to 16, from src[i].off on.  A device kernel expands the codes into seq2 / inv (reverse-strand reads reverse-complemented;
+ * an IUPAC letter gets the code its ASCII gives, as in tps_batch_upload): the slot then holds an ordinary packed batch.  Pinned
+ * sources are copied asynchronously, like tps_batch_upload_packed. */
+int  tps_batch_upload_nib4(tps_ctx* ctx, int32_t slot, const uint8_t* nib, int64_t nib_bytes, const tps_nib_src* src,
+                           const tps_read_desc* desc, int64_t n_reads, int64_t n_words);
 /* Make `slot` of `ctx` refer to the resident packed batch of `src_slot` of ANOTHER context on the same device (no copy; the
  * batch stays owned by `src`, which must neither upload into that slot nor be destroyed while the borrower may still scan it;
  * `ctx`'s stream waits for `src`'s pending upload).  Several pattern tables over one batch -- `--telophrase 4 5 6`, the

@@ -26,7 +26,13 @@ const char* tps_io_last_error(void);
 
 /* ---- reader ---------------------------------------------------------------------------------------------------------------- */
 /* Opens a FASTA / FASTQ file, plain or gzip'ed (ordinary gzip and BGZF are told apart by their headers).  The format comes from
- * the first character of the first line, like check_file_type (allsteps.py:36-50).  0, or -1 (unreadable, unknown format). */
+ * the first character of the first line, like check_file_type (allsteps.py:36-50).  0, or -1 (unreadable, unknown format).
+ * A BGZF file whose text starts with "BAM\1" is read as BAM (format 3; SAMv1 section 4.2), unaligned or aligned: records flagged
+ * secondary (0x100) or supplementary (0x800) are skipped, reverse-strand ones (0x10) are given back in the sequencer's orientation
+ * (bases reverse-complemented, qualities reversed), records without bases stay as zero-length reads; the read's id is its
+ * read_name.  CIGAR, mapping fields and aux tags are not looked at -- what `samtools fastq` gives by default.  A record without
+ * stored qualities (0xFF) gets '!' for every base.  BAM leaves as ASCII batches (tps_reader_next) or nib4 batches
+ * (tps_reader_next_nib4); tps_reader_next_packed / _heads and byte ranges refuse it. */
 int  tps_reader_open(const char* path, void** out);
 /* One reader per BYTE RANGE of a plain (uncompressed) file: the records that START in [lo, hi) -- the first one found like a team
  * thread finds the first record of its stretch, the last one decoded to its end beyond hi.  Readers over adjacent ranges partition
@@ -36,7 +42,7 @@ int  tps_reader_open(const char* path, void** out);
  * i + 1 began (the caller's seam check; FASTQ framing is a heuristic only at a range's first record).  Compressed input: -1. */
 int  tps_reader_open_range(const char* path, int64_t lo, int64_t hi, int32_t threads, void** out);
 int  tps_reader_range_info(void* reader, int64_t* first_record, int64_t* stopped_at);
-/* 0 = empty file, 1 = FASTA, 2 = FASTQ. */
+/* 0 = empty file, 1 = FASTA, 2 = FASTQ, 3 = BAM. */
 int  tps_reader_format(void* reader);
 void tps_reader_close(void* reader);
 /* ASCII batches -- what SeqIO.parse yields (allsteps.py:127-149), for inputs the packed decoder declines and for the per-read API:
@@ -58,6 +64,13 @@ int64_t tps_reader_next_packed(void* reader, uint32_t* seq2, uint16_t* inv, int6
 int64_t tps_reader_next_heads(void* reader, int32_t heads_bp, uint32_t* seq2, uint16_t* inv, int64_t words_cap, tps_read_desc* desc,
                               int64_t max_records, char* heads, int64_t heads_cap, int64_t* head_off, int64_t* spans, int32_t* full_len,
                               int64_t* n_words);
+/* BAM: a batch of records as they are stored -- nib (8 x words_cap bytes) receives each record's 4-bit base codes, from a 16-byte
+ * boundary on ((len + 1) / 2 bytes, zero-padded to 16), src[i] where and TPS_NIB_REVERSE, desc[i] the read in the packed layout
+ * (tps_pack.h; TPS_RD_HAS_INVALID exact) -- what tps_batch_upload_nib4 takes; heads / head_off receive the read names; spans (may be
+ * NULL) 4 entries per record into the window of tps_reader_text_hold: name offset, name length, seq offset, qual offset.  *n_words =
+ * words the batch takes packed, *nib_bytes = bytes of nib used.  Returns like tps_reader_next_packed (-1 also: not a BAM reader). */
+int64_t tps_reader_next_nib4(void* reader, uint8_t* nib, tps_nib_src* src, int64_t words_cap, tps_read_desc* desc, int64_t max_records,
+                             char* heads, int64_t heads_cap, int64_t* head_off, int64_t* spans, int64_t* n_words, int64_t* nib_bytes);
 /* Compressed input: the window of inflated text the LAST packed batch's spans point into (*text, *len) and a reference on it
  * (*hold; NULL for a plain file, whose text is the file itself), to be given back with tps_text_release when the batch's records
  * have been written. */
@@ -76,6 +89,12 @@ int64_t tps_packed_words_total(const int64_t* offsets, int64_t n);
 int64_t tps_pack_reads(const uint8_t* bases, const int64_t* offsets, int64_t n, uint32_t* seq2, uint16_t* inv, tps_read_desc* desc,
                        int32_t nthreads);
 
+/* A nib4 batch into the packed format (the host reference of tps_batch_upload_nib4's kernel): the lengths of desc_in lay the batch
+ * out (tps::pack_layout), seq2 / inv receive the reads, desc their descriptors with TPS_RD_HAS_INVALID.  Returns the words or -1 (a
+ * read outside nib_bytes, words_cap too small). */
+int64_t tps_pack_nib4(const uint8_t* nib, int64_t nib_bytes, const tps_nib_src* src, const tps_read_desc* desc_in, int64_t n, uint32_t* seq2,
+                      uint16_t* inv, tps_read_desc* desc, int64_t words_cap);
+
 /* ---- writers --------------------------------------------------------------------------------------------------------------- */
 /* The records idx[0 .. n) of a packed FASTQ batch to `fd` in SeqIO.write's layout (main.py:83-86): writev straight from the
  * text the spans point into.  Returns the bytes written or -1. */
@@ -85,6 +104,11 @@ int64_t tps_write_fastq_spans(int fd, const char* text, int64_t text_len, const 
 int64_t tps_write_fastq_spans_at(int fd, int64_t file_off, const char* text, int64_t text_len, const int64_t* spans, const int32_t* lens,
                                  const int64_t* idx, int64_t n);
 int64_t tps_fastq_spans_bytes(const int64_t* spans, const int32_t* lens, const int64_t* idx, int64_t n);
+/* The same for the records of a BAM batch (spans of tps_reader_next_nib4): "@" name "\n" bases "\n+\n" qualities + 33 "\n",
+ * reverse-strand records reverse-complemented and their qualities reversed, '!' for every base of a record without stored
+ * qualities.  A record takes tps_fastq_spans_bytes's count.  Returns the bytes written or -1. */
+int64_t tps_write_bam_fastq_spans_at(int fd, int64_t file_off, const char* text, int64_t text_len, const int64_t* spans, const int32_t* lens,
+                                     const int64_t* idx, int64_t n);
 /* zlib's crc32(crc, p, n) by carry-less multiplication (the checksum callback of tps_batch_raw_to_fd) and crc32_combine. */
 uint32_t tps_crc32(uint32_t crc, const uint8_t* p, int64_t n);
 uint32_t tps_crc32_combine(uint32_t crc1, uint32_t crc2, int64_t len2);

@@ -9,6 +9,7 @@ context, two contexts per GPU -- pull batches from ONE shared queue (dynamic bal
 """
 from __future__ import annotations
 
+import logging
 import os
 import queue
 import threading
@@ -70,15 +71,24 @@ def _sink_rows(job, seq, eng, slot, recs, res, slot_index=None):
 
 
 def upload_batch(engine, recs, slot: int = 0):
-    """A seqio.PackedBatch is uploaded as it is (3 bits per base); a seqio.RecordBatch or a list of records goes up as
-    ASCII and is packed on the device."""
-    if hasattr(recs, "seq2"):
+    """A seqio.PackedBatch is uploaded as it is (3 bits per base; a BAM batch as its 4-bit codes, expanded on the device); a
+    seqio.RecordBatch or a list of records goes up as ASCII and is packed on the device."""
+    if getattr(recs, "nib", None) is not None:
+        # BAM records as stored: 4-bit codes + per-read source + descriptors, expanded on the device
+        recs.uploaded_bytes = len(recs.nib) + 32 * len(recs.desc)
+        engine.upload_nib4(slot, recs.nib, recs.src, recs.desc, recs.n_words)
+    elif hasattr(recs, "seq2"):
         recs.uploaded_bytes = 4 * len(recs.seq2) + (2 * len(recs.inv) if recs.any_invalid else 0) + 16 * len(recs.desc)
         engine.upload_packed(slot, recs.seq2, recs.inv if recs.any_invalid else None, recs.desc)
     elif hasattr(recs, "bases"):
         engine.upload(slot, recs.bases, recs.offsets)
     else:
         engine.upload(slot, *hiplib.pack_reads([r.seq for r in recs]))
+
+
+def seqio_is_bam(filepath) -> bool:
+    from . import seqio
+    return seqio.is_bam(filepath)
 
 
 TWO_PASS_MAX_PASSING = 0.25      # heads mode stays on while at most this share of a batch's reads passes step 1
@@ -321,7 +331,9 @@ class EnginePool:
         reads_cap = min(BATCH_READS, max(64, max_bases // 256))
         jobs = list(jobs)
         ranges = None
-        if shards and shards > 1 and not any(j.want_sums or j.want_raw for j in jobs):
+        if shards and shards > 1 and seqio.is_bam(filepath):
+            logging.info("%s: BAM has no record index: one reader (--shards %d ignored; its blocks still inflate on the team)", filepath, shards)
+        elif shards and shards > 1 and not any(j.want_sums or j.want_raw for j in jobs):
             ranges = seqio.shard_ranges(filepath, shards, shard_min_bytes)
         if not ranges:
             pool = self._staging_pool(words_cap, reads_cap)
@@ -371,6 +383,12 @@ class EnginePool:
         telomere-enriched file (the demo, the synthetic benchmarks: every read passes) drops to the one-pass route after its
         first batch -- there the second pass would upload what the first one spared."""
         mode = self.two_pass
+        if mode != "off" and filepath is not None and seqio_is_bam(filepath):
+            # BAM goes up whole: its reader is inflate-bound (~1e9 - 4e9 bases/s), and whole reads cost the GPU ~3e-13 s and PCIe
+            # ~0.5 byte per base -- the heads route would save nothing measurable (an estimate)
+            if mode == "on":
+                logging.info("%s: BAM input is scanned as whole reads (--twopass on does not apply)", filepath)
+            mode = "off"
         if mode == "auto" and filepath is not None:
             try:
                 small = os.path.getsize(filepath) < (AUTO_MIN_FILE_BYTES // 4 if str(filepath).endswith(".gz") else AUTO_MIN_FILE_BYTES)

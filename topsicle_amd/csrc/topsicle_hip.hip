@@ -110,6 +110,58 @@ extern "C" __global__ void __launch_bounds__(256) tps_pack_kernel(const uint8_t*
     }
 }
 
+// BAM's 4-bit base codes -> packed batch (tps_batch_upload_nib4), one workgroup per read, one thread per word of 16 bases.  A word's
+// 16 codes are one 64-bit load (two for a reverse-strand read, whose window starts at any code: a funnel shift), the two codes of each
+// byte swapped so that code t sits in nibble t; v_bfrev of the 64 bits then reverses the order of the codes AND complements each of
+// them (on these codes the IUPAC complement is the bit reversal of the code: A = 1 <-> T = 8, C = 2 <-> G = 4, ...).  Code c becomes
+// the 2-bit code of its letter's ASCII ((ASCII >> 1) & 3: "=ACMGRSVTWYHKDBN" -> NIB4_CODE2) and is flagged in inv unless it is one of
+// A, C, G, T: bit-identical to tps_pack_kernel on the records' ASCII text.  A read's codes take whole 16-byte units of the nibble
+// buffer from a 16-byte boundary on (the host checks it), so a 64-bit load that holds one of its codes never leaves them.
+constexpr uint32_t NIB4_CODE2 = 0xd90ed792u;         // bits [2c, 2c+1]: the code of BAM letter c
+constexpr uint32_t NIB4_ACGT = 0x0116u;              // bit c: code c is one of A (1), C (2), G (4), T (8)
+__device__ __forceinline__ uint64_t nib_swap(uint64_t v) { return ((v >> 4) & 0x0F0F0F0F0F0F0F0Full) | ((v & 0x0F0F0F0F0F0F0F0Full) << 4); }
+extern "C" __global__ void __launch_bounds__(256) tps_pack_kernel_nib4(const uint8_t* nib, const tps_nib_src* src, const tps_read_desc* desc,
+                                                                        uint32_t* seq2, uint16_t* inv, int64_t n_reads) {
+    const int64_t r = blockIdx.x;
+    if (r >= n_reads) return;
+    const int64_t L = desc[r].len;
+    const int64_t w0 = desc[r].word_off;
+    const int64_t nw = ((L + 63) / 64) * 4;
+    const uint64_t* q = (const uint64_t*)(nib + src[r].off);
+    const bool rev = (src[r].flags & TPS_NIB_REVERSE) != 0u;
+    for (int64_t w = threadIdx.x; w < nw; w += 256) {
+        const int64_t left = L - 16 * w;               // bases of this word (<= 0: padding up to the quad boundary)
+        uint32_t packed = 0, bad = 0;
+        if (left > 0) {
+            uint64_t x;
+            if (!rev) {
+                x = nib_swap(q[w]);
+            } else {
+                // output bases 16 w .. 16 w + 15 are the complements of stored codes L - 1 - 16 w down to a = L - 16 - 16 w (a < 0 only
+                // in the read's last word, where the codes below 0 land on output bases >= L and are masked off)
+                const int64_t a = L - 16 - 16 * w;
+                const int64_t qa = a >> 4;                                       // (floor division)
+                const uint32_t sh = (uint32_t)(a & 15) * 4u;
+                const uint64_t lo = qa >= 0 ? nib_swap(q[qa]) : 0ull;
+                x = sh ? (lo >> sh) | (nib_swap(q[qa + 1]) << (64u - sh)) : lo;
+                x = __brevll(x);
+            }
+#pragma unroll
+            for (int t = 0; t < 16; ++t) {
+                const uint32_t c = (uint32_t)(x >> (4 * t)) & 15u;
+                packed |= ((NIB4_CODE2 >> (2 * c)) & 3u) << (2 * t);
+                bad |= ((~NIB4_ACGT >> c) & 1u) << t;
+            }
+            if (left < 16) {
+                packed &= (1u << (2 * (int)left)) - 1u;
+                bad &= (1u << (int)left) - 1u;
+            }
+        }
+        seq2[w0 + w] = packed;
+        inv[w0 + w] = (uint16_t)bad;
+    }
+}
+
 // ======================================================================== host side
 namespace {
 
@@ -217,6 +269,7 @@ struct tps_ctx {
     size_t table_rr = 0;
     DevBuf follow_picks, follow_hist; // outputs of tps_batch_kmer_followers
     DevBuf ascii, ascii_off;          // staging of tps_batch_upload: ASCII bases + offsets, packed on the device right after the copy
+    DevBuf nib, nib_src;              // staging of tps_batch_upload_nib4: BAM base codes + where each read's are, expanded right after the copy
     std::set<void*> pinned;           // host buffers handed out by tps_host_alloc
     std::vector<tps_read_desc> h_desc;   // scratch of the ASCII upload path
     tps::PatInfo pat{};
@@ -346,6 +399,49 @@ int do_upload_packed(tps_ctx* c, Slot& sl, const uint32_t* seq2, const uint16_t*
     const bool all_pinned = is_pinned(seq2, (size_t)n_words * 4) && is_pinned(inv, inv ? (size_t)n_words * 2 : 0) && is_pinned(desc, (size_t)n * sizeof(tps_read_desc));
     if (!all_pinned) HIP_TRY(hipStreamSynchronize(c->stream));     // ordinary memory: the copy is over when the call returns
     sl.inv_valid = inv != nullptr;
+    sl.any_invalid = flagged;
+    reset_slot(sl, n, n_words);
+    return TPS_OK;
+}
+
+// BAM records: their 4-bit codes, where each read's are and the descriptors go up; tps_pack_kernel_nib4 writes seq2 / inv.  Pinned
+// sources (tps_host_alloc) are copied asynchronously.  The descriptors come from the caller with exact TPS_RD_HAS_INVALID flags.
+int do_upload_nib4(tps_ctx* c, Slot& sl, const uint8_t* nib, int64_t nib_bytes, const tps_nib_src* src, const tps_read_desc* desc, int64_t n,
+                   int64_t n_words) {
+    if (n < 0 || n_words < 0 || nib_bytes < 0 || (n > 0 && (!desc || !src)) || (nib_bytes > 0 && !nib)) return fail(TPS_E_ARG, "bad nib4 batch pointers");
+    sl.h_offsets.resize((size_t)n + 1);
+    int64_t acc = 0;
+    bool flagged = false;
+    for (int64_t i = 0; i < n; ++i) {
+        const tps_read_desc& d = desc[i];
+        if (d.len < 0 || d.word_off < 0 || (d.word_off & 3) || d.word_off + tps::packed_words(d.len) > n_words)
+            return fail(TPS_E_ARG, "read %lld: descriptor outside the packed batch (word_off %lld, len %d, %lld words)", (long long)i,
+                        (long long)d.word_off, d.len, (long long)n_words);
+        const int64_t units = (((int64_t)d.len + 1) / 2 + 15) & ~(int64_t)15;            // the 16-byte units the kernel may load from
+        if (src[i].off < 0 || (src[i].off & 15) || src[i].off + units > nib_bytes)
+            return fail(TPS_E_ARG, "read %lld: codes outside the nibble buffer (off %lld, len %d, %lld bytes)", (long long)i,
+                        (long long)src[i].off, d.len, (long long)nib_bytes);
+        sl.h_offsets[(size_t)i] = acc;
+        acc += d.len;
+        flagged = flagged || (d.flags & TPS_RD_HAS_INVALID);
+    }
+    sl.h_offsets[(size_t)n] = acc;
+    int rc;
+    if ((rc = ensure_packed(sl, n, n_words))) return rc;
+    if ((rc = c->nib.ensure((size_t)std::max<int64_t>(nib_bytes, 16)))) return rc;
+    if ((rc = c->nib_src.ensure((size_t)std::max<int64_t>(n, 1) * sizeof(tps_nib_src)))) return rc;
+    if (nib_bytes) HIP_TRY(hipMemcpyAsync(c->nib.p, nib, (size_t)nib_bytes, hipMemcpyHostToDevice, c->stream));
+    if (n) {
+        HIP_TRY(hipMemcpyAsync(c->nib_src.p, src, (size_t)n * sizeof(tps_nib_src), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(sl.desc.p, desc, (size_t)n * sizeof(tps_read_desc), hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(tps_pack_kernel_nib4, dim3((unsigned)n), dim3(256), 0, c->stream, (const uint8_t*)c->nib.p,
+                           (const tps_nib_src*)c->nib_src.p, (const tps_read_desc*)sl.desc.p, (uint32_t*)sl.seq2.p, (uint16_t*)sl.inv.p, n);
+        HIP_TRY(hipGetLastError());
+    }
+    const bool all_pinned = is_pinned(nib, (size_t)nib_bytes) && is_pinned(src, (size_t)n * sizeof(tps_nib_src)) &&
+                            is_pinned(desc, (size_t)n * sizeof(tps_read_desc));
+    if (!all_pinned) HIP_TRY(hipStreamSynchronize(c->stream));     // ordinary memory: the copy is over when the call returns
+    sl.inv_valid = true;
     sl.any_invalid = flagged;
     reset_slot(sl, n, n_words);
     return TPS_OK;
@@ -710,6 +806,8 @@ int tps_ctx_destroy(tps_ctx* c) {
     for (auto& t : c->tables) t.dev.release();
     c->ascii.release();
     c->ascii_off.release();
+    c->nib.release();
+    c->nib_src.release();
     c->follow_picks.release();
     c->follow_hist.release();
     for (void* hp : c->pinned) {
@@ -842,6 +940,15 @@ int tps_batch_upload_packed(tps_ctx* c, int32_t slot, const uint32_t* seq2, cons
     Slot* sl = get_slot(c, slot);
     if (!sl) return TPS_E_ARG;
     return do_upload_packed(c, *sl, seq2, inv, desc, n, n_words);
+}
+
+int tps_batch_upload_nib4(tps_ctx* c, int32_t slot, const uint8_t* nib, int64_t nib_bytes, const tps_nib_src* src, const tps_read_desc* desc,
+                          int64_t n, int64_t n_words) {
+    int rc;
+    if ((rc = bind(c))) return rc;
+    Slot* sl = get_slot(c, slot);
+    if (!sl) return TPS_E_ARG;
+    return do_upload_nib4(c, *sl, nib, nib_bytes, src, desc, n, n_words);
 }
 
 int tps_batch_share(tps_ctx* c, int32_t slot, tps_ctx* src, int32_t src_slot) {

@@ -980,9 +980,220 @@ struct Fast {
     }
 };
 
+// ---------------------------------------------------------------- BAM (SAMv1 section 4.2)
+// A BGZF file whose text begins with "BAM\1": the header (l_text, text, n_ref reference entries) is skipped, then records are walked
+// by block_size across windows of inflated text (the BGZF source's thread team inflates the blocks; a record that straddles a window
+// end is carried into the next window, like a partial FASTQ record).  The host does no per-base work on the way to the GPU: a record's
+// 4-bit base codes are copied as stored (nib4 batches) and expanded on the device (tps_batch_upload_nib4); ASCII batches and the
+// FASTQ writer decode them here.  Which records are kept, and in which orientation, is what `samtools fastq` gives by default.
+constexpr uint16_t BAM_FREVERSE = 0x10, BAM_FSKIP = 0x100 | 0x800;          // reverse strand; secondary, supplementary
+const char BAM_NT16[] = "=ACMGRSVTWYHKDBN";
+inline uint8_t nib_at(const uint8_t* s, int64_t k) { return (k & 1) ? (uint8_t)(s[k >> 1] & 15) : (uint8_t)(s[k >> 1] >> 4); }
+// on the 4-bit codes the IUPAC complement is the bit reversal of the code (A = 1 <-> T = 8, C = 2 <-> G = 4, M = 3 <-> K = 12, ...)
+inline uint8_t nib_comp(uint8_t c) { return (uint8_t)(((c & 1) << 3) | ((c & 2) << 1) | ((c & 4) >> 1) | ((c & 8) >> 3)); }
+// bases of a record as ASCII (reverse-strand records reverse-complemented) and qualities + 33 (reversed; '!' when not stored)
+inline void bam_decode(const uint8_t* seq, const uint8_t* qual, int64_t L, bool rev, uint8_t* out_seq, uint8_t* out_qual) {
+    if (out_seq)
+        for (int64_t j = 0; j < L; ++j) out_seq[j] = (uint8_t)(rev ? BAM_NT16[nib_comp(nib_at(seq, L - 1 - j))] : BAM_NT16[nib_at(seq, j)]);
+    if (out_qual) {
+        if (L && qual[0] == 0xFF) { memset(out_qual, '!', (size_t)L); return; }
+        for (int64_t j = 0; j < L; ++j) out_qual[j] = (uint8_t)(qual[rev ? L - 1 - j : j] + 33);
+    }
+}
+// per byte of codes: does it hold a code that is not one of A, C, G, T (one-hot)?  (low nibble only: the last byte of an odd read)
+struct NibBad {
+    uint8_t both[256], high[256];
+    NibBad() {
+        auto bad = [](int c) { return c != 1 && c != 2 && c != 4 && c != 8; };
+        for (int b = 0; b < 256; ++b) { high[b] = bad(b >> 4); both[b] = (uint8_t)(high[b] | bad(b & 15)); }
+    }
+};
+inline const NibBad& nib_bad() { static const NibBad t; return t; }
+
+struct Bam {
+    Bgzf* z = nullptr;
+    TextHold* hold = nullptr;                  // the window of inflated text (batches handed out keep a reference on theirs)
+    const char* data = nullptr;
+    size_t size = 0, pos = 0;                  // pos: the first unconsumed record
+    bool header_done = false;
+    ~Bam() {
+        delete z;
+        if (hold) hold->unref();
+    }
+    size_t group() const { const long long g = g_opt.bgzf_group.load(); return g ? (size_t)g : (size_t)128 << 20; }
+    // at least `need` bytes from pos on in the window: a NEW window (batches already handed out keep pointing into the old one) that
+    // begins with the unconsumed tail, followed by further groups of blocks.  false: the input ends first, or a block is corrupt (g_err)
+    bool ensure(size_t need) {
+        if (size - pos >= need) return true;
+        if (z->eof() || z->failed) return false;
+        TextHold* nh = TextHold::get();
+        const size_t keep = size - pos;
+        nh->buf.resize(keep);
+        if (keep) memcpy(nh->buf.data(), data + pos, keep);
+        if (hold) hold->unref();
+        hold = nh;
+        pos = 0;
+        while (!z->eof() && hold->buf.size() < need)
+            if (!z->read_group(hold->buf, std::max(group(), need - hold->buf.size()))) break;
+        data = hold->buf.data();
+        size = hold->buf.size();
+        return !z->failed && size >= need;
+    }
+    int32_t i32(size_t at) const { int32_t v; memcpy(&v, data + at, 4); return v; }
+    int bad(const char* what) {
+        if (!z->failed) g_err = std::string("BAM: ") + what;
+        return -1;
+    }
+    // magic, l_text + text, n_ref + the reference entries
+    int header() {
+        if (header_done) return 0;
+        if (!ensure(8)) return bad("header truncated");
+        if (memcmp(data + pos, "BAM\1", 4) != 0) return bad("bad magic (not a BAM file)");
+        const int64_t l_text = i32(pos + 4);
+        if (l_text < 0) return bad("negative l_text");
+        size_t off = 8 + (size_t)l_text;
+        if (!ensure(off + 4)) return bad("header truncated");
+        const int64_t n_ref = i32(pos + off);
+        if (n_ref < 0) return bad("negative n_ref");
+        off += 4;
+        for (int64_t i = 0; i < n_ref; ++i) {
+            if (!ensure(off + 4)) return bad("header truncated");
+            const int64_t l_name = i32(pos + off);
+            if (l_name < 0) return bad("negative l_name in a reference entry");
+            off += 4 + (size_t)l_name + 4;
+            if (!ensure(off)) return bad("header truncated");
+        }
+        pos += off;
+        header_done = true;
+        return 0;
+    }
+    struct Rec { size_t name, seq, qual, next; int64_t len; uint32_t l_name; uint16_t flag; };
+    // the record at window offset p: 1 = whole in the window, 0 = the window ends inside it, -1 = malformed
+    int rec_at(size_t p, Rec& r) const {
+        if (size - p < 4) return 0;
+        const int64_t bs = i32(p);
+        if (bs < 32) { g_err = "BAM: record with block_size " + std::to_string(bs) + " (< 32)"; return -1; }
+        if (size - p - 4 < (size_t)bs) return 0;
+        const uint8_t* q = (const uint8_t*)data + p;
+        uint16_t n_cigar, flag;
+        int32_t l_seq;
+        memcpy(&n_cigar, q + 16, 2);
+        memcpy(&flag, q + 18, 2);
+        memcpy(&l_seq, q + 20, 4);
+        r.l_name = q[12];
+        if (r.l_name < 1 || l_seq < 0 || 32 + (int64_t)r.l_name + 4 * (int64_t)n_cigar + ((int64_t)l_seq + 1) / 2 + l_seq > bs) {
+            g_err = "BAM: a record's fields run past its block_size";
+            return -1;
+        }
+        r.flag = flag;
+        r.len = l_seq;
+        r.name = p + 36;
+        r.seq = r.name + r.l_name + 4 * (size_t)n_cigar;
+        r.qual = r.seq + (size_t)(l_seq + 1) / 2;
+        r.next = p + 4 + (size_t)bs;
+        return 1;
+    }
+    // the next record to hand out (secondary / supplementary ones are passed over): 1 = r, 0 = end of the input, 2 = the window ends
+    // inside it and this batch may not move to a new window (`may_refill` false: records of the batch point into this one), -1 = error
+    int next_rec(Rec& r, bool may_refill) {
+        for (;;) {
+            const int k = rec_at(pos, r);
+            if (k < 0) return -1;
+            if (k == 0) {
+                if (pos == size && z->eof()) return 0;
+                if (!may_refill) return 2;
+                const size_t need = size - pos >= 4 ? 4 + (size_t)(uint32_t)i32(pos) : 4;
+                if (!ensure(need)) return bad("file ends inside a record (truncated)");
+                continue;
+            }
+            if (r.flag & BAM_FSKIP) { pos = r.next; continue; }
+            return 1;
+        }
+    }
+    // a batch's worth of text in the window before a batch starts (the window is only ever replaced between batches)
+    int top_up(size_t target) {
+        if (size - pos < target && !z->eof()) {
+            ensure(target);
+            if (z->failed) return -1;
+        }
+        return 0;
+    }
+    int64_t next_ascii(uint8_t* bases, int64_t bases_cap, int64_t* offsets, int64_t max_records, char* heads, int64_t heads_cap,
+                       int64_t* head_off, uint8_t* quals) {
+        if (header() < 0 || top_up((size_t)std::max<int64_t>(bases_cap, 1 << 20) * 2) < 0) return -1;
+        int64_t n = 0, nb = 0, nh = 0;
+        while (n < max_records) {
+            Rec r;
+            const int k = next_rec(r, n == 0);
+            if (k < 0) return -1;
+            if (k != 1) break;
+            const int64_t hl = r.l_name - 1;
+            if (nb + r.len > bases_cap || nh + hl > heads_cap) {
+                if (n == 0) { g_err = "record larger than the batch buffers"; return -2; }
+                break;
+            }
+            bam_decode((const uint8_t*)data + r.seq, (const uint8_t*)data + r.qual, r.len, r.flag & BAM_FREVERSE, bases + nb, quals ? quals + nb : nullptr);
+            memcpy(heads + nh, data + r.name, (size_t)hl);
+            nb += r.len;
+            nh += hl;
+            ++n;
+            offsets[n] = nb;
+            head_off[n] = nh;
+            pos = r.next;
+        }
+        return n;
+    }
+    int64_t next_nib4(uint8_t* nib, tps_nib_src* src, int64_t words_cap, tps_read_desc* desc, int64_t max_records, char* heads,
+                      int64_t heads_cap, int64_t* head_off, int64_t* spans, int64_t* n_words, int64_t* nib_bytes) {
+        if (header() < 0 || top_up((size_t)std::max<int64_t>(words_cap, 1024) * 24) < 0) return -1;
+        const NibBad& nb_t = nib_bad();
+        int64_t n = 0, nw = 0, nh = 0, nbytes = 0;
+        while (n < max_records) {
+            Rec r;
+            const int k = next_rec(r, n == 0);
+            if (k < 0) return -1;
+            if (k != 1) break;
+            const int64_t hl = r.l_name - 1, L = r.len, w = tps::packed_words(L), sb = (L + 1) / 2, pad = (sb + 15) & ~(int64_t)15;
+            if (L > 0x7FFFFFFFll) { g_err = "BAM: read longer than 2^31 - 1 bases"; return -1; }
+            if (nw + w > words_cap || nh + hl > heads_cap) {          // (nib holds 8 bytes per word: pad <= 8 w)
+                if (n == 0) { g_err = "record larger than the batch buffers"; return -2; }
+                break;
+            }
+            const uint8_t* s = (const uint8_t*)data + r.seq;
+            memcpy(nib + nbytes, s, (size_t)sb);
+            memset(nib + nbytes + sb, 0, (size_t)(pad - sb));
+            // TPS_RD_HAS_INVALID: any code that is not A, C, G or T (the bytes are in cache from the copy)
+            uint8_t any = 0;
+            for (int64_t j = 0; j < L / 2; ++j) any |= nb_t.both[s[j]];
+            if (L & 1) any |= nb_t.high[s[L / 2]];
+            src[n].off = nbytes;
+            src[n].flags = (r.flag & BAM_FREVERSE) ? TPS_NIB_REVERSE : 0u;
+            src[n].reserved = 0;
+            desc[n].word_off = nw;
+            desc[n].len = (int32_t)L;
+            desc[n].flags = any ? TPS_RD_HAS_INVALID : 0u;
+            memcpy(heads + nh, data + r.name, (size_t)hl);
+            if (spans) {
+                spans[4 * n] = (int64_t)r.name; spans[4 * n + 1] = hl;
+                spans[4 * n + 2] = (int64_t)r.seq; spans[4 * n + 3] = (int64_t)r.qual;
+            }
+            nw += w;
+            nh += hl;
+            nbytes += pad;
+            ++n;
+            head_off[n] = nh;
+            pos = r.next;
+        }
+        *n_words = nw;
+        *nib_bytes = nbytes;
+        return n;
+    }
+};
+
 struct Handle {
     Reader* slow = nullptr;
     Fast* fast = nullptr;
+    Bam* bam = nullptr;                        // BAM input (format 3)
     std::string path;
     int format = 0;
     // byte ranges (tps_reader_open_range): the reader owns the records that start in [first, limit); first = the first record start
@@ -991,6 +1202,7 @@ struct Handle {
     ~Handle() {
         if (slow) { if (slow->gz) gzclose(slow->gz); delete slow; }
         delete fast;
+        delete bam;
     }
 };
 
@@ -1053,6 +1265,34 @@ int tps_reader_open(const char* path, void** out) {
     if (!r->fill() && r->len == 0) {
         if (!g_err.empty()) { delete h; return -1; }                             // unreadable (corrupt gzip), not empty
         h->format = 0; *out = h; return 0;                                       // empty file: no records
+    }
+    // BAM: BGZF-compressed binary records (SAMv1 section 4.2), recognised by the magic of its inflated text
+    if (!plain && r->len >= 4 && memcmp(r->buf.data(), "BAM\1", 4) == 0) {
+        Bgzf* z = new Bgzf();
+        z->fd = open(path, O_RDONLY);
+        struct stat st;
+        size_t bs = 0, hd = 0;
+        if (z->fd >= 0 && fstat(z->fd, &st) == 0 && st.st_size >= 28) {
+            void* m = mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, z->fd, 0);
+            if (m != MAP_FAILED) {
+                z->data = (const uint8_t*)m;
+                z->size = (size_t)st.st_size;
+                madvise(m, z->size, MADV_SEQUENTIAL);
+            }
+        }
+        if (!z->data || !Bgzf::block_at(z->data, z->size, bs, hd)) {
+            g_err = std::string(path) + ": a BAM file must be BGZF-compressed";
+            delete z;
+            delete h;
+            return -1;
+        }
+        z->threads = io_threads();
+        h->bam = new Bam();
+        h->bam->z = z;
+        h->format = 3;
+        if (h->slow) { if (h->slow->gz) gzclose(h->slow->gz); delete h->slow; h->slow = nullptr; }
+        *out = h;
+        return 0;
     }
     // the format comes from the first character of the FIRST line, like check_file_type (allsteps.py:36-50): a file that
     // starts with a blank line is "format cannot be identified" there, so it is here
@@ -1165,6 +1405,7 @@ int tps_reader_open_range(const char* path, int64_t lo, int64_t hi, int32_t thre
     if (tps_reader_open(path, out) != 0) return -1;
     Handle* h = (Handle*)*out;
     if (!h->format) return 0;                                                // an empty file
+    if (h->bam) { g_err = "byte ranges of a BAM file: it has no record index; read it with one reader"; delete h; *out = nullptr; return -1; }
     if (h->fast && h->fast->src && h->fast->src->as_bgzf()) {
         // BGZF: the range is one of COMPRESSED bytes; the reader owns the blocks that start in it
         Fast* f = h->fast;
@@ -1236,6 +1477,7 @@ int64_t tps_reader_next(void* hv, uint8_t* bases, int64_t bases_cap, int64_t* of
     offsets[0] = 0;
     head_off[0] = 0;
     if (!h->format) return 0;
+    if (h->bam) return h->bam->next_ascii(bases, bases_cap, offsets, max_records, heads, heads_cap, head_off, quals);
     if (h->fast && h->fast->bgzf_range) {
         g_err = "records the thread-team decoder does not take inside a BGZF byte range: read this file with one reader";
         return -1;
@@ -1304,6 +1546,7 @@ static int64_t reader_next_packed(void* hv, uint32_t* seq2, uint16_t* inv, int64
     *n_words = 0;
     head_off[0] = 0;
     if (!h->format) return 0;
+    if (h->bam) { g_err = "BAM input has no packed batches: read it with tps_reader_next_nib4 (or tps_reader_next)"; return -1; }
     if (!h->fast) return -4;
     Fast* f = h->fast;
     f->want_lines = false;
@@ -1410,6 +1653,19 @@ int64_t tps_pack_spans(const char* text, int64_t text_len, int32_t fasta, const 
     return nw;
 }
 
+// BAM: a batch of records as stored (Bam::next_nib4), for tps_batch_upload_nib4.
+int64_t tps_reader_next_nib4(void* hv, uint8_t* nib, tps_nib_src* src, int64_t words_cap, tps_read_desc* desc, int64_t max_records,
+                             char* heads, int64_t heads_cap, int64_t* head_off, int64_t* spans, int64_t* n_words, int64_t* nib_bytes) {
+    Handle* h = (Handle*)hv;
+    if (!h || !nib || !src || !desc || !heads || !head_off || !n_words || !nib_bytes) { g_err = "null argument"; return -1; }
+    *n_words = 0;
+    *nib_bytes = 0;
+    head_off[0] = 0;
+    if (!h->format) return 0;
+    if (!h->bam) { g_err = "not a BAM reader: nib4 batches come from BAM input only"; return -1; }
+    return h->bam->next_nib4(nib, src, words_cap, desc, max_records, heads, heads_cap, head_off, spans, n_words, nib_bytes);
+}
+
 // The text the spans of the LAST packed batch point into, for a compressed input (for a plain file the caller maps the file
 // itself and *hold stays NULL): *text / *len = the window, *hold = a reference the caller gives back with tps_text_release when
 // it is done with the batch's records.
@@ -1417,6 +1673,14 @@ int tps_reader_text_hold(void* hv, const char** text, int64_t* len, void** hold)
     Handle* h = (Handle*)hv;
     if (!h || !text || !len || !hold) { g_err = "null argument"; return -1; }
     *text = nullptr; *len = 0; *hold = nullptr;
+    if (h->bam) {
+        if (!h->bam->hold) return 0;
+        h->bam->hold->ref();
+        *text = h->bam->data;
+        *len = (int64_t)h->bam->size;
+        *hold = h->bam->hold;
+        return 0;
+    }
     if (!h->fast || !h->fast->src || !h->fast->hold) return 0;
     h->fast->hold->ref();
     *text = h->fast->data;
@@ -1447,6 +1711,45 @@ int64_t tps_pack_reads(const uint8_t* bases, const int64_t* offsets, int64_t n, 
         int64_t b = t + 1 == nt ? n : std::lower_bound(desc, desc + n, wb, [](const tps_read_desc& d, int64_t v) { return d.word_off < v; }) - desc;
         tps::pack_range(bases, offsets, a, b, desc, seq2, inv);
     });
+    return nw;
+}
+
+// A nib4 batch into the packed format: the host reference of tps_pack_kernel_nib4 (libtopsicle_hip.so) and what the test emulation
+// runs.  Output base j of a read is code j of its stored codes, or -- reverse strand -- the complement of code len - 1 - j; the 2-bit
+// code of a code is that of its IUPAC letter's ASCII, (c >> 1) & 3, as the ASCII packers give it, and every code that is not A, C, G
+// or T is flagged in inv: the batch is bit-identical to the packed ASCII text of the same records.
+int64_t tps_pack_nib4(const uint8_t* nib, int64_t nib_bytes, const tps_nib_src* src, const tps_read_desc* desc_in, int64_t n, uint32_t* seq2,
+                      uint16_t* inv, tps_read_desc* desc, int64_t words_cap) {
+    if (n < 0 || (n > 0 && (!nib || !src || !desc_in || !desc)) || !seq2 || !inv) { g_err = "null argument"; return -1; }
+    const tps::PackLut& t = tps::pack_lut();
+    int64_t nw = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t L = desc_in[i].len;
+        if (L < 0 || src[i].off < 0 || src[i].off + (L + 1) / 2 > nib_bytes) { g_err = "read " + std::to_string(i) + " outside the nibble buffer"; return -1; }
+        nw += tps::packed_words(L);
+    }
+    if (nw > words_cap) { g_err = "the batch does not fit words_cap"; return -1; }
+    nw = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t L = desc_in[i].len, w0 = nw;
+        const uint8_t* s = nib + src[i].off;
+        const bool rev = src[i].flags & TPS_NIB_REVERSE;
+        desc[i].word_off = w0;
+        desc[i].len = (int32_t)L;
+        desc[i].flags = 0;
+        nw += tps::packed_words(L);
+        memset(seq2 + w0, 0, (size_t)(nw - w0) * 4);
+        memset(inv + w0, 0, (size_t)(nw - w0) * 2);
+        for (int64_t j = 0; j < L; ++j) {
+            const uint8_t c = rev ? nib_comp(nib_at(s, L - 1 - j)) : nib_at(s, j);
+            const uint8_t a = (uint8_t)BAM_NT16[c];
+            seq2[w0 + (j >> 4)] |= (uint32_t)t.code[a] << (2 * (j & 15));
+            if (t.bad[a]) {
+                inv[w0 + (j >> 4)] |= (uint16_t)(1u << (j & 15));
+                desc[i].flags = TPS_RD_HAS_INVALID;
+            }
+        }
+    }
     return nw;
 }
 
@@ -1515,6 +1818,52 @@ int64_t tps_fastq_spans_bytes(const int64_t* spans, const int32_t* lens, const i
     for (int64_t j = 0; j < n; ++j) total += spans[4 * idx[j] + 1] + 2 * (int64_t)lens[idx[j]] + 6;     // "@" head "\n" seq "\n+\n" qual "\n"
     return total;
 }
+// Passing BAM records as FASTQ at byte file_off of fd (spans of tps_reader_next_nib4: name, name length, seq, qual offsets into the
+// window of inflated text); the record's flag word lies 18 bytes in front of its name.  The bases are decoded here (the few records
+// that pass), into a buffer that is written with pwrite.
+int64_t tps_write_bam_fastq_spans_at(int fd, int64_t file_off, const char* text, int64_t text_len, const int64_t* spans, const int32_t* lens,
+                                     const int64_t* idx, int64_t n) {
+    if (fd < 0 || !text || !spans || !lens || (n > 0 && !idx)) { g_err = "null argument"; return -1; }
+    if (file_off < 0) { g_err = "negative file offset"; return -1; }
+    std::vector<uint8_t> buf;
+    int64_t total = 0;
+    auto flush = [&]() -> bool {
+        size_t done = 0;
+        while (done < buf.size()) {
+            const ssize_t w = pwrite(fd, buf.data() + done, buf.size() - done, (off_t)(file_off + total));
+            if (w < 0) { if (errno == EINTR) continue; g_err = std::string("pwrite: ") + strerror(errno); return false; }
+            done += (size_t)w;
+            total += w;
+        }
+        buf.clear();
+        return true;
+    };
+    for (int64_t j = 0; j < n; ++j) {
+        const int64_t i = idx[j];
+        const int64_t h0 = spans[4 * i], hl = spans[4 * i + 1], s0 = spans[4 * i + 2], q0 = spans[4 * i + 3], L = lens[i];
+        if (h0 < 18 || hl < 0 || s0 < 0 || q0 < 0 || L < 0 || h0 + hl > text_len || s0 + (L + 1) / 2 > text_len || q0 + L > text_len) {
+            g_err = "record span outside the text";
+            return -1;
+        }
+        uint16_t flag;
+        memcpy(&flag, text + h0 - 18, 2);
+        const size_t at = buf.size();
+        buf.resize(at + (size_t)(hl + 2 * L + 6));
+        uint8_t* o = buf.data() + at;
+        *o++ = '@';
+        memcpy(o, text + h0, (size_t)hl);
+        o += hl;
+        *o++ = '\n';
+        bam_decode((const uint8_t*)text + s0, (const uint8_t*)text + q0, L, flag & BAM_FREVERSE, o, o + L + 3);
+        o += L;
+        memcpy(o, "\n+\n", 3);
+        o[3 + L] = '\n';
+        if (buf.size() > ((size_t)4 << 20) && !flush()) return -1;
+    }
+    if (!flush()) return -1;
+    return total;
+}
+
 static int64_t write_fastq_spans(int fd, int64_t file_off, const char* text, int64_t text_len, const int64_t* spans, const int32_t* lens, const int64_t* idx, int64_t n) {
     if (fd < 0 || !text || !spans || !lens || (n > 0 && !idx)) { g_err = "null argument"; return -1; }
     static const char at = '@', nl = '\n', plus[3] = {'\n', '+', '\n'};

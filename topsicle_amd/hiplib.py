@@ -20,7 +20,7 @@ MAX_K, MAX_PATTERNS, MAX_SLOTS = 15, 31, 16
 
 EXPORTS = [
     "tps_abi_version", "tps_device_count", "tps_ctx_create", "tps_ctx_destroy", "tps_last_error",
-    "tps_set_patterns", "tps_batch_upload", "tps_batch_upload_packed", "tps_batch_share", "tps_host_alloc", "tps_host_free",
+    "tps_set_patterns", "tps_batch_upload", "tps_batch_upload_packed", "tps_batch_upload_nib4", "tps_batch_share", "tps_host_alloc", "tps_host_free",
     "tps_batch_download_packed", "tps_batch_kmer_followers", "tps_batch_set_tails", "tps_batch_scan", "tps_sync",
     "tps_batch_results", "tps_batch_window_offsets", "tps_batch_window_sums", "tps_batch_window_raw",
     "tps_batch_raw_to_fd", "tps_batch_trc_counts", "tps_trc_counts", "tps_window_counts", "tps_binseg_l2", "tps_binseg_l2_ties", "tps_batch_read_sums", "tps_window_count",
@@ -43,6 +43,10 @@ class Params(C.Structure):
 DESC_DTYPE = np.dtype([("word_off", "<i8"), ("len", "<i4"), ("flags", "<u4")], align=True)      # struct tps_read_desc
 assert DESC_DTYPE.itemsize == 16
 RD_HAS_INVALID = 1
+
+NIB_SRC_DTYPE = np.dtype([("off", "<i8"), ("flags", "<u4"), ("reserved", "<u4")], align=True)    # struct tps_nib_src
+assert NIB_SRC_DTYPE.itemsize == 16
+NIB_REVERSE = 1        # TPS_NIB_REVERSE: a reverse-strand BAM record (the read is the reverse complement of its stored codes)
 
 RESULT_DTYPE = np.dtype([("best_start", "<i4"), ("best_start_idx", "<i4"), ("best_end", "<i4"),
                          ("best_end_idx", "<i4"), ("tail", "<i4"), ("pass", "<i4"), ("n_win", "<i4"),
@@ -82,6 +86,7 @@ def load_library(path: str | None = None) -> C.CDLL:
         "tps_set_patterns": (C.c_int, [vp, C.c_char_p, i32, i32]),
         "tps_batch_upload": (C.c_int, [vp, i32, vp, vp, i64]),
         "tps_batch_upload_packed": (C.c_int, [vp, i32, vp, vp, vp, i64, i64]),
+        "tps_batch_upload_nib4": (C.c_int, [vp, i32, vp, i64, vp, vp, i64, i64]),
         "tps_batch_share": (C.c_int, [vp, i32, vp, i32]),
         "tps_host_alloc": (C.c_int, [vp, i64, C.POINTER(vp)]),
         "tps_host_free": (C.c_int, [vp, vp]),
@@ -319,6 +324,15 @@ class HipScanner:
         n, nw = len(desc), len(seq2)
         assert inv is None or len(inv) == nw
         self._check(self.lib.tps_batch_upload_packed(self._h, slot, _ptr(seq2), _ptr(inv), _ptr(desc), n, nw))
+        self._n[slot] = n
+
+    def upload_nib4(self, slot: int, nib: np.ndarray, src: np.ndarray, desc: np.ndarray, n_words: int):
+        """A batch of BAM records as stored (seqio.read_batches_packed on BAM input): their 4-bit base codes `nib`, where each read's
+        codes are and its strand (`src`, NIB_SRC_DTYPE), the reads' descriptors in the packed layout; a device kernel expands them
+        into the slot's packed batch (tps_batch_upload_nib4).  Buffers from `host_alloc` are copied asynchronously, like upload_packed."""
+        assert nib.dtype == np.uint8 and src.dtype == NIB_SRC_DTYPE and desc.dtype == DESC_DTYPE and len(src) == len(desc)
+        n = len(desc)
+        self._check(self.lib.tps_batch_upload_nib4(self._h, slot, _ptr(nib), len(nib), _ptr(src), _ptr(desc), n, int(n_words)))
         self._n[slot] = n
 
     def share(self, slot: int, src: "HipScanner", src_slot: int):

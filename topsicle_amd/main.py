@@ -103,7 +103,10 @@ def tprint(*args, **kwargs):
 
 
 def _formats(seq_loc: str):
-    """(input format, filtered-file extension) by file name, as main.py:68-81 decides it."""
+    """(input format, filtered-file extension) by file name, as main.py:68-81 decides it; BAM input (recognised by its content)
+    leaves its passing records as FASTQ."""
+    if seqio.is_bam(seq_loc):
+        return "fastq"
     if seq_loc.endswith(".gz"):
         fq = seq_loc.endswith(".fastq.gz") or seq_loc.endswith(".fq.gz")
     else:
@@ -214,6 +217,11 @@ def process_file_multi(args, seq_loc, phrases, engines):
     # records only -- plots and raw rows keep one reader).  --shards N forces it (tests); the default cuts files of at least 256 MiB per GPU
     n_shards = int(getattr(args, "shards", 0) or 0)
     shard_min = 4096
+    if seqio.is_bam(seq_loc):
+        if n_shards > 1:
+            tprint(f"{base_name}: BAM input is read by one reader (--shards {n_shards} ignored: BAM has no record index)")
+        if getattr(args, "twopass", None) == "on":
+            tprint(f"{base_name}: BAM input is scanned as whole reads (--twopass on ignored)")
     if n_shards <= 0:
         n_shards, shard_min = max(1, len({getattr(e, "device", 0) for e in engines})), 256 << 20
     ok = False

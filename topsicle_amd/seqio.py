@@ -30,7 +30,9 @@ def _open_text(path: str):
 
 
 def check_file_type(filepath: str):
-    """'fastq' / 'fasta' from the first character of the file, 0 if unknown (allsteps.py:36-50)."""
+    """'fastq' / 'fasta' from the first character of the file, 0 if unknown (allsteps.py:36-50); 'bam' for a BAM file."""
+    if is_bam(filepath):
+        return "bam"
     try:
         with _open_text(filepath) as h:
             first = h.readline().strip()
@@ -96,11 +98,37 @@ def parse(handle, fmt: str):
         raise ValueError(f"unknown format {fmt!r}")
 
 
+def is_bam(filepath) -> bool:
+    """True for a BGZF file whose inflated text starts with BAM's magic "BAM\\1" (SAMv1 section 4.2): by content, like the other
+    formats.  False for anything else, unreadable files included."""
+    import zlib
+    try:
+        with open(filepath, "rb") as fh:
+            head = fh.read(1 << 16)
+    except (OSError, TypeError):
+        return False
+    if len(head) < 18 or head[:2] != b"\x1f\x8b" or head[2] != 8 or not (head[3] & 4) or head[12:14] != b"BC":
+        return False
+    try:
+        text = zlib.decompressobj(31).decompress(head, 4)
+    except zlib.error:
+        return False
+    return text[:4] == b"BAM\x01"
+
+
 def read_records(filepath: str):
-    """Generator over the records of a FASTA/FASTQ(.gz) file (unzip_file, allsteps.py:127-149).
+    """Generator over the records of a FASTA/FASTQ(.gz) or BAM file (unzip_file, allsteps.py:127-149).
     Parse errors are logged and end the iteration, as upstream."""
     if not isinstance(filepath, str):
         logging.error("Input must be a string representing the file path.")
+        return
+    if is_bam(filepath):
+        # BAM: the native reader decodes the records (ids = read names, reverse-strand records in the sequencer's orientation)
+        if _load_io() is None:
+            raise RuntimeError("libtopsicle_io.so is not built: BAM input needs the native reader")
+        for b in read_batches(filepath):
+            for i in range(b.n):
+                yield b.record(i)
         return
     fmt = check_file_type(filepath)
     if not fmt:
@@ -188,15 +216,19 @@ IO_EXPORTS = {
                                            "c_void_p", "POINTER(c_int64)"]),
     "tps_reader_next_heads": ("c_int64", ["c_void_p", "c_int32", "c_void_p", "c_void_p", "c_int64", "c_void_p", "c_int64", "c_void_p", "c_int64",
                                           "c_void_p", "c_void_p", "c_void_p", "POINTER(c_int64)"]),
+    "tps_reader_next_nib4": ("c_int64", ["c_void_p", "c_void_p", "c_void_p", "c_int64", "c_void_p", "c_int64", "c_void_p", "c_int64", "c_void_p",
+                                         "c_void_p", "POINTER(c_int64)", "POINTER(c_int64)"]),
     "tps_reader_text_hold": ("c_int", ["c_void_p", "POINTER(c_void_p)", "POINTER(c_int64)", "POINTER(c_void_p)"]),
     "tps_text_release": (None, ["c_void_p"]),
     "tps_pack_spans": ("c_int64", ["c_void_p", "c_int64", "c_int32", "c_void_p", "c_void_p", "c_void_p", "c_void_p", "c_int64", "c_int32", "c_void_p",
                                    "c_void_p", "c_void_p", "c_int64"]),
+    "tps_pack_nib4": ("c_int64", ["c_void_p", "c_int64", "c_void_p", "c_void_p", "c_int64", "c_void_p", "c_void_p", "c_void_p", "c_int64"]),
     "tps_packed_words_total": ("c_int64", ["c_void_p", "c_int64"]),
     "tps_pack_reads": ("c_int64", ["c_void_p", "c_void_p", "c_int64", "c_void_p", "c_void_p", "c_void_p", "c_int32"]),
     "tps_write_fastq_spans": ("c_int64", ["c_int", "c_void_p", "c_int64", "c_void_p", "c_void_p", "c_void_p", "c_int64"]),
     "tps_write_fastq_spans_at": ("c_int64", ["c_int", "c_int64", "c_void_p", "c_int64", "c_void_p", "c_void_p", "c_void_p", "c_int64"]),
     "tps_fastq_spans_bytes": ("c_int64", ["c_void_p", "c_void_p", "c_void_p", "c_int64"]),
+    "tps_write_bam_fastq_spans_at": ("c_int64", ["c_int", "c_int64", "c_void_p", "c_int64", "c_void_p", "c_void_p", "c_void_p", "c_int64"]),
     "tps_crc32": ("c_uint32", ["c_uint32", "c_void_p", "c_int64"]),
     "tps_crc32_combine": ("c_uint32", ["c_uint32", "c_uint32", "c_int64"]),
     "tps_io_set_option": ("c_int", ["c_char_p", "c_int64"]),
@@ -268,11 +300,11 @@ def read_batches(filepath: str, max_bases: int = 256 << 20, max_records: int = 1
         logging.error("Error parsing file: %s", lib.tps_io_last_error().decode())
         return
     try:
-        fmt = {1: "fasta", 2: "fastq"}.get(lib.tps_reader_format(h), "fasta")
+        fmt = {1: "fasta", 2: "fastq", 3: "bam"}.get(lib.tps_reader_format(h), "fasta")
         cap = max_bases
         while True:
             bases = np.empty(cap, np.uint8)
-            quals = np.empty(cap, np.uint8) if (want_quals and fmt == "fastq") else None
+            quals = np.empty(cap, np.uint8) if (want_quals and fmt in ("fastq", "bam")) else None
             nrec = min(max_records, cap // 64 + 1024)
             offsets = np.empty(nrec + 1, np.int64)
             head_off = np.empty(nrec + 1, np.int64)
@@ -283,6 +315,8 @@ def read_batches(filepath: str, max_bases: int = 256 << 20, max_records: int = 1
                 cap *= 2
                 continue
             if n < 0:
+                if fmt == "bam":                # (a damaged BAM file is an error, never a short read set)
+                    raise RuntimeError("%s: %s" % (filepath, lib.tps_io_last_error().decode()))
                 logging.error("Error parsing file: %s", lib.tps_io_last_error().decode())
                 return
             if n == 0:
@@ -320,6 +354,56 @@ def pack_reads_host(bases, offsets, out=None, threads: int = 0):
     return seq2[:nw], inv[:nw], desc[:n]
 
 
+def pack_nib4_host(nib, src, desc, n_words: int):
+    """A nib4 batch (BAM records as stored: read_batches_packed on BAM input) into the packed upload format on the host
+    (tps_pack_nib4, the reference of the device kernel behind HipScanner.upload_nib4): (seq2, inv, desc)."""
+    import numpy as np
+    from . import hiplib
+    lib = _load_io()
+    if lib is None:
+        raise RuntimeError("libtopsicle_io.so is not built")
+    nib = np.ascontiguousarray(nib, np.uint8)
+    src = np.ascontiguousarray(src, hiplib.NIB_SRC_DTYPE)
+    desc_in = np.ascontiguousarray(desc, hiplib.DESC_DTYPE)
+    n = len(desc_in)
+    seq2 = np.zeros(max(int(n_words), 4), np.uint32)
+    inv = np.zeros(max(int(n_words), 4), np.uint16)
+    out = np.zeros(max(n, 1), hiplib.DESC_DTYPE)
+    got = lib.tps_pack_nib4(nib.ctypes.data, len(nib), src.ctypes.data, desc_in.ctypes.data, n, seq2.ctypes.data, inv.ctypes.data,
+                            out.ctypes.data, len(seq2))
+    if got < 0:
+        raise RuntimeError(lib.tps_io_last_error().decode())
+    return seq2[:got], inv[:got], out[:n]
+
+
+_NT16 = b"=ACMGRSVTWYHKDBN"
+_NIB_COMP = bytes(((c & 1) << 3) | ((c & 2) << 1) | ((c & 4) >> 1) | ((c & 8) >> 3) for c in range(16))   # complement = bit reversal
+
+
+def _bam_flag(text, name_off: int) -> int:
+    """The flag word of the BAM record whose read_name starts at text offset name_off (it lies 18 bytes in front of the name)."""
+    b = text[name_off - 18:name_off - 16]
+    return b[0] | (b[1] << 8)
+
+
+def bam_seq_qual(text, name_off: int, seq_off: int, qual_off: int, n: int):
+    """(bases, qualities) of a BAM record as FASTQ text: reverse-strand records reverse-complemented, qualities + 33 ('!' for every
+    base when none are stored) -- what the native reader and tps_write_bam_fastq_spans_at give."""
+    import numpy as np
+    rev = bool(_bam_flag(text, name_off) & 0x10)
+    raw = np.frombuffer(text[seq_off:seq_off + (n + 1) // 2], np.uint8)
+    codes = np.empty(2 * len(raw), np.uint8)
+    codes[0::2], codes[1::2] = raw >> 4, raw & 15
+    codes = codes[:n]
+    q = np.frombuffer(text[qual_off:qual_off + n], np.uint8)
+    if rev:
+        codes = np.frombuffer(_NIB_COMP, np.uint8)[codes[::-1]]
+        q = q[::-1]
+    seq = np.frombuffer(_NT16, np.uint8)[codes].tobytes()
+    qual = b"!" * n if (n and q[-1 if rev else 0] == 0xFF) else (q.astype(np.uint16) + 33).astype(np.uint8).tobytes()
+    return seq, qual
+
+
 class BufferSet:
     """One set of upload staging buffers (seq2, inv, desc), typically pinned (HipScanner.host_alloc)."""
 
@@ -330,6 +414,8 @@ class BufferSet:
         if alloc is None:
             def alloc(nbytes):
                 return np.empty(nbytes, np.uint8)
+        self._alloc = alloc
+        self._nib = self._src = None                                # BAM input only (nib4 batches): allocated on first use
         self.seq2 = alloc(4 * self.words_cap).view(np.uint32)
         self.inv = alloc(2 * self.words_cap).view(np.uint16)
         self.desc = alloc(16 * self.reads_cap).view(hiplib.DESC_DTYPE)
@@ -339,6 +425,21 @@ class BufferSet:
         self.head_off = np.empty(self.reads_cap + 1, np.int64)
         self.spans = np.empty((self.reads_cap, 4), np.int64)
         self.full_len = np.empty(self.reads_cap, np.int32)          # (heads mode: every read's own length)
+
+    @property
+    def nib(self):
+        """BAM records' 4-bit base codes: 8 bytes per 16 bases (tps_reader_next_nib4)."""
+        if self._nib is None:
+            self._nib = self._alloc(8 * self.words_cap)
+        return self._nib
+
+    @property
+    def src(self):
+        """Where each read's codes are and its strand (tps_nib_src per read)."""
+        if self._src is None:
+            from . import hiplib
+            self._src = self._alloc(16 * self.reads_cap).view(hiplib.NIB_SRC_DTYPE)
+        return self._src
 
 
 class BufferPool:
@@ -385,8 +486,12 @@ class PackedBatch:
     """A batch of reads in the packed upload format, plus what is needed to write single records back out: either the
     records' spans in the mmap'ed input file (plain FASTQ, nothing was copied) or the ASCII RecordBatch it was packed from."""
 
-    def __init__(self, seq2, inv, desc, heads, head_off, fmt, spans=None, text=None, ascii_batch=None, bufset=None, pool=None, full_len=None):
+    def __init__(self, seq2, inv, desc, heads, head_off, fmt, spans=None, text=None, ascii_batch=None, bufset=None, pool=None, full_len=None,
+                 nib=None, src=None, n_words=0):
         self.seq2, self.inv, self.desc, self.heads, self.head_off, self.fmt = seq2, inv, desc, heads, head_off, fmt
+        # a nib4 batch (fmt "bam"): the records' 4-bit codes as stored, where each read's are, and the words the packed batch takes;
+        # uploaded with HipScanner.upload_nib4 (seq2 / inv are None); spans = name, name length, seq and qual offsets into `text`
+        self.nib, self.src, self.n_words = nib, src, int(n_words)
         self.spans, self.text, self.ascii_batch = spans, text, ascii_batch
         # heads mode (read_batches_packed(heads_bp=...)): seq2 / desc hold every read's first + last heads_bp bases only (all that
         # step 1 looks at); full_len = the reads' own lengths.  batch.scan_jobs runs step 1 on them and packs the scanned part of the
@@ -411,7 +516,7 @@ class PackedBatch:
             self.desc = np.array(self.desc)               # lengths stay available for the writers
             if self.full_len is not None:
                 self.desc["len"] = self.full_len          # (heads mode: from here on the batch describes the whole reads)
-            self.seq2 = self.inv = None
+            self.seq2 = self.inv = self.nib = self.src = None
             self._pool.put(self._bufset)
             self._bufset = None
 
@@ -430,7 +535,13 @@ class PackedBatch:
     def read_len(self, i: int) -> int:
         return int(self.desc["len"][i] if self.full_len is None else self.full_len[i])
 
+    def _bam(self, i: int):
+        sp = self.spans[i]
+        return bam_seq_qual(self.text, int(sp[0]), int(sp[2]), int(sp[3]), self.read_len(i))
+
     def seq_bytes(self, i: int) -> bytes:
+        if self.fmt == "bam":
+            return self._bam(i)[0]
         if self.spans is not None:
             s0, n = int(self.spans[i, 2]), self.read_len(i)
             if self.fmt == "fasta":
@@ -455,6 +566,8 @@ class PackedBatch:
         return raw.replace(b"\r", b"").replace(b"\n", b"")[:n]
 
     def qual_bytes(self, i: int):
+        if self.fmt == "bam":
+            return self._bam(i)[1]
         if self.fmt == "fasta":
             return None                       # (a FASTA span's fourth entry is the end of the sequence text, not a quality offset)
         if self.spans is not None:
@@ -486,7 +599,7 @@ class PackedBatch:
         through it (FASTA, ASCII batches): the caller can then give every batch its place in the file up front and let several
         threads write at once (write_records(..., offset))."""
         import numpy as np
-        if not (fmt == "fastq" and self.fmt == "fastq" and self.spans is not None and self.text is not None) or _load_io() is None:
+        if not (fmt == "fastq" and self.fmt in ("fastq", "bam") and self.spans is not None and self.text is not None) or _load_io() is None:
             return None
         idx = np.ascontiguousarray(indices, dtype=np.int64)
         lens = (self.desc["len"] if self.full_len is None else self.full_len).astype(np.int64)
@@ -498,6 +611,27 @@ class PackedBatch:
         mapping, no copy in user space (tps_write_fastq_spans).  offset (native path only: native_fastq_bytes is not None): write
         at that byte of the file whatever the handle's position (pwritev) -- several threads, one file."""
         import numpy as np
+        if fmt == "fastq" and self.fmt == "bam" and self.spans is not None and self.text is not None and len(indices):
+            # BAM records leave through tps_write_bam_fastq_spans_at (decoded there; pwrite at `offset`, or where the handle stands)
+            lib = _load_io()
+            if lib is not None:
+                try:
+                    fd = handle.fileno()
+                except (AttributeError, OSError, ValueError):
+                    fd = None
+                if fd is not None:
+                    handle.flush()
+                    at = handle.tell() if offset is None else int(offset)
+                    text = np.frombuffer(self.text.buffer() if hasattr(self.text, "buffer") else self.text, dtype=np.uint8)
+                    idx = np.ascontiguousarray(indices, dtype=np.int64)
+                    lens = np.ascontiguousarray(self.desc["len"], dtype=np.int32)
+                    spans = np.ascontiguousarray(self.spans, dtype=np.int64)
+                    got = lib.tps_write_bam_fastq_spans_at(fd, at, text.ctypes.data, len(text), spans.ctypes.data, lens.ctypes.data, idx.ctypes.data, len(idx))
+                    if got < 0:
+                        raise OSError(lib.tps_io_last_error().decode())
+                    if offset is None:
+                        handle.seek(at + got)
+                    return
         if fmt == "fastq" and self.fmt == "fastq" and self.spans is not None and self.text is not None and len(indices):
             lib = _load_io()
             try:
@@ -598,6 +732,30 @@ def pack_spans(pb: "PackedBatch", idx, tails, maxlen: int):
     return seq2[:got], inv[:got], desc
 
 
+def _bam_batches(lib, h, filepath, pool, nrec_cap):
+    """nib4 batches of an open BAM reader (tps_reader_next_nib4): PackedBatch with nib / src / desc in a BufferSet of `pool`, the
+    read names as heads and spans into the reader's window of inflated text, which the batch holds until it is gone."""
+    import ctypes as C
+    while True:
+        bs = pool.get()
+        nib, src = bs.nib, bs.src
+        nw, nb = C.c_int64(0), C.c_int64(0)
+        n = lib.tps_reader_next_nib4(h, nib.ctypes.data, src.ctypes.data, bs.words_cap, bs.desc.ctypes.data, nrec_cap, bs.heads.ctypes.data,
+                                     bs.heads_cap, bs.head_off.ctypes.data, bs.spans.ctypes.data, C.byref(nw), C.byref(nb))
+        if n <= 0:
+            pool.put(bs)
+            if n == 0:
+                return
+            if n == -2:
+                raise RuntimeError("a single read does not fit the upload buffers; raise the batch size")
+            raise RuntimeError("%s: %s" % (filepath, lib.tps_io_last_error().decode()))
+        tp, tl, th = C.c_void_p(), C.c_int64(0), C.c_void_p()
+        lib.tps_reader_text_hold(h, C.byref(tp), C.byref(tl), C.byref(th))
+        text = _HeldText(lib, tp.value, tl.value, th.value)
+        yield PackedBatch(None, None, bs.desc[:n], bs.heads[:int(bs.head_off[n])].copy(), bs.head_off[:n + 1].copy(), "bam",
+                          spans=bs.spans[:n].copy(), text=text, bufset=bs, pool=pool, nib=nib[:nb.value], src=src[:n], n_words=nw.value)
+
+
 def shard_ranges(filepath: str, n_shards: int, min_bytes: int = 64 << 20):
     """Byte ranges [(lo, hi), ...] that cut a plain FASTA / FASTQ file -- or a BGZF-compressed one, at block boundaries -- into at most
     n_shards readers of at least min_bytes each (read_batches_packed(byte_range=...): a record belongs to the range its first byte
@@ -654,7 +812,11 @@ def read_batches_packed(filepath: str, pool: BufferPool, max_records: int = 1 <<
         return
     fh = mm = None
     try:
-        fmt = {1: "fasta", 2: "fastq"}.get(lib.tps_reader_format(h), "fasta")
+        fmt = {1: "fasta", 2: "fastq", 3: "bam"}.get(lib.tps_reader_format(h), "fasta")
+        if fmt == "bam":
+            # BAM: the records' base codes go up as stored and are expanded on the device (HipScanner.upload_nib4); whole reads always
+            yield from _bam_batches(lib, h, filepath, pool, min(max_records, pool.reads_cap))
+            return
         packed_mode = True
         nrec_cap = min(max_records, pool.reads_cap)
         if first_batch_records > 0:
