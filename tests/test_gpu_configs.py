@@ -1,7 +1,7 @@
 """GPU parity at the shapes of BASELINE.json's configs that the first suite did not reach:
 
   configs[0]  demo file, --pattern AAACCCT, defaults (slide = len(pattern) = 7)
-  configs[2]  PacBio-HiFi-like reads x 20 kb, AAACCCT k=5 slide 7 (2829 windows, kernel _s7)
+  configs[2]  PacBio-HiFi-like reads x 20 kb, AAACCCT k=5 slide 7 (2829 windows, kernel _s7q)
   configs[3]  ONT-like reads x 30 kb (L > maxlengthtelo), CCCTAA k=4 slide 6 (3301 windows, HALO tiles), --cutoff sweep
   every config: change-point == the FLOAT64 restatement of what allsteps.py:310-311 runs (oracle.c, numpy order),
                 over thousands of reads, not only the exact-rational arg-max
@@ -94,7 +94,7 @@ def test_config3_hifi_20kb_slide7_vs_oracle(sc):
     sc.set_patterns(pats)
     bases, offsets, truth = synth.make_reads(64, 20000, motif, seed=20250919 + 2, errors=synth.HIFI)
     res, sums, win_off = _scan(sc, 0, bases, offsets, _params(motif, slide))
-    assert "tps_scan_kernel_s7" in sc.kernel_info(0)
+    assert sc.kernel_info(0).split(" lds=")[0] == "tps_scan_kernel_s7q"      # (k = 5 without self-overlap: the 16-bit pair table)
     assert res["pass"].all() and (res["n_win"] == 2829).all()
     assert np.array_equal(res["tail"], truth["reverse"].astype(np.int32))
     _check_reads_vs_oracle(bases, offsets, res, sums, win_off, pats, motif, slide, 0.7, range(0, 64, 4))

@@ -581,7 +581,7 @@ def test_default_kernels_other_slides(sc, slide, k, motif):
     sc.scan(6, prm)
     sc.sync()
     info = sc.kernel_info(6)
-    assert info.startswith("tps_scan_kernel_s%d" % slide) and not info.startswith("tps_scan_kernel "), info
+    assert info.split(" lds=")[0] == "tps_scan_kernel_s%d%s" % (slide, "p" if k <= 4 else ""), info      # (k <= 4: the pair table)
     res = sc.results(6).copy()
     sums, win_off = sc.window_sums(6)
     cs_all, ce_all = sc.batch_trc_counts(6)
