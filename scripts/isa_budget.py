@@ -12,7 +12,9 @@ s_nop, branches and barriers).  Static counts: a loop body counts once, a branch
 Rows: the kernel's regions between clock stamps (step 1 = stamps 1..4, the change point = 9..10), and per tile
 instantiation (S, RPT, ROTZ, PAIR) its phases; `home` marks the instantiation of the default geometry (slide 6, r = 0,
 q a multiple of 8, pair table), the one config 2 runs five times per read.  The strided candidate pass is a loop (config 2:
-two passes per tile) that a tile which stores its candidates lane by lane skips."""
+two passes per tile) that a tile which stores its candidates lane by lane skips.  `region*` rows are the parts of a read's
+program outside the tile phases (TPS_ISA_REGION): tile set-up, per tile the staging store, the prefetch and the dispatch,
+and the change point's stages; REGION_LOWER holds a written floor for each."""
 import argparse
 import csv
 import os
@@ -30,6 +32,22 @@ STAMPS = {0: "entry", 1: "step1_stage_count", 2: "step1_decide", 3: "step1_decid
 # per window pair one packed subtract + add of the counts; scan: 6 DPP steps and 8 prefix adds; candidates: two stores' sums
 # (the strided pass: none -- the lanes' own candidates need no second pass)
 LOWER = {1: 24 + 16, 2: 8 * 2 + 4 * 2, 3: 6 + 8 + 2, 4: 2, 6: 0, 5: 0}
+REGIONS = {1: "tile_setup", 2: "stage_store", 3: "prefetch", 4: "tile_dispatch", 5: "binseg_prefilter", 6: "binseg_f64_reduce",
+           7: "binseg_exact_result"}
+# written floors of the regions, VALU per wave and execution (static rows hold BOTH sides of every branch, so a row can lie
+# above its floor by the side a read does not take):
+# 1 tile set-up: the first prefetch (a lane id, a compare, four zeros) -- everything else is wave-uniform: 6
+# 2 staging store, one quad per lane: an LDS address and the compare against the buffer's quads, + the reversal of a reverse
+#   tail (4 words x bfrev, two shifts, bfi): 2 forward, 18 reverse
+# 3 prefetch: the compare against the staged quads and four zeros under the masked load; the address is per read: 5
+# 4 dispatch: the invalid flag's LDS read and its readfirstlane; the switch is scalar: 2
+# 5 prefilter, per group of four candidates: an address and a compare per load (8), per candidate D (mul, sub, cvt), the
+#   denominator (2 cvt, mul), rcp, two multiplies, the select of unused slots, compare + four selects + max for best /
+#   runner-up (17) = 76; + the wave maximum (6 DPP steps, a readlane) and the ballot's compare: 9
+# 6 one float64 candidate per lane (41, the fraction comparison as written) + one division (about 12) + three wave maxima
+#   (21) + two ballots' compares: 76
+# 7 the exact tournament never runs without a tie; the result store is one lane's: 0
+REGION_LOWER = {1: 6, 2: 2, 3: 5, 4: 2, 5: 76 + 9, 6: 76, 7: 0}
 
 
 def compile_isa(src, group, out):
@@ -58,7 +76,7 @@ def regions(isa_path, kernel):
     end = next(i for i in range(start, len(lines)) if lines[i].strip().startswith(".Lfunc_end") or lines[i].startswith(".Lfunc_end"))
     acc, cur = {}, ("stamp", 0)
     for l in lines[start + 1:end]:
-        m = re.search(r";tps_(stamp|mark) (0x[0-9a-f]+|\d+)", l)
+        m = re.search(r";tps_(stamp|mark|region) (0x[0-9a-f]+|\d+)", l)
         if m:
             cur = (m.group(1), int(m.group(2), 0))
             continue
@@ -97,6 +115,9 @@ def main():
         if what == "stamp":
             rows.append(dict(tag=o.tag, kernel=o.kernel, region=f"stamp{v}_{STAMPS.get(v, '?')}", S="", rpt="", rotz="", pair="", home="",
                              lower_bound_valu="", **d))
+        elif what == "region":
+            rows.append(dict(tag=o.tag, kernel=o.kernel, region=f"region{v}_{REGIONS.get(v, '?')}", S="", rpt="", rotz="", pair="", home="",
+                             lower_bound_valu=REGION_LOWER.get(v, ""), **d))
         else:
             p, S, rpt, rotz, pair, inv, cd = decode(v)
             home = int(S == 6 and rpt == 0 and rotz == 1 and pair == 1 and inv == 0 and cd == 0)

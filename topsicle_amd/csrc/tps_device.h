@@ -235,7 +235,14 @@ TPS_DEV uint32_t g16_load(uint64_t base, uint32_t i) {
 #ifdef TPS_EMU
 TPS_DEV void g32_store(uint64_t base, uint32_t i, uint32_t v) { ((uint32_t*)(uintptr_t)base)[i] = v; }
 TPS_DEV uint32_t g32_load(uint64_t base, uint32_t i) { return ((const uint32_t*)(uintptr_t)base)[i]; }
+TPS_DEV uint32_t g32_load_at(uint64_t base, uint32_t byte_off) { return *(const uint32_t*)(uintptr_t)(base + byte_off); }
 #else
+// ... at an unsigned 32-bit BYTE offset from a wave-uniform base: one scalar-base load, no 64-bit address arithmetic per lane
+TPS_DEV uint32_t g32_load_at(uint64_t base, uint32_t byte_off) {
+    typedef const __attribute__((address_space(1))) uint8_t* gb_t;
+    typedef const __attribute__((address_space(1))) uint32_t* gp_t;
+    return *(gp_t)((gb_t)(uintptr_t)base + byte_off);
+}
 TPS_DEV void g32_store(uint64_t base, uint32_t i, uint32_t v) {
     typedef __attribute__((address_space(1))) uint32_t* gp_t;
     ((gp_t)(uintptr_t)base)[i] = v;
@@ -268,13 +275,19 @@ constexpr int clog2(int x) { return x <= 1 ? 0 : 1 + clog2(x / 2); }
 #if defined(TPS_ISA_MARKS) && !defined(TPS_EMU)
 #define TPS_STAMP(i) asm volatile(";tps_stamp %0" ::"i"(i))
 #define TPS_ISA_MARK(id) asm volatile(";tps_mark %0" ::"i"(id))
+#define TPS_ISA_REGION(id) asm volatile(";tps_region %0" ::"i"(id))
 #elif defined(TPS_EMU) || !defined(TPS_STAMPS)
 #define TPS_STAMP(i) ((void)0)
 #define TPS_ISA_MARK(id) ((void)(id))
+#define TPS_ISA_REGION(id) ((void)(id))
 #else
 #define TPS_STAMP(i) do { if (a.stamps && (threadIdx.x & 63u) == 0) a.stamps[r * 16 + (i)] = __builtin_readcyclecounter(); } while (0)
 #define TPS_ISA_MARK(id) ((void)(id))
+#define TPS_ISA_REGION(id) ((void)(id))
 #endif
+// (TPS_ISA_REGION: the parts of a read's program OUTSIDE the tile phases, for the same static budget -- 1 tile set-up, 2 the
+// tile's staging store, 3 the next tile's prefetch, 4 the tile dispatch, 5 the change point's float32 prefilter, 6 its float64
+// stage and wave reduction, 7 the exact tournament and the result)
 // ... inside the per-pattern tiles (first tile of a read only): 6 = phase 1 done, 7 = windows done, 11 = rows out, 12 = candidates done
 #if defined(TPS_EMU) || !defined(TPS_STAMPS)
 #define TPS_PP_STAMP(i) ((void)0)
@@ -578,12 +591,34 @@ TPS_DEV uint32_t rev2(uint32_t x) {
     const uint32_t y = bitrev32(x);               // fields reversed, the two bits of each field swapped
     return ((y >> 1) & 0x55555555u) | ((y & 0x55555555u) << 1);
 }
+// a loaded quad of a reverse tail in LDS order.  The reversed words are made opaque one by one: v_bfrev, two shifts and one
+// v_bfi per word (the optimiser otherwise shares masks across the four words and ends with six instructions each), and a
+// caller that branches on the wave's orientation keeps a real scalar branch -- a forward tail runs none of this, where
+// stage_orient's select computes the reversal for every quad of every read and then drops it for half of them
+TPS_DEV u32x4 stage_reversed(const u32x4& v) {
+    u32x4 r;
+    r.x = rev2(v.w); TPS_PIN_V(r.x);
+    r.y = rev2(v.z); TPS_PIN_V(r.y);
+    r.z = rev2(v.y); TPS_PIN_V(r.z);
+    r.w = rev2(v.x); TPS_PIN_V(r.w);
+    return r;
+}
 // a loaded quad in LDS order
 TPS_DEV u32x4 stage_orient(const Stage& st, const u32x4& v) {
     if (!st.reverse) return v;
     u32x4 r;
     r.x = rev2(v.w); r.y = rev2(v.z); r.z = rev2(v.y); r.w = rev2(v.x);
     return r;
+}
+// the part of stage_addr / stage_inv_addr that depends on the lane alone (quad c = lane + a wave-uniform count): the fused tiles
+// compute it once per read
+TPS_DEV uint32_t stage_lane_off(bool reverse, int lane) { return reverse ? 16u * (uint32_t)(STAGE_KMAX - lane) : 16u * (uint32_t)lane; }
+// ... and the wave-uniform rest: the address of quad `c0 + lane` is stage_base(st, c0) + stage_lane_off(st.reverse, lane)
+TPS_DEV const uint8_t* stage_base(const Stage& st, int c0) {
+    return (const uint8_t*)(uintptr_t)(st.reverse ? st.q0 - 16ull * STAGE_KMAX - 16ull * (uint32_t)c0 : st.q0 + 16ull * (uint32_t)c0);
+}
+TPS_DEV const uint8_t* stage_inv_base(const Stage& st, int c0) {      // (+ half the lane's offset: 8 bytes of invalid words per quad)
+    return (const uint8_t*)(uintptr_t)(st.reverse ? st.v0 - 8ull * STAGE_KMAX - 8ull * (uint32_t)c0 : st.v0 + 8ull * (uint32_t)c0);
 }
 // the four 16-bit invalid words of a quad (two per dword) in LDS order
 TPS_DEV u32x2 stage_orient_inv(const Stage& st, const u32x2& v) {
@@ -3405,6 +3440,15 @@ TPS_DEV void binseg_from_lc(const ScanArgs& a, const Lds& l, uint64_t lc_g, cons
     // candidate in single precision from the EXACT D (float64 fma, then rounded once), the wave maximum, and only
     // candidates within 1e-4 of it -- two orders of magnitude more than single precision can be off -- go through the
     // float64 fraction comparison below (41 instructions per candidate; the prefilter costs about a third of that).
+#ifndef TPS_PREFILTER_LEAN
+#define TPS_PREFILTER_LEAN 1      // (0: A/B builds with the round-6 prefilter -- float64 D, masked loads)
+#endif
+    // Where n T < 2^31 (wave-uniform; config 2: n = 2 467, T of the order of 3e5) both products of D and D itself fit a signed
+    // 32-bit integer: D is then computed exactly in integers -- b and T b advance by a uniform step from slot to slot -- and
+    // v_cvt_f32_i32 rounds it to nearest-even exactly as the float64 fma's result is rounded by v_cvt_f32_f64: the same d32, bit
+    // for bit, without two conversions to float64, a multiply and an fma per candidate.  Slots past c_max load candidate c_max
+    // (an index clamp instead of a masked load with its zeroed register; their score is replaced by -1 as before).
+    const bool int_d = TPS_PREFILTER_LEAN != 0 && (double)tot * (double)n < 2147483648.0;
     constexpr int LCV = 16;
     const bool prefilter = !a.lc16 && lc_g && exact53 && c_max - c_min < LCV * NT;
     int nslot = c_max >= c_min ? (c_max - c_min + NT) / NT : 0;          // candidate slots per lane that any lane uses
@@ -3421,24 +3465,40 @@ TPS_DEV void binseg_from_lc(const ScanArgs& a, const Lds& l, uint64_t lc_g, cons
     static thread_local int pc_keep[NT];
     float emu_m32 = 0.0f;
 #endif
+    TPS_ISA_REGION(5);
     if (prefilter) {
+        // (one phase per variant, each with its own laundered lane id: written as two branches of one phase the slots' shared index
+        // arithmetic and compares of all sixteen slots are hoisted in front of the branch, used or not)
+        auto prefilter_phase = [&](auto lean_) {
         TPS_PHASE {
             p_s1 = -1.0f; p_s2 = -1.0f; p_lc = 0; p_c = -1;
             // four slots at a time behind ONE uniform test (nslot lives in an SGPR): slots no lane uses cost nothing;
             // the four loads of a group are requested before the first one is used
             auto group = [&](int g) {
+                constexpr bool LEAN = decltype(lean_)::value != 0;
                 uint32_t lcv[4];
                 TPS_UNROLL
                 for (int i = 0; i < 4; ++i) {
                     const int c = c_min + tid + (4 * g + i) * NT;
-                    lcv[i] = c <= c_max ? g32_load(lc_g, (uint32_t)c) : 0u;
+                    if constexpr (LEAN) lcv[i] = g32_load_at(lc_g, 4u * (uint32_t)(c <= c_max ? c : c_max));
+                    else lcv[i] = c <= c_max ? g32_load(lc_g, (uint32_t)c) : 0u;
                 }
+                const int b0 = (c_min + tid + 4 * g * NT) * jump;
+                const uint32_t tb0 = (uint32_t)tot * (uint32_t)b0, tb_step = (uint32_t)tot * (uint32_t)(NT * jump);
                 TPS_UNROLL
                 for (int i = 0; i < 4; ++i) {
                     const int c = c_min + tid + (4 * g + i) * NT;
-                    const int b = c * jump;
-                    const double bf = (double)b;
-                    const float d32 = (float)__builtin_fma(-totf, bf, nf * (double)lcv[i]);
+                    const int b = LEAN ? b0 + i * (NT * jump) : c * jump;
+                    float d32;
+                    if constexpr (LEAN) {
+                        // (T b made opaque: an add per slot; folded into the product it becomes a 64-bit multiply-add per candidate)
+                        uint32_t tb = tb0 + (uint32_t)i * tb_step;
+                        TPS_PIN_V(tb);
+                        d32 = (float)(int32_t)((uint32_t)n * lcv[i] - tb);     // exact: |D| < 2^31
+                    } else {
+                        const double bf = (double)b;
+                        d32 = (float)__builtin_fma(-totf, bf, nf * (double)lcv[i]);
+                    }
                     const float den32 = (float)b * (float)(n - b);
 #ifdef TPS_EMU
                     float s_ = d32 * d32 * (1.0f / den32);
@@ -3463,6 +3523,9 @@ TPS_DEV void binseg_from_lc(const ScanArgs& a, const Lds& l, uint64_t lc_g, cons
             emu_m32 = p_s1 > emu_m32 ? p_s1 : emu_m32;
 #endif
         }
+        };
+        if (int_d) prefilter_phase(IntC<1>());
+        else prefilter_phase(IntC<0>());
         float m32;
 #ifdef TPS_EMU
         m32 = emu_m32;
@@ -3482,6 +3545,7 @@ TPS_DEV void binseg_from_lc(const ScanArgs& a, const Lds& l, uint64_t lc_g, cons
         crowded = __builtin_amdgcn_ballot_w64(p_s2 >= thr32 && p_s2 >= 0.0f) != 0;
 #endif
     }
+    TPS_ISA_REGION(6);
     TPS_PHASE {
         double bn = -1.0, bd = 1.0;
         best_b = -1;
@@ -3560,6 +3624,7 @@ TPS_DEV void binseg_from_lc(const ScanArgs& a, const Lds& l, uint64_t lc_g, cons
     }
 #endif
     (void)misc;
+    TPS_ISA_REGION(7);
     if (crowded) ntie = 2u;                        // the prefilter kept one candidate per lane: a second one that close needs the full comparison
     tie = ntie > 1u;
     if (ntie > 1u) {                               // float noise cannot separate them: exact integers decide
@@ -3779,27 +3844,52 @@ TPS_DEV void scan_read(const ScanArgs& a, int64_t r, uint32_t* lds_base, uint32_
                 // the look-ahead of the self-overlap tests (<= 13 bases in all)
                 const int64_t need = (int64_t)(tw - 1 + tc.q) * prm.slide + tc.r + 13;
                 if (cap > need) cap = need;
-                if (n_stage > cap) n_stage = cap;
-                return stage_plan(a.seq2, a.inv, woff, L, tail == 1, prm.trimfirst, i0, (int)n_stage);
+                // 0 < window <= n_stage <= maxlen < 2^31 (w0_ < n_win; the host rejects a negative trimfirst or maxlen): the minimum in
+                // 32 bits -- the scalar unit has no 64-bit compare, it came out as v_cmp_lt_i64 on a pair of moved registers, twice per tile
+                const int ns32 = (int)n_stage, cap32 = (int)cap;
+                const int n_st = ns32 > cap32 ? cap32 : ns32;
+                return stage_plan(a.seq2, a.inv, woff, L, tail == 1, prm.trimfirst, i0, n_st);
             };
             // Software prefetch: the 16-byte load(s) of the NEXT tile are issued right after the current tile has been
             // copied into LDS and complete while it is being scanned, so a wave pays the HBM latency once per read
             // instead of once per tile.  One quad (64 bases) per lane covers a tile up to slide 7.
             u32x4 pf[PF];
             u32x2 pv[PF];
+            // (ORIENT kernels: the invalid words are loaded for the staged quads of reads that have any, and the store below reads them
+            // for exactly those -- no zeroing per tile)
+            for (int u = 0; u < PF; ++u) pv[u].x = pv[u].y = 0;
 #ifdef TPS_EMU
             u32x4 pf_keep[NT][PF];
             u32x2 pv_keep[NT][PF];
+#endif
+            // The lane's byte offset into a tile's quads depends on the read's orientation alone: one VGPR per read, made opaque so
+            // that it is neither recomputed per tile (a shift, a subtract and a select in every prefetch) nor folded back into it.
+            // Only in the default kernels with one quad per lane and tile (no self-overlap, no raw rows, slide <= 7).  The raw-row
+            // kernels are compiled for five waves per SIMD at 96 VGPRs: one more register alive across the per-pattern tiles costs `_s6r`
+            // 60 more spilled VGPRs (config 5: 483 -> 500 us per step); the self-overlap sums kernels sit at their 80, and with two quads
+            // per lane (slide 8 and up) the second set of loop-carried registers made `_s8so` / `_s8sol` spill.  They keep round 6's code.
+            const bool rv = tail == 1;
+            constexpr bool ORIENT = !RAW && !SO && PF == 1;
+#ifdef TPS_EMU
+#define TPS_PF_OFF(tid_) stage_lane_off(rv, tid_)
+#else
+            uint32_t pf_off = 0;
+            if constexpr (ORIENT) {
+                pf_off = stage_lane_off(rv, (int)(threadIdx.x & 63u));
+                TPS_PIN_V(pf_off);
+            }
+#define TPS_PF_OFF(tid_) (ORIENT ? pf_off : stage_lane_off(rv, tid_))
 #endif
             auto pf_load = [&](const Stage& stn, int tid_) {
                 TPS_UNROLL
                 for (int u = 0; u < PF; ++u) {
                     const int c = tid_ + u * NT;
                     pf[u].x = pf[u].y = pf[u].z = pf[u].w = 0;
-                    pv[u].x = pv[u].y = 0;
+                    if constexpr (!ORIENT) pv[u].x = pv[u].y = 0;
                     if (c < stn.nq) {
-                        pf[u] = load16(stage_addr(stn, c));
-                        if (has_inv) pv[u] = load8(stage_inv_addr(stn, c));
+                        const uint32_t off = TPS_PF_OFF(tid_);
+                        pf[u] = load16(stage_base(stn, u * NT) + off);
+                        if (has_inv) pv[u] = load8(stage_inv_base(stn, u * NT) + (off >> 1));
                     }
 #ifdef TPS_EMU
                     pf_keep[tid_][u] = pf[u];
@@ -3807,6 +3897,7 @@ TPS_DEV void scan_read(const ScanArgs& a, int64_t r, uint32_t* lds_base, uint32_
 #endif
                 }
             };
+            TPS_ISA_REGION(1);
             if (n_win > 0) {
                 const Stage st0 = tile_stage(0);
                 TPS_PHASE {
@@ -3816,9 +3907,11 @@ TPS_DEV void scan_read(const ScanArgs& a, int64_t r, uint32_t* lds_base, uint32_
             }
             for (int w0 = 0, tile = 0; w0 < n_win; w0 += tw, ++tile) {
                 const int nw_tile = (n_win - w0) < tw ? (n_win - w0) : tw;
+                TPS_ISA_REGION(2);
                 const Stage st = tile_stage(w0);
                 // (misc[M_INVALID] / [M_NTIE] are zero here: cleared with the rest of misc at the start of the read and again
                 // by the last phase of every tile -- no extra phase and barrier per tile for that)
+                // (the read's orientation is wave-uniform: a forward tail's quads go to LDS as they were loaded)
                 TPS_PHASE {
                     TPS_UNROLL
                     for (int u = 0; u < PF; ++u) {
@@ -3828,9 +3921,13 @@ TPS_DEV void scan_read(const ScanArgs& a, int64_t r, uint32_t* lds_base, uint32_
                         pv[u] = pv_keep[tid][u];
 #endif
                         if (c < t_::NQ) {              // every quad of the tile buffer is written (zeros past the staged range)
-                            lds_store16(l.seq2 + SEQ_LEAD + 4 * c, stage_orient(st, pf[u]));
+                            if constexpr (!ORIENT) lds_store16(l.seq2 + SEQ_LEAD + 4 * c, stage_orient(st, pf[u]));
+                            else if (rv) lds_store16(l.seq2 + SEQ_LEAD + 4 * c, stage_reversed(pf[u]));
+                            else lds_store16(l.seq2 + SEQ_LEAD + 4 * c, pf[u]);
                             if (has_inv) {
-                                const u32x2 o = stage_orient_inv(st, pv[u]);
+                                u32x2 o;
+                                o.x = o.y = 0;
+                                if (!ORIENT || c < st.nq) o = stage_orient_inv(st, pv[u]);     // (ORIENT: zeros past the staged range)
                                 if (o.x | o.y) l.misc[M_INVALID] = 1u;
                                 lds_store8((uint32_t*)l.val + (SEQ_LEAD >> 1) + 2 * c, o);
                             }
@@ -3844,11 +3941,13 @@ TPS_DEV void scan_read(const ScanArgs& a, int64_t r, uint32_t* lds_base, uint32_
                     }
                 }
                 TPS_SYNC();
+                TPS_ISA_REGION(3);
                 if (w0 + tw < n_win) {
                     const Stage stn = tile_stage(w0 + tw);
                     TPS_PHASE { pf_load(stn, tid); }
                 }
                 if (w0 == 0) TPS_STAMP(5);
+                TPS_ISA_REGION(4);
                 const int fdelta = st.delta + 16 * SEQ_LEAD;      // LDS position of the tile's first base
                 if constexpr (RAW) {
                     // per-pattern tiles: raw counts wanted, or a table with one self-overlap period (exact without recounts)
@@ -3945,6 +4044,7 @@ TPS_DEV void scan_read(const ScanArgs& a, int64_t r, uint32_t* lds_base, uint32_
                 }
                 if (w0 == 0) TPS_STAMP(8);
             }
+#undef TPS_PF_OFF
         }
     }
     res.n_win = n_win;
