@@ -49,7 +49,7 @@ extern "C" {
 #define TPS_E_NO_DEVICE  -1   /* no HIP device / device index out of range              */
 #define TPS_E_HIP        -2   /* a HIP runtime call failed (message has the HIP error)  */
 #define TPS_E_ARG        -3   /* invalid argument                                        */
-#define TPS_E_PATTERN    -4   /* pattern table not set / unsupported (non-ACGT, k>15, P>31) */
+#define TPS_E_PATTERN    -4   /* pattern table not set / unsupported (non-ACGT, k>15, P>31; wide tables: k>32, P>64) */
 #define TPS_E_CAPACITY   -5   /* parameter combination does not fit the kernel's LDS plan */
 #define TPS_E_STATE      -6   /* call order (e.g. scan before upload)                    */
 
@@ -57,6 +57,8 @@ extern "C" {
 #define TPS_MAX_K         15  /* k-mer length: 4^k-entry LDS table up to TPS_DIRECT_K, a perfect-hash table above */
 #define TPS_DIRECT_K      7
 #define TPS_MAX_PATTERNS 31   /* patterns in one table (bit 31 of the mask is a flag)       */
+#define TPS_WIDE_MAX_K        32  /* wide tables (tps_set_patterns_wide): a k-mer's 2-bit code fits 64 bits          */
+#define TPS_WIDE_MAX_PATTERNS 64  /* ... and a 32-letter motif has 64 patterns at every k                            */
 
 /* flags for tps_params.flags */
 #define TPS_F_STEP1      1u   /* run the TRC step (a3) and choose tail / pass per read       */
@@ -133,6 +135,15 @@ const char* tps_last_error(void);
  * order (sorted k-mers then their complements, allsteps.py:104-120); order defines pattern
  * indices (first-max tie-break, raw count column order). */
 int  tps_set_patterns(tps_ctx* ctx, const char* pats, int32_t n_patterns, int32_t k);
+/* The same for tables beyond TPS_MAX_K / TPS_MAX_PATTERNS: 1 <= k <= TPS_WIDE_MAX_K letters, 1 <= n_patterns <= TPS_WIDE_MAX_PATTERNS
+ * -- the reference's defaults (k = len - 2, 2 len patterns: Topsicle/main.py:189-193) for every motif of 16 to 32 letters.  Any list
+ * of equal-length ACGT strings in reference order is legal: duplicates, k-mers that overlap themselves, narrow tables too.  While a
+ * wide table is current tps_batch_scan launches ONE kernel for every slide and flag combination (tps_scan_kernel_wide: 64-bit k-mer
+ * codes, a hash of the distinct codes, counts per window by sliding) and every call downstream of the scan works unchanged; the
+ * one-shot calls scan with it too.  tps_batch_kmer_followers keeps n_fwd <= 15 and refuses a wide table.  A window that can hold more
+ * than 255 occurrences of a k-mer ((window - 1) / k > 255), or a window / step-1 head of more than 32768 bases, is TPS_E_CAPACITY.
+ * The next tps_set_patterns makes the narrow kernels current again; either call re-plans every resident batch. */
+int  tps_set_patterns_wide(tps_ctx* ctx, const char* pats, int32_t n_patterns, int32_t k);
 
 /* ---- resident batch (throughput path) ------------------------------------------------ */
 /* Copy a batch of reads into HBM.  `slot` (0..TPS_MAX_SLOTS-1) names one resident batch so

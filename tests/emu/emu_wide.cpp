@@ -1,0 +1,87 @@
+// TEST INFRASTRUCTURE ONLY -- sequential host emulation of the wide-table scan kernel (topsicle_amd/csrc/tps_wide.h).
+//
+// Like emu_scan.cpp for tps_device.h: the header compiled with -DTPS_EMU, TPS_PHASE looping over the 64 lane ids, the table and
+// the LDS plan built by the very functions the library calls (tps_wide_plan.h).  Never linked into the product.
+#define TPS_EMU 1
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../topsicle_amd/csrc/tps_wide.h"
+#include "../../topsicle_amd/csrc/tps_wide_plan.h"
+#include "../../topsicle_amd/csrc/tps_pack.h"
+#include "../../topsicle_amd/csrc/tps_plan.h"
+
+static std::string g_err;
+extern "C" const char* emu_wide_last_error() { return g_err.c_str(); }
+
+// the table alone: rc, and out8 = {n_groups, n_so, rot, mul, used slots, mask_lo, mask_hi, 0}
+extern "C" int emu_wide_table(const char* pats, int P, int k, uint32_t* out8) {
+    std::vector<uint32_t> img;
+    tps::WidePat wp;
+    std::string err = tps::build_wide_table(pats, P, k, img, wp);
+    if (!err.empty()) { g_err = err; return TPS_E_PATTERN; }
+    uint32_t used = 0;
+    for (int s = 0; s < tps::WIDE_SLOTS; ++s) used += img[4 * (size_t)s + 2] != 0;
+    out8[0] = (uint32_t)wp.n_groups; out8[1] = (uint32_t)wp.n_so; out8[2] = wp.rot; out8[3] = wp.mul; out8[4] = used;
+    out8[5] = wp.mask_lo; out8[6] = wp.mask_hi; out8[7] = 0;
+    return TPS_OK;
+}
+
+// One scan over a batch, like tps_set_patterns_wide + tps_batch_upload + tps_batch_scan + downloads.  base_shift moves the
+// batch inside its buffer by whole quads; words the layout does not own are garbage.
+extern "C" int emu_wide_scan(const char* pats, int P, int k, const uint8_t* bases, const int64_t* offsets, int64_t n,
+                             const uint8_t* tails, const tps_params* prm, int base_shift, tps_read_result* results,
+                             int32_t* c_start, int32_t* c_end, int64_t* win_off_out, int32_t* sums, uint8_t* raw) {
+    std::vector<uint32_t> img;
+    tps::WideArgs a{};
+    std::string err = tps::build_wide_table(pats, P, k, img, a.pat);
+    if (!err.empty()) { g_err = err; return TPS_E_PATTERN; }
+    if (prm->window < 1 || prm->slide < 1 || prm->trimfirst < 0 || prm->maxlen < 0 || prm->no_bp < 0) { g_err = "bad window/slide/trimfirst/maxlen/no_bp"; return TPS_E_ARG; }
+    err = tps::plan_wide(a, *prm, 160 * 1024 / 4);
+    if (!err.empty()) { g_err = err; return TPS_E_CAPACITY; }
+    std::vector<int64_t> win_off((size_t)n + 1);
+    int64_t acc = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        win_off[(size_t)i] = acc;
+        acc += tps::window_count(offsets[i + 1] - offsets[i], prm->window, prm->slide, prm->trimfirst, prm->maxlen);
+    }
+    win_off[(size_t)n] = acc;
+    if (win_off_out) memcpy(win_off_out, win_off.data(), (size_t)(n + 1) * 8);
+
+    std::vector<tps_read_desc> desc((size_t)(n > 0 ? n : 1));
+    const int64_t n_words = tps::pack_layout(offsets, n, desc.data());
+    const int64_t lead = 4 * (int64_t)(base_shift & 3);
+    std::vector<uint32_t> seq2buf((size_t)(n_words + lead + 8), 0xDEADBEEFu);
+    std::vector<uint16_t> invbuf((size_t)(n_words + lead + 8), (uint16_t)0xFFFFu);
+    for (int64_t i = 0; i < n; ++i) desc[(size_t)i].word_off += lead;
+    tps::pack_range(bases, offsets, 0, n, desc.data(), seq2buf.data(), invbuf.data());
+    a.seq2 = seq2buf.data();
+    a.inv = invbuf.data();
+    a.desc = desc.data();
+    a.tails_in = ((prm->flags & TPS_F_TAILS_IN) && !(prm->flags & TPS_F_STEP1)) ? tails : nullptr;
+    a.results = results;
+    a.c_start = (prm->flags & TPS_F_STEP1) ? c_start : nullptr;
+    a.c_end = (prm->flags & TPS_F_STEP1) ? c_end : nullptr;
+    a.win_off = win_off.data();
+    a.sums = sums;
+    a.raw = (prm->flags & TPS_F_STORE_RAW) ? raw : nullptr;
+    a.n_reads = n;
+    a.prm = *prm;
+    // the workgroup's copy of the table image, 16-byte aligned like LDS
+    std::vector<uint32_t> imgbuf((size_t)tps::WIDE_IMG_DW + 4);
+    uint32_t* img_al = (uint32_t*)(((uintptr_t)imgbuf.data() + 15) & ~(uintptr_t)15);
+    memcpy(img_al, img.data(), (size_t)tps::WIDE_IMG_DW * 4);
+    a.img = img_al;
+    // exactly the planned wave slice: the sanitizer build sees every access past it
+    const size_t dw = (size_t)tps::wide_lds_dwords(a);
+    uint32_t* lds = nullptr;
+    if (posix_memalign((void**)&lds, 16, dw * 4)) { g_err = "out of memory"; return TPS_E_ARG; }
+    for (int64_t r = 0; r < n; ++r) {
+        for (size_t i = 0; i < dw; ++i) lds[i] = 0xDEADBEEFu;       // LDS content is undefined at workgroup start
+        tps::wide_read(a, r, lds, img_al);
+    }
+    free(lds);
+    return TPS_OK;
+}

@@ -95,7 +95,7 @@ def patternTRC_count(filepath, telopattern, read_length=0, kmer=4, no_bp=1000, c
     patterns = patterns_to_search(telopattern, cut_length=kmer)
     ratio = no_bp / len(telopattern)
     eng = get_engine()
-    eng.set_patterns(patterns)
+    hiplib.set_table(eng, patterns)
     rows = []
     prm = hiplib.make_params(no_bp=no_bp, min_len=read_length, min_count=min_count_for_cutoff(cutoff, ratio, no_bp),
                              flags=hiplib.F_STEP1)
@@ -126,7 +126,7 @@ def seq_cut_windows(s, window_size, step):
 # ---------------------------------------------------------------------------- a5 / a6
 def _window_scan(seq, tails, patterns, windowSize, slide, trimfirst, maxlengthtelo, raw=False):
     eng = get_engine()
-    eng.set_patterns(patterns)
+    hiplib.set_table(eng, patterns)
     bases, offsets = hiplib.pack_reads([seq] * len(tails))
     tv = np.array([0 if t == "forward" else 1 for t in tails], dtype=np.uint8)
     return eng.window_counts(bases, offsets, tv, windowSize, slide, trimfirst, maxlengthtelo, raw=raw)

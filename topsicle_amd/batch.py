@@ -127,12 +127,12 @@ def scan_jobs_heads(engine, recs, jobs, slot: int = 0, seq=None):
                 if eng is not engine:
                     eng.share(slot, engine, slot)
                 if getattr(eng, "patterns", None) != job.patterns:
-                    eng.set_patterns(job.patterns)
+                    hiplib.set_table(eng, job.patterns)
                 eng.scan(slot, p)
         for n, (eng, job, p) in enumerate(zip(engines, jobs, prm_a)):
             if not concurrent:
                 if len(jobs) > 1 or getattr(eng, "patterns", None) != job.patterns:
-                    eng.set_patterns(job.patterns)
+                    hiplib.set_table(eng, job.patterns)
                 eng.scan(slot, p)
             eng.sync()
             res_a.append(eng.results(slot))
@@ -154,7 +154,7 @@ def scan_jobs_heads(engine, recs, jobs, slot: int = 0, seq=None):
                 tails = ra["tail"][idx].astype(np.uint8)
                 key = (idx.tobytes(), tails.tobytes(), int(job.prm.maxlen))
                 if not concurrent and len(jobs) > 1 and getattr(eng, "patterns", None) != job.patterns:
-                    eng.set_patterns(job.patterns)
+                    hiplib.set_table(eng, job.patterns)
                 if holds.get(id(eng)) != key:
                     owner = uploaded.get(key)
                     if owner is not None and owner is not eng and holds.get(id(owner)) == key and hasattr(eng, "share"):
@@ -241,12 +241,12 @@ def scan_jobs(engine, recs, jobs, slot: int = 0, seq=None):
                 if eng is not engine:
                     eng.share(slot, engine, slot)
                 if getattr(eng, "patterns", None) != job.patterns:
-                    eng.set_patterns(job.patterns)
+                    hiplib.set_table(eng, job.patterns)
                 eng.scan(slot, p)
         for n, (eng, job, p) in enumerate(zip(engines, jobs, prms)):
             if not concurrent:
                 if len(jobs) > 1 or getattr(eng, "patterns", None) != job.patterns:
-                    eng.set_patterns(job.patterns)
+                    hiplib.set_table(eng, job.patterns)
                 eng.scan(slot, p)
             eng.sync()
             if n == 0 and hasattr(recs, "release"):
@@ -301,7 +301,7 @@ class EnginePool:
         self.patterns = None if patterns is None else list(patterns)
         if self.patterns is not None:
             for e in self.engines:
-                e.set_patterns(self.patterns)
+                hiplib.set_table(e, self.patterns)
 
     # -- sources
     def scan_file(self, filepath, prm, want_sums=False, want_raw=False, max_bases=None):

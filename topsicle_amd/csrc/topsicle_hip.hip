@@ -23,6 +23,8 @@
 #include "tps_device.h"
 #include "tps_pack.h"
 #include "tps_plan.h"
+#include "tps_wide.h"
+#include "tps_wide_plan.h"
 
 // ======================================================================== kernels
 // The scan kernels live in tps_kernels.h (one macro body, instantiated per slide / table kind / outputs).  Compiled alone,
@@ -47,6 +49,24 @@ extern "C" __global__ void __launch_bounds__(tps::NT * tps::WPG) tps_stride_kern
     uint32_t* mine = smem + wave * (tps::BINSEG_SMEM_DW + a.s16_dw);
     tps::stride_read(a, r, mine, a.s16_dw ? (uint16_t*)(mine + tps::BINSEG_SMEM_DW) : nullptr);
 }
+
+// Wide pattern tables (tps_set_patterns_wide; csrc/tps_wide.h): one wave per read like the scan kernels above, the workgroup's table
+// image (hash table, group multiplicities, pattern -> group) copied into LDS once.  Compiled for four waves per SIMD (<= 128 VGPRs).
+#if !defined(TPS_KGROUP) || TPS_KGROUP == 0
+extern "C" __global__ void __launch_bounds__(tps::NT * tps::WPG, 4) tps_scan_kernel_wide(tps::WideArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    for (int c = 4 * (int)threadIdx.x; c < tps::WIDE_IMG_DW; c += 4 * tps::NT * tps::WPG)
+        *(uint4*)(lds + c) = *(const uint4*)(a.img + c);
+    __syncthreads();
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    uint32_t* slice = lds + tps::WIDE_IMG_DW + wave * tps::wide_lds_dwords(a);
+    const int64_t slot = (int64_t)blockIdx.x * tps::WPG + wave;
+    if (slot < a.n_reads) {
+        const int64_t r = a.order ? (int64_t)__builtin_amdgcn_readfirstlane(a.order[slot]) : slot;
+        tps::wide_read(a, r, slice, lds);
+    }
+}
+#endif
 
 extern "C" __global__ void __launch_bounds__(tps::NT * tps::WPG) tps_followers_kernel(tps::FollowArgs a) {
     __shared__ __attribute__((aligned(16))) uint32_t smem[tps::WPG * tps::FOLLOW_LDS_DW];
@@ -251,6 +271,12 @@ struct Slot {
     bool rows_inline = false;            // ... and it did (last scan)
     int stride_base = 0;                 // of the cached plan: 0 = the planned kernel runs itself
     std::string info_name;               // kernel_name of a strided scan ("<base kernel> every <m>th window")
+    // cached plan of the wide kernel (do_scan_wide): by parameters and by the table's serial number -- any tps_set_patterns* call
+    // drops it, like `planned`
+    bool wplanned = false;
+    tps_params wplan_prm{};
+    uint64_t wplan_table = 0;
+    tps::WideArgs wargs{};
 };
 
 struct EventPair { hipEvent_t a, b; };
@@ -266,6 +292,13 @@ struct tps_ctx {
     struct Table { DevBuf dev; int P = 0, k = 0; std::string key; tps::PatInfo pat{}; size_t off_e32 = 0, off_fld = 0, off_m16 = 0, off_f16 = 0, off_p16 = 0, off_pfld = 0; };
     std::deque<Table> tables;         // resident pattern tables (deque: pointers to elements stay valid)
     Table* lut_cur = nullptr;
+    // wide tables (tps_set_patterns_wide): the image tps_scan_kernel_wide copies into LDS; `serial` names a table in the slots' plans
+    struct WideTable { DevBuf dev; std::string key; int P = 0, k = 0; tps::WidePat pat{}; uint64_t serial = 0; };
+    std::deque<WideTable> wtables;
+    WideTable* wide_cur = nullptr;    // non-null: the current table is a wide one, tps_batch_scan launches the wide kernel
+    size_t wtable_rr = 0;
+    uint64_t table_serial = 0;
+    size_t lds_set_wide = 0;
     size_t table_rr = 0;
     DevBuf follow_picks, follow_hist; // outputs of tps_batch_kmer_followers
     DevBuf ascii, ascii_off;          // staging of tps_batch_upload: ASCII bases + offsets, packed on the device right after the copy
@@ -322,8 +355,18 @@ int check_params(const tps_params& p) {
     return TPS_OK;
 }
 
+// a table or knob change: every cached plan goes, the strided scans' hidden sub-slots included
+void drop_plans(tps_ctx* c) {
+    for (auto& sl : c->slots) {
+        sl.planned = false;
+        sl.wplanned = false;
+        if (sl.sub) { sl.sub->planned = false; sl.sub->wplanned = false; }
+    }
+}
+
 void reset_slot(Slot& sl, int64_t n, int64_t n_words) {
     sl.sub_stale = true;
+    sl.wplanned = false;
     sl.n = n;
     sl.n_words = n_words;
     sl.has_tails = false;
@@ -512,9 +555,130 @@ int do_scan_strided(tps_ctx* c, Slot& sl, const tps_params& prm, int base, hipEv
     return TPS_OK;
 }
 
+// The scan while a wide table is current: one kernel for every slide and flag combination, outputs in the generic kernel's layout
+// (results in mapped host memory, c_start / c_end, int32 sums at win_off, u8 rows at win_off * P), so everything downstream is shared.
+int do_scan_wide(tps_ctx* c, Slot& sl, const tps_params& prm) {
+    int rc;
+    if (sl.n < 0) return fail(TPS_E_STATE, "no batch uploaded in this slot");
+    if ((rc = check_params(prm))) return rc;
+    if (!(prm.flags & TPS_F_STEP1) && (prm.flags & TPS_F_TAILS_IN) && !sl.has_tails)
+        return fail(TPS_E_STATE, "TPS_F_TAILS_IN without tps_batch_set_tails");
+    const tps_ctx::WideTable& wt = *c->wide_cur;
+    const int64_t n = sl.n;
+    const int P = wt.P;
+    if (!sl.wplanned || !same_params(prm, sl.wplan_prm) || sl.wplan_table != wt.serial) {
+        tps::WideArgs w{};
+        w.pat = wt.pat;
+        const size_t lds_max = c->prop.sharedMemPerBlock > 0 ? std::min<size_t>(c->prop.sharedMemPerBlock, 160 * 1024) : 64 * 1024;
+        const std::string err = tps::plan_wide(w, prm, (int64_t)lds_max / 4);
+        if (!err.empty()) return fail(TPS_E_CAPACITY, "%s", err.c_str());
+        sl.h_win_off.resize((size_t)n + 1);
+        std::vector<int64_t> nwv((size_t)n);
+        std::vector<uint8_t> longer((size_t)n);
+        int64_t acc = 0;
+        for (int64_t i = 0; i < n; ++i) {
+            sl.h_win_off[(size_t)i] = acc;
+            const int64_t len = sl.h_offsets[i + 1] - sl.h_offsets[i];
+            const int64_t nw = window_count(len, prm.window, prm.slide, prm.trimfirst, prm.maxlen);
+            acc += nw;
+            nwv[(size_t)i] = (prm.flags & TPS_F_WINDOWS) ? nw : 0;
+            longer[(size_t)i] = !(prm.flags & TPS_F_STEP1) || len > prm.min_len;
+        }
+        sl.h_win_off[(size_t)n] = acc;
+        sl.h_order.clear();
+        if (!c->file_order) tps::plan_dispatch_order(nwv.data(), longer.data(), n, sl.h_order);
+        if (!sl.h_order.empty()) {
+            if ((rc = sl.order.ensure((size_t)n * 4))) return rc;
+            HIP_TRY(hipMemcpyAsync(sl.order.p, sl.h_order.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+        }
+        if ((rc = sl.win_off.ensure((size_t)(n + 1) * 8))) return rc;
+        HIP_TRY(hipMemcpyAsync(sl.win_off.p, sl.h_win_off.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        sl.wargs = w;
+        sl.wplan_prm = prm;
+        sl.wplan_table = wt.serial;
+        sl.wplanned = true;
+    }
+    // what the shared downstream calls look at: no fused layout, the wide P, this kernel's name; a later narrow scan plans afresh
+    sl.planned = false;
+    sl.args = tps::ScanArgs{};
+    sl.args.wpg = sl.wargs.wpg;
+    sl.plan_p = P;
+    sl.plan_k = wt.k;
+    sl.stride_base = 0;
+    sl.rows_inline = false;
+    sl.lds_bytes = (size_t)tps::wide_wg_lds_dwords(sl.wargs) * 4;
+    static const char wide_name[] = "tps_scan_kernel_wide";
+    sl.kernel_name = wide_name;
+    sl.last_flags = prm.flags;
+    const int64_t total_win = sl.h_win_off[(size_t)n];
+    if (sl.h_results_cap < (size_t)n) {
+        if (sl.h_results) (void)hipHostFree(sl.h_results);
+        sl.h_results = nullptr;
+        size_t want = (size_t)n + (size_t)n / 8 + 16;
+        HIP_TRY(hipHostMalloc((void**)&sl.h_results, want * sizeof(tps_read_result), hipHostMallocMapped));
+        sl.h_results_cap = want;
+    }
+    tps::WideArgs& a = sl.wargs;
+    a.seq2 = (const uint32_t*)sl.seq2.p;
+    a.inv = (const uint16_t*)sl.inv.p;
+    a.desc = (const tps_read_desc*)sl.desc.p;
+    a.tails_in = ((prm.flags & TPS_F_TAILS_IN) && !(prm.flags & TPS_F_STEP1)) ? (const uint8_t*)sl.tails.p : nullptr;
+    a.img = (const uint32_t*)wt.dev.p;
+    a.results = sl.h_results;
+    a.c_start = a.c_end = nullptr;
+    if (prm.flags & TPS_F_STEP1) {
+        if ((rc = sl.c_start.ensure((size_t)std::max<int64_t>(n * P, 1) * 4))) return rc;
+        if ((rc = sl.c_end.ensure((size_t)std::max<int64_t>(n * P, 1) * 4))) return rc;
+        a.c_start = (int32_t*)sl.c_start.p;
+        a.c_end = (int32_t*)sl.c_end.p;
+    }
+    a.win_off = (const int64_t*)sl.win_off.p;
+    a.order = sl.h_order.empty() ? nullptr : (const int32_t*)sl.order.p;
+    a.sums = nullptr;
+    a.raw = nullptr;
+    if (prm.flags & TPS_F_WINDOWS) {
+        if ((rc = sl.sums.ensure((size_t)std::max<int64_t>(total_win, 1) * 4))) return rc;
+        a.sums = (int32_t*)sl.sums.p;
+    }
+    if (prm.flags & TPS_F_STORE_RAW) {
+        if ((rc = sl.raw.ensure((size_t)std::max<int64_t>(total_win * P, 1)))) return rc;
+        a.raw = (uint8_t*)sl.raw.p;
+    }
+    a.n_reads = n;
+    a.prm = prm;
+    if (n == 0) { sl.scanned = true; return TPS_OK; }
+    if (sl.lds_bytes > c->lds_set_wide) {
+        HIP_TRY(hipFuncSetAttribute((const void*)tps_scan_kernel_wide, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sl.lds_bytes));
+        c->lds_set_wide = sl.lds_bytes;
+    }
+    if (c->ev_used == c->ev_pool.size()) {
+        if (c->ev_pool.size() >= 16384) {
+            c->ev_used = c->ev_base = 0;
+        } else {
+            const size_t grow = c->ev_pool.empty() ? 512 : c->ev_pool.size();
+            for (size_t i = 0; i < grow; ++i) {
+                EventPair ep;
+                HIP_TRY(hipEventCreate(&ep.a));
+                HIP_TRY(hipEventCreate(&ep.b));
+                c->ev_pool.push_back(ep);
+            }
+        }
+    }
+    const bool timed = !c->no_events && (c->launch_seq++ % (uint64_t)c->event_stride) == 0;
+    EventPair& ep = c->ev_pool[timed ? c->ev_used++ : 0];
+    const int64_t grid = (n + a.wpg - 1) / a.wpg;
+    void* kargs[] = {(void*)&a};
+    HIP_TRY(hipExtLaunchKernel((const void*)tps_scan_kernel_wide, dim3((unsigned)grid), dim3(tps::NT * a.wpg), kargs, sl.lds_bytes, c->stream,
+                               timed ? ep.a : nullptr, timed ? ep.b : nullptr, 0));
+    sl.scanned = true;
+    return TPS_OK;
+}
+
 int do_scan(tps_ctx* c, Slot& sl, const tps_params& prm, bool inner, hipEvent_t ev_start) {
     int rc;
     if (!c->have_pat) return fail(TPS_E_PATTERN, "tps_set_patterns has not been called");
+    if (c->wide_cur) return do_scan_wide(c, sl, prm);
     if (sl.n < 0) return fail(TPS_E_STATE, "no batch uploaded in this slot");
     if ((rc = check_params(prm))) return rc;
     if (!(prm.flags & TPS_F_STEP1) && (prm.flags & TPS_F_TAILS_IN) && !sl.has_tails)
@@ -804,6 +968,7 @@ int tps_ctx_destroy(tps_ctx* c) {
         if (sl.h_results) (void)hipHostFree(sl.h_results);
     }
     for (auto& t : c->tables) t.dev.release();
+    for (auto& t : c->wtables) t.dev.release();
     c->ascii.release();
     c->ascii_off.release();
     c->nib.release();
@@ -857,7 +1022,8 @@ int tps_set_patterns(tps_ctx* c, const char* pats, int32_t P, int32_t k) {
             c->lut_cur = &t;
             c->pat = t.pat;
             c->have_pat = true;
-            for (auto& sl : c->slots) sl.planned = false;
+            c->wide_cur = nullptr;
+            drop_plans(c);
             return TPS_OK;
         }
     std::vector<uint32_t> lut;
@@ -921,7 +1087,40 @@ int tps_set_patterns(tps_ctx* c, const char* pats, int32_t P, int32_t k) {
     c->lut_cur = slot;
     c->pat = pi;
     c->have_pat = true;
-    for (auto& sl : c->slots) sl.planned = false;     // kernel choice and LDS plan depend on the table (periods, duplicates, k)
+    c->wide_cur = nullptr;
+    drop_plans(c);                                     // kernel choice and LDS plan depend on the table (periods, duplicates, k)
+    return TPS_OK;
+}
+
+int tps_set_patterns_wide(tps_ctx* c, const char* pats, int32_t P, int32_t k) {
+    int rc;
+    if ((rc = bind(c))) return rc;
+    if (!pats) return fail(TPS_E_ARG, "null pattern table");
+    if (P < 1 || k < 1 || P > TPS_WIDE_MAX_PATTERNS || k > TPS_WIDE_MAX_K) return fail(TPS_E_PATTERN, "%d patterns of %d letters not supported", P, k);
+    const std::string key(pats, (size_t)P * (size_t)k);
+    tps_ctx::WideTable* cur = nullptr;
+    for (auto& t : c->wtables)
+        if (t.P == P && t.k == k && t.key == key) cur = &t;
+    if (!cur) {
+        std::vector<uint32_t> img;
+        tps::WidePat wp{};
+        const std::string err = tps::build_wide_table(pats, P, k, img, wp);
+        if (!err.empty()) return fail(TPS_E_PATTERN, "%s", err.c_str());
+        HIP_TRY(hipStreamSynchronize(c->stream));          // no launch may still be reading the table that gets recycled
+        if (c->wtables.size() < 6) { c->wtables.emplace_back(); cur = &c->wtables.back(); }
+        else { cur = &c->wtables[c->wtable_rr++ % c->wtables.size()]; }
+        if ((rc = cur->dev.ensure(img.size() * 4))) return rc;
+        HIP_TRY(hipMemcpyAsync(cur->dev.p, img.data(), img.size() * 4, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        cur->P = P; cur->k = k; cur->key = key; cur->pat = wp;
+        cur->serial = ++c->table_serial;
+    }
+    c->wide_cur = cur;
+    c->pat = tps::PatInfo{};                           // (what the shared host code reads of the narrow table's description: P and k)
+    c->pat.P = P;
+    c->pat.k = k;
+    c->have_pat = true;
+    drop_plans(c);
     return TPS_OK;
 }
 
@@ -1027,6 +1226,7 @@ int tps_batch_kmer_followers(tps_ctx* c, int32_t slot, int32_t n_fwd, int32_t fo
     Slot* sl = get_slot(c, slot);
     if (!sl) return TPS_E_ARG;
     if (!c->have_pat) return fail(TPS_E_PATTERN, "tps_set_patterns has not been called");
+    if (c->wide_cur) return fail(TPS_E_PATTERN, "tps_batch_kmer_followers does not take a wide pattern table (n_fwd <= 15: set the table with tps_set_patterns)");
     if (sl->n < 0) return fail(TPS_E_STATE, "no batch uploaded in this slot");
     if (n_fwd < 1 || n_fwd > 15 || 2 * n_fwd > c->pat.P) return fail(TPS_E_ARG, "n_fwd must be 1..15 and the table must hold the complements behind the k-mers");
     if (follow < 0 || follow > 8) return fail(TPS_E_CAPACITY, "follow must be 0..8 bases");
@@ -1364,6 +1564,7 @@ int tps_binseg_l2_ties(tps_ctx* c, const int32_t* sums, const int64_t* win_off, 
     if ((rc = sl.win_off.ensure((size_t)(n + 1) * 8))) return rc;
     if ((rc = sl.results.ensure((size_t)n * 17))) return rc;          // gain (8n), bkp (4n), tie (n): gain first for alignment
     sl.planned = false;                                                // the slot's plan buffers were overwritten
+    sl.wplanned = false;
     sl.scanned = false;
     if (nw) HIP_TRY(hipMemcpyAsync(sl.sums.p, sums, (size_t)nw * 4, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(sl.win_off.p, win_off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, c->stream));
@@ -1418,7 +1619,7 @@ int tps_ctx_debug_option(tps_ctx* c, const char* key, int64_t value) {
     else if (k == "no_stride") c->no_stride = value != 0;
     else if (k == "no_inline_rows") c->no_inline_rows = value != 0;
     else return fail(TPS_E_ARG, "unknown debug option '%s' (event_stride, no_events, force_generic, spans_per_tile, force_pair, so_order, wpg, stamps, file_order, no_stride, no_inline_rows)", key);
-    for (auto& sl : c->slots) sl.planned = false;
+    drop_plans(c);
     return TPS_OK;
 }
 

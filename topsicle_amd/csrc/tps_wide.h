@@ -1,0 +1,383 @@
+// tps_wide.h -- the scan of WIDE pattern tables (tps_set_patterns_wide: up to 64 patterns of up to 32 letters), one kernel.
+//
+// The kernels of tps_device.h are built on 32-bit pattern masks and 32-bit k-mer codes; this one is not, and shares only the resident
+// batch, the staging (stage_plan / stage_thread), the change point (binseg_wg) and the outputs' layout with them.  One wave owns one
+// read, as there.  What differs:
+//   * the code of a position is 64 bits wide: four staged dwords, three funnel shifts per 16 positions and two per position;
+//   * the table is a collision-free hash of the distinct codes (host: tps_wide_plan.h): the code is folded to 32 bits
+//     (lo + rotate(hi): an XOR would send every homopolymer of 32 letters to 0), ONE 32-bit multiply picks one of 256 slots, one
+//     16-byte LDS read gives (key lo, key hi, group + 1), the whole key is compared.  An unused slot holds group + 1 = 0: no code is reserved as a marker (all ones IS a code at k = 32);
+//   * a position holds at most one distinct k-mer, so the table yields a GROUP id (the distinct codes, numbered with the
+//     self-overlapping ones first), not a mask; one byte per position (group + 1, 0 = nothing) is what the counting phases read.
+//     Duplicates of the list are a group -> patterns map (pg[]) applied when counts leave;
+//   * windows are counted by LANES: a lane takes m consecutive windows of the tile, counts the first one position by position and
+//     then SLIDES -- the positions that leave are taken off, the ones that enter are added (2 x slide byte reads per window instead
+//     of W - k), the counts of the lane's current window live in 64 private LDS bytes.  S_w = sum of max(1, count) is kept as a
+//     running value: an occurrence that makes a count 2 or more adds the group's number of list patterns, one that leaves a count
+//     of 1 or more takes it off.  That is exact for every k-mer without a period (two occurrences cannot overlap).  Only groups
+//     WITH a period (homopolymers, ACAC...) are walked leftmost-first per window, and only in windows that hold one of them;
+//   * raw rows leave through the whole wave: after every step the 64 lanes hold one finished window each, and lane (window, pattern)
+//     stores one byte -- a row is one contiguous piece of HBM;
+//   * the change point is binseg_wg on the stored sums, in the same launch (the standalone kernel's arithmetic, TPS_RES_TIE alike).
+//
+// Compiles under TPS_EMU like tps_device.h (tests/emu/emu_wide.cpp).
+#pragma once
+#include "tps_device.h"
+
+namespace tps {
+
+constexpr int WIDE_SLOTS = 256;                       // hash slots of 16 bytes: 4 KB per workgroup
+constexpr int WIDE_TAB_DW = 4 * WIDE_SLOTS;
+constexpr int WIDE_GM_DW = 64;                        // per group: how many list patterns spell it
+constexpr int WIDE_PG_DW = 16;                        // per list pattern: its group (bytes)
+constexpr int WIDE_IMG_DW = WIDE_TAB_DW + WIDE_GM_DW + WIDE_PG_DW;
+constexpr int WIDE_CS = 17;                           // dwords of a lane's 64 byte counters (+ 1: the lanes' rows start on different banks)
+constexpr int WIDE_CNT_DW = NT * WIDE_CS;             // also step 1's histogram and the change point's scratch
+constexpr int WIDE_TP_MIN = 4096;                     // positions a tile holds at least
+constexpr int WIDE_TP_MAX = 32768;                    // ... and at most (a window or step-1 head longer than that is refused)
+
+struct WidePat {
+    int32_t P, k;
+    int32_t n_groups;        // distinct k-mers of the list
+    int32_t n_so;            // groups 0 .. n_so - 1 can overlap themselves (have a period < k)
+    uint32_t mask_lo, mask_hi;   // the low 2k bits
+    uint32_t rot, mul;       // slot = ((lo + rotate_right(hi, rot)) * mul) >> 24
+};
+
+struct WideArgs {
+    const uint32_t* seq2;        // the resident packed batch, as in ScanArgs
+    const uint16_t* inv;
+    const tps_read_desc* desc;
+    const uint8_t* tails_in;     // n, or nullptr
+    const uint32_t* img;         // WIDE_IMG_DW dwords: hash table, group multiplicities, pattern -> group
+    tps_read_result* results;
+    int32_t* c_start;            // n * P or nullptr
+    int32_t* c_end;
+    const int64_t* win_off;      // n + 1
+    int32_t* sums;               // int32 at win_off[r] (whenever the window step runs)
+    uint8_t* raw;                // u8 at win_off[r] * P, or nullptr
+    const int32_t* order;        // n, or nullptr (plan_dispatch_order)
+    int64_t n_reads;
+    WidePat pat;
+    tps_params prm;
+    int32_t tp_cap;              // positions a tile can hold
+    int32_t tw;                  // windows per tile
+    int32_t seq_dw;              // dwords of the staged bases
+    int32_t wpg;                 // waves per workgroup
+};
+
+TPS_HD int64_t wide_nx_dw(const WideArgs& a) { return ((int64_t)NT * a.pat.n_so + 1) / 2; }
+TPS_HD int64_t wide_lds_dwords(const WideArgs& a) {          // per wave
+    const int64_t dw = WIDE_CNT_DW + 2 * NT + a.seq_dw + (a.seq_dw / 2 + 4) + (a.tp_cap / 4 + 8) + wide_nx_dw(a) + MISC_DW;
+    return (dw + 3) & ~3ll;
+}
+TPS_HD int64_t wide_wg_lds_dwords(const WideArgs& a) { return WIDE_IMG_DW + (int64_t)a.wpg * wide_lds_dwords(a); }
+
+struct WideLds {
+    uint32_t* cnt;       // NT x WIDE_CS: the lanes' byte counters
+    uint32_t* st;        // 2 NT: a lane's running S_w and its count of self-overlapping occurrences in the window
+    uint32_t* seq;
+    uint16_t* val;
+    uint32_t* pm;        // one byte per position: group + 1
+    uint16_t* nx;        // NT x n_so: the walk's next admissible start per self-overlapping group
+    uint32_t* misc;
+    const uint32_t* tab;
+    const uint32_t* gm;
+    const uint8_t* pg;
+};
+TPS_DEV WideLds wide_carve(uint32_t* base, const uint32_t* img, const WideArgs& a) {
+    WideLds l;
+    uint32_t* p = base;
+    l.cnt = p;  p += WIDE_CNT_DW;
+    l.st = p;   p += 2 * NT;
+    l.seq = p;  p += a.seq_dw;
+    l.val = (uint16_t*)p;  p += a.seq_dw / 2 + 4;
+    l.pm = p;   p += a.tp_cap / 4 + 8;
+    l.nx = (uint16_t*)p;   p += wide_nx_dw(a);
+    l.misc = p;
+    l.tab = img;
+    l.gm = img + WIDE_TAB_DW;
+    l.pg = (const uint8_t*)(img + WIDE_TAB_DW + WIDE_GM_DW);
+    return l;
+}
+
+#ifdef TPS_EMU
+TPS_DEV u32x4 lds_load16(const uint32_t* p) { u32x4 v; v.x = p[0]; v.y = p[1]; v.z = p[2]; v.w = p[3]; return v; }
+TPS_DEV void g8_store(uint64_t base, uint32_t i, uint32_t v) { ((uint8_t*)(uintptr_t)base)[i] = (uint8_t)v; }
+#else
+TPS_DEV u32x4 lds_load16(const uint32_t* p) { return *(const u32x4*)p; }          // ds_read_b128 (p is 16-byte aligned)
+TPS_DEV void g8_store(uint64_t base, uint32_t i, uint32_t v) {
+    typedef __attribute__((address_space(1))) uint8_t* gp_t;
+    ((gp_t)(uintptr_t)base)[i] = (uint8_t)v;
+}
+#endif
+
+// group + 1 of the k-mer whose code is the low 2k bits of hi:lo, 0 if the list does not hold it
+TPS_DEV uint32_t wide_gid1(const WidePat& pat, const uint32_t* tab, uint32_t lo, uint32_t hi) {
+    lo &= pat.mask_lo;
+    hi &= pat.mask_hi;
+    const uint32_t f = lo + alignbit(hi, hi, pat.rot);
+    const uint32_t slot = (f * pat.mul) >> 24;
+    const u32x4 e = lds_load16(tab + 4 * slot);
+    return (e.x == lo && e.y == hi) ? e.z : 0u;          // (an unused slot: key 0, group + 1 = 0)
+}
+
+// pm[p] = group + 1 of the k-mer at start position p of the staged range, p < npos; lane `tid` takes chunks of 16 positions
+TPS_DEV void wide_lookup(const WideArgs& a, const WideLds& l, int delta, int npos, bool inv, int tid) {
+    const int nch = (npos + 15) >> 4;
+    for (int c = tid; c < nch; c += NT) {
+        const int p0 = c * 16, q0 = delta + p0, idx = q0 >> 4;
+        const uint32_t sh = (uint32_t)(q0 & 15) * 2u;
+        const uint32_t d0 = l.seq[idx], d1 = l.seq[idx + 1], d2 = l.seq[idx + 2], d3 = l.seq[idx + 3];
+        const uint32_t w0 = alignbit(d1, d0, sh), w1 = alignbit(d2, d1, sh), w2 = alignbit(d3, d2, sh);
+        uint32_t out[4];
+        TPS_UNROLL
+        for (int g4 = 0; g4 < 4; ++g4) {
+            uint32_t pk = 0;
+            TPS_UNROLL
+            for (int i = 0; i < 4; ++i) {
+                const int j = 4 * g4 + i;
+                const uint32_t lo = j ? alignbit(w1, w0, 2u * j) : w0;
+                const uint32_t hi = j ? alignbit(w2, w1, 2u * j) : w1;
+                uint32_t g1 = wide_gid1(a.pat, l.tab, lo, hi);
+                if (p0 + j >= npos) g1 = 0;
+                if (inv && g1 && invalid_at(l.val, q0 + j, a.pat.k)) g1 = 0;
+                pk |= g1 << (8 * i);
+            }
+            out[g4] = pk;
+        }
+        u32x4 o;
+        o.x = out[0]; o.y = out[1]; o.z = out[2]; o.w = out[3];
+        lds_store16(l.pm + 4 * c, o);
+    }
+}
+
+// stage s-indices [i0, i0 + n) of a tail and look every start position up; returns npos.  Called by the whole wave.
+TPS_DEV int wide_stage_lookup(const WideArgs& a, const WideLds& l, int64_t woff, int64_t L, bool reverse, int64_t t, int64_t i0, int n, bool has_inv) {
+    const Stage st = stage_plan(a.seq2, a.inv, woff, L, reverse, t, i0, n);
+    const int nqd = st.nq + 1;                             // (+ a quad of zeros: the last chunk reads three dwords ahead)
+    TPS_PHASE { if (tid == 0) l.misc[M_INVALID] = 0; }
+    TPS_SYNC();
+    TPS_PHASE { stage_thread(st, has_inv, l.seq, l.val, nqd, &l.misc[M_INVALID], tid); }
+    TPS_SYNC();
+    const bool inv = has_inv && uniform(l.misc[M_INVALID]) != 0;
+    const int npos = n - a.pat.k + 1 > 0 ? n - a.pat.k + 1 : 0;
+    TPS_PHASE { wide_lookup(a, l, st.delta, npos, inv, tid); }
+    TPS_SYNC();
+    return npos;
+}
+
+// step 1 of one side: per-pattern counts of the head -> c_out[P] (or nullptr), the first maximum as count << 6 | 63 - pattern
+TPS_DEV uint32_t wide_trc_side(const WideArgs& a, const WideLds& l, int64_t woff, int64_t L, bool reverse, int n1, bool has_inv, int32_t* c_out, int side) {
+    const WidePat& pat = a.pat;
+    TPS_PHASE { l.cnt[tid] = 0; }
+    const int npos = wide_stage_lookup(a, l, woff, L, reverse, 0, 0, n1, has_inv);
+    TPS_PHASE {
+        const int nch = (npos + 15) >> 4;
+        for (int c = tid; c < nch; c += NT) {
+            const u32x4 v = lds_load16(l.pm + 4 * c);
+            const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+            TPS_UNROLL
+            for (int j = 0; j < 16; ++j) {
+                const uint32_t g1 = (w[j >> 2] >> (8 * (j & 3))) & 255u;
+                if (g1 > (uint32_t)pat.n_so) lds_add(&l.cnt[g1 - 1], 1u);     // a k-mer without a period: its occurrences cannot overlap
+            }
+        }
+    }
+    TPS_SYNC();
+    if (pat.n_so) {
+        // a k-mer with a period: leftmost non-overlapping, one lane per such group
+        TPS_PHASE {
+            if (tid < pat.n_so) {
+                const uint8_t* pmb = (const uint8_t*)l.pm;
+                uint32_t cnt = 0;
+                int next = 0;
+                for (int p = 0; p < npos; ++p)
+                    if (pmb[p] == (uint8_t)(tid + 1) && p >= next) { ++cnt; next = p + pat.k; }
+                l.cnt[tid] = cnt;
+            }
+        }
+        TPS_SYNC();
+    }
+    TPS_PHASE {
+        if (tid < pat.P) {
+            const uint32_t c = l.cnt[l.pg[tid]];
+            if (c_out) g32_store((uint64_t)(uintptr_t)c_out, (uint32_t)tid, c);
+            lds_max_i32((int32_t*)&l.misc[M_BEST + side], (int32_t)((c << 6) | (uint32_t)(63 - tid)));
+        }
+    }
+    TPS_SYNC();
+    return uniform(l.misc[M_BEST + side]);
+}
+
+// an occurrence (g1 = group + 1 of its position, 0 = none) enters / leaves a lane's window: the group's byte counter, the running
+// S_w = sum of max(1, count) over the list patterns, and the number of self-overlapping occurrences in the window (walked, not slid)
+// (S and nso change by VALUES computed on both paths: written as `if (...) ++nso; else S += ...` the compiler stores through a selected
+// pointer and both live in scratch)
+TPS_DEV void wide_enter(const WideLds& l, const WidePat& pat, uint8_t* cb, uint32_t g1, uint32_t& S, uint32_t& nso) {
+    const bool so = g1 != 0 && g1 <= (uint32_t)pat.n_so;
+    uint32_t ds = 0;
+    if (g1 != 0 && !so) {
+        const uint32_t c = cb[g1 - 1];
+        cb[g1 - 1] = (uint8_t)(c + 1);
+        ds = c >= 1 ? l.gm[g1 - 1] : 0u;
+    }
+    S += ds;
+    nso += so ? 1u : 0u;
+}
+TPS_DEV void wide_leave(const WideLds& l, const WidePat& pat, uint8_t* cb, uint32_t g1, uint32_t& S, uint32_t& nso) {
+    const bool so = g1 != 0 && g1 <= (uint32_t)pat.n_so;
+    uint32_t ds = 0;
+    if (g1 != 0 && !so) {
+        const uint32_t c = cb[g1 - 1];
+        cb[g1 - 1] = (uint8_t)(c - 1);
+        ds = c >= 2 ? l.gm[g1 - 1] : 0u;
+    }
+    S -= ds;
+    nso -= so ? 1u : 0u;
+}
+
+// one step of the window phase: lane `tid` brings its counters to window wl = tid * m + j of the tile and stores that window's S_w
+TPS_DEV void wide_step(const WideArgs& a, const WideLds& l, int j, int m, int nw_tile, int lw1, uint64_t sums_g, int tid) {
+    const int wl = tid * m + j;
+    if (wl >= nw_tile) return;
+    const WidePat& pat = a.pat;
+    const int s = a.prm.slide;
+    uint8_t* cb = (uint8_t*)(l.cnt + tid * WIDE_CS);
+    const uint8_t* pmb = (const uint8_t*)l.pm;
+    uint32_t S, nso;
+    const int base = wl * s;
+    if (j == 0) {
+        for (int i = 0; i < WIDE_CS; ++i) l.cnt[tid * WIDE_CS + i] = 0;
+        S = (uint32_t)pat.P;                               // every pattern absent: each counts as 1
+        nso = 0;
+        for (int p = base; p < base + lw1; ++p) wide_enter(l, pat, cb, pmb[p], S, nso);
+    } else {
+        S = l.st[tid];
+        nso = l.st[NT + tid];
+        const int prev = base - s;
+        const int gone = prev + (s < lw1 ? s : lw1);
+        for (int p = prev; p < gone; ++p) wide_leave(l, pat, cb, pmb[p], S, nso);
+        for (int p = (base > prev + lw1 ? base : prev + lw1); p < base + lw1; ++p) wide_enter(l, pat, cb, pmb[p], S, nso);
+    }
+    uint32_t extra = 0;
+    if (pat.n_so) {
+        uint16_t* nx = l.nx + tid * pat.n_so;
+        for (int i = 0; i < pat.n_so; ++i) { cb[i] = 0; nx[i] = 0; }
+        if (nso) {
+            for (int p = base; p < base + lw1; ++p) {
+                const uint32_t g1 = pmb[p];
+                if (g1 && g1 <= (uint32_t)pat.n_so && p >= (int)nx[g1 - 1]) {
+                    const uint32_t c = cb[g1 - 1];
+                    cb[g1 - 1] = (uint8_t)(c + 1);
+                    nx[g1 - 1] = (uint16_t)(p + pat.k);
+                    if (c >= 1) extra += l.gm[g1 - 1];
+                }
+            }
+        }
+    }
+    l.st[tid] = S;
+    l.st[NT + tid] = nso;
+    g32_store(sums_g, (uint32_t)wl, S + extra);
+}
+
+// the raw rows of the 64 windows the lanes have just finished: lane (window, pattern) stores max(1, count)
+TPS_DEV void wide_rows(const WideArgs& a, const WideLds& l, int j, int m, int nw_tile, uint64_t raw_g, int tid) {
+    const int P = a.pat.P;
+    const int wpi = NT / P;                                // windows per store instruction
+    const int sub = tid / P, p = tid - sub * P;
+    if (sub >= wpi) return;
+    const uint32_t g = l.pg[p];
+    for (int lw = sub; lw < NT && lw * m + j < nw_tile; lw += wpi) {
+        const uint32_t c = ((const uint8_t*)(l.cnt + lw * WIDE_CS))[g];
+        g8_store(raw_g, (uint32_t)((lw * m + j) * P + p), c ? c : 1u);
+    }
+}
+
+// ------------------------------------------------------------------ the per-read program
+// `lds_base` is this wave's LDS slice, `img` the workgroup's copy of WideArgs::img.  Every lane of the wave executes this.
+TPS_DEV void wide_read(const WideArgs& a, int64_t r, uint32_t* lds_base, const uint32_t* img) {
+    const WideLds l = wide_carve(lds_base, img, a);
+    const WidePat& pat = a.pat;
+    const tps_params& prm = a.prm;
+    const int64_t woff = a.desc[r].word_off;
+    const int64_t L = a.desc[r].len;
+    const bool has_inv = (a.desc[r].flags & TPS_RD_HAS_INVALID) != 0;
+    const bool step1 = (prm.flags & TPS_F_STEP1) != 0;
+
+    TPS_PHASE { for (int i = tid; i < MISC_DW; i += NT) l.misc[i] = 0; }
+    TPS_SYNC();
+
+    int tail = 0, pass = 1;
+    tps_read_result res;
+    res.best_start = res.best_end = 0;
+    res.best_start_idx = res.best_end_idx = 0;
+    res.n_win = 0; res.bkp = -1; res.gain = 0.0;
+    res.flags = 0; res.reserved = 0;
+
+    if (step1) {
+        const int n1 = (int)(L < prm.no_bp ? L : prm.no_bp);
+        const uint32_t ks = wide_trc_side(a, l, woff, L, false, n1, has_inv, a.c_start ? a.c_start + r * pat.P : nullptr, 0);
+        const uint32_t ke = wide_trc_side(a, l, woff, L, true, n1, has_inv, a.c_end ? a.c_end + r * pat.P : nullptr, 1);
+        res.best_start = (int32_t)(ks >> 6); res.best_start_idx = 63 - (int32_t)(ks & 63u);
+        res.best_end = (int32_t)(ke >> 6); res.best_end_idx = 63 - (int32_t)(ke & 63u);
+        // forward only if strictly larger (allsteps.py:193); strict cutoff and length tests
+        tail = res.best_start > res.best_end ? 0 : 1;
+        const int best = tail ? res.best_end : res.best_start;
+        pass = (L > prm.min_len && best > prm.min_count) ? 1 : 0;
+    } else if (a.tails_in) {
+        const uint8_t tv = a.tails_in[r];
+        tail = tv & 1;
+        pass = (tv & 2) ? 0 : 1;                   // bit 1 set = skip this read
+    }
+    res.tail = tail;
+    res.pass = pass;
+
+    int n_win = 0;
+    const int64_t out_base = a.win_off ? a.win_off[r] : 0;
+    if (pass && (prm.flags & TPS_F_WINDOWS)) {
+        const int64_t m_ = L < prm.maxlen ? L : prm.maxlen;
+        const int64_t n_s = m_ - prm.trimfirst;
+        if (n_s >= prm.window) n_win = (int)((n_s - prm.window) / prm.slide) + 1;
+        const int lw1 = prm.window - pat.k > 0 ? prm.window - pat.k : 0;      // start positions of a window of W - 1 characters
+        for (int w0 = 0; w0 < n_win; w0 += a.tw) {
+            const int nw_tile = (n_win - w0) < a.tw ? (n_win - w0) : a.tw;
+            const int m = (nw_tile + NT - 1) / NT;           // consecutive windows per lane
+            const int64_t i0 = (int64_t)w0 * prm.slide;
+            const int n_stage = (nw_tile - 1) * prm.slide + prm.window - 1;   // <= tp_cap (host) and <= n_s - i0 (the windows exist)
+            wide_stage_lookup(a, l, woff, L, tail == 1, prm.trimfirst, i0, n_stage, has_inv);
+            const uint64_t sums_g = (uint64_t)(uintptr_t)(a.sums + out_base + w0);
+            const uint64_t raw_g = a.raw ? (uint64_t)(uintptr_t)(a.raw + (out_base + w0) * pat.P) : 0ull;
+            for (int j = 0; j < m; ++j) {
+                TPS_PHASE { wide_step(a, l, j, m, nw_tile, lw1, sums_g, tid); }
+                TPS_SYNC();
+                if (raw_g) {
+                    TPS_PHASE { wide_rows(a, l, j, m, nw_tile, raw_g, tid); }
+                    TPS_SYNC();
+                }
+            }
+        }
+    }
+    res.n_win = n_win;
+
+    if (n_win > 0 && (prm.flags & TPS_F_BINSEG) && binseg_admissible(n_win, prm.jump, prm.min_size)) {
+        int bkp;
+        double gain;
+        bool tie = false;
+#ifndef TPS_EMU
+        // same wave, same CU: workgroup scope orders this wave's S_w stores before its own loads
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+#endif
+        uint32_t* xs = l.cnt;                              // (the counters are done: XS_DW + MISC_DW + NT dwords fit their region)
+        uint32_t* bmisc = xs + ((XS_DW + 1) / 2) * 2;
+        uint32_t* bs = bmisc + MISC_DW;
+        binseg_wg((const int32_t*)(a.sums + out_base), n_win, prm.jump, prm.min_size, pat.P, bs, bmisc, xs, bkp, gain, tie);
+        res.bkp = bkp;
+        res.gain = gain;
+        res.flags = tie ? TPS_RES_TIE : 0u;
+    }
+    TPS_PHASE { if (tid == 0) a.results[r] = res; }
+}
+static_assert(((XS_DW + 1) / 2) * 2 + MISC_DW + NT <= WIDE_CNT_DW, "the change point's scratch must fit the counter region");
+
+}  // namespace tps

@@ -102,8 +102,13 @@ def pattern_matches(records, telopattern, telophrase, minSeqLength, engine=None)
     from . import allsteps, hiplib
     pattern_all = pattern_scramble_telo(telopattern, cut_length=telophrase)
     follow = int(len(telopattern) - telophrase)
+    table = allsteps.patterns_to_search(telopattern, telophrase)
+    if len(pattern_all) > 15 or hiplib.needs_wide(table):
+        raise hiplib.TopsicleHipError(f"the k-mer / follower heat map takes up to 15 k-mers of up to {hiplib.MAX_K} letters (tps_batch_kmer_followers: "
+                                      f"n_fwd <= 15); {telopattern} at k = {telophrase} has {len(pattern_all)} -- the telomere scan itself takes motifs of up to "
+                                      f"{hiplib.WIDE_MAX_K} letters")
     eng = engine or allsteps.get_engine()
-    eng.set_patterns(allsteps.patterns_to_search(telopattern, telophrase))
+    eng.set_patterns(table)
     recs = [r for r in records if len(r.seq) > minSeqLength]
     if not recs:
         return pattern_all, [], None

@@ -117,7 +117,7 @@ def measure(bases, offsets, motif: str, k: int, slide: int, device: int = 0, con
             held = list(seqio.read_batches_packed(fq, held_pool)) if held_pool is not None else []
             assert len(held) < 6
             if held:
-                engines[0].set_patterns(pats)
+                hiplib.set_table(engines[0], pats)
                 times = []
                 for _ in range(repeats + 1):
                     t0 = time.perf_counter()

@@ -17,10 +17,11 @@ LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
 # flags (TPS_F_*)
 F_STEP1, F_WINDOWS, F_BINSEG, F_STORE_SUMS, F_STORE_RAW, F_TAILS_IN = 1, 2, 4, 8, 16, 32
 MAX_K, MAX_PATTERNS, MAX_SLOTS = 15, 31, 16
+WIDE_MAX_K, WIDE_MAX_PATTERNS = 32, 64      # tps_set_patterns_wide (TPS_WIDE_MAX_K, TPS_WIDE_MAX_PATTERNS)
 
 EXPORTS = [
     "tps_abi_version", "tps_device_count", "tps_ctx_create", "tps_ctx_destroy", "tps_last_error",
-    "tps_set_patterns", "tps_batch_upload", "tps_batch_upload_packed", "tps_batch_upload_nib4", "tps_batch_share", "tps_host_alloc", "tps_host_free",
+    "tps_set_patterns", "tps_set_patterns_wide", "tps_batch_upload", "tps_batch_upload_packed", "tps_batch_upload_nib4", "tps_batch_share", "tps_host_alloc", "tps_host_free",
     "tps_batch_download_packed", "tps_batch_kmer_followers", "tps_batch_set_tails", "tps_batch_scan", "tps_sync",
     "tps_batch_results", "tps_batch_window_offsets", "tps_batch_window_sums", "tps_batch_window_raw",
     "tps_batch_raw_to_fd", "tps_batch_trc_counts", "tps_trc_counts", "tps_window_counts", "tps_binseg_l2", "tps_binseg_l2_ties", "tps_batch_read_sums", "tps_window_count",
@@ -84,6 +85,7 @@ def load_library(path: str | None = None) -> C.CDLL:
         "tps_ctx_destroy": (C.c_int, [vp]),
         "tps_last_error": (C.c_char_p, []),
         "tps_set_patterns": (C.c_int, [vp, C.c_char_p, i32, i32]),
+        "tps_set_patterns_wide": (C.c_int, [vp, C.c_char_p, i32, i32]),
         "tps_batch_upload": (C.c_int, [vp, i32, vp, vp, i64]),
         "tps_batch_upload_packed": (C.c_int, [vp, i32, vp, vp, vp, i64, i64]),
         "tps_batch_upload_nib4": (C.c_int, [vp, i32, vp, i64, vp, vp, i64, i64]),
@@ -127,6 +129,20 @@ def load_library(path: str | None = None) -> C.CDLL:
 
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def needs_wide(patterns) -> bool:
+    """The table is beyond what set_patterns takes (k > MAX_K letters or more than MAX_PATTERNS patterns): it goes through
+    set_patterns_wide and the wide kernel.  Every other table keeps the narrow call."""
+    return bool(patterns) and (len(patterns[0]) > MAX_K or len(patterns) > MAX_PATTERNS)
+
+
+def set_table(engine, patterns):
+    """set_patterns for a narrow table, set_patterns_wide for one that needs it: what every scan site of the package calls."""
+    if needs_wide(patterns):
+        engine.set_patterns_wide(patterns)
+    else:
+        engine.set_patterns(patterns)
 
 
 def debug_options_from_env() -> dict:
@@ -307,6 +323,18 @@ class HipScanner:
             raise TopsicleHipError("all patterns of one table must have the same length")
         blob = "".join(patterns).encode("ascii")
         self._check(self.lib.tps_set_patterns(self._h, blob, len(patterns), k))
+        self.patterns = list(patterns)
+
+    def set_patterns_wide(self, patterns: list[str]):
+        """Up to WIDE_MAX_PATTERNS patterns of up to WIDE_MAX_K letters (tps_set_patterns_wide): scans then run the wide kernel,
+        everything downstream of the scan is unchanged.  Takes narrow tables too; kmer_followers refuses a wide table."""
+        if not patterns:
+            raise TopsicleHipError("empty pattern list")
+        k = len(patterns[0])
+        if any(len(p) != k for p in patterns):
+            raise TopsicleHipError("all patterns of one table must have the same length")
+        blob = "".join(patterns).encode("ascii", "replace")
+        self._check(self.lib.tps_set_patterns_wide(self._h, blob, len(patterns), k))
         self.patterns = list(patterns)
 
     # -- resident batches

@@ -324,6 +324,10 @@ def analysis_run(args, engines=None, engine_factory=None, wait_plots=True):
         tprint(f"{k}: {v}")
     print("---------------------")
     tprint("Starting Topsicle analysis")
+    if len(args.pattern) > hiplib.WIDE_MAX_K:
+        # (before any file is read or written: k-mers of up to 32 letters and 64 patterns per table is what the scan kernels hold)
+        tprint(f"--pattern has {len(args.pattern)} letters: motifs of up to {hiplib.WIDE_MAX_K} letters are supported")
+        sys.exit(2)
     os.makedirs(args.outputDir, exist_ok=True)
 
     if args.threads is not None:
