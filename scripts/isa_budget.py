@@ -2,13 +2,14 @@
 """Static per-phase instruction budget of one scan kernel (no GPU needed).
 
 Compiles the kernel's group with -DTPS_ISA_MARKS (the clock-stamp boundaries and the phases of the sums tiles become
-comments in the ISA, nothing else: csrc/tps_device.h, TPS_ISA_MARK) and counts the instructions between consecutive marks
+comments in the ISA, nothing else: csrc/tps_wave.h, TPS_ISA_MARK) and counts the instructions between consecutive marks
 in the kernel's text, in layout order: VALU (v_*), LDS (ds_*), VMEM (global_*, buffer_*), SALU (s_*, without s_waitcnt,
 s_nop, branches and barriers).  Static counts: a loop body counts once, a branch's both sides count.
 
   usage: scripts/isa_budget.py [--kernel tps_scan_kernel_s6p] [--group 1] [--src DIR] [--csv OUT]
 
---src: a directory with the csrc headers to compile instead of the tree's (e.g. an older revision, for a before/after).
+--src: the csrc directory of another copy of the tree to compile instead of this one's (e.g. an older revision, for a
+before/after; scripts/isa_diff.py shows how to take one from git).
 Rows: the kernel's regions between clock stamps (step 1 = stamps 1..4, the change point = 9..10), and per tile
 instantiation (S, RPT, ROTZ, PAIR) its phases; `home` marks the instantiation of the default geometry (slide 6, r = 0,
 q a multiple of 8, pair table), the one config 2 runs five times per read.  The strided candidate pass is a loop (config 2:

@@ -1,8 +1,8 @@
 // TEST INFRASTRUCTURE ONLY -- sequential host emulation of the HIP kernel source.
 //
 // Compiles topsicle_amd/csrc/tps_device.h with -DTPS_EMU: the very same per-read program the
-// GPU runs, with TPS_PHASE looping over the 256 thread ids and the few gfx950 intrinsics
-// replaced by portable C.  It lets the kernel LOGIC be checked against the oracle in a
+// GPU runs, with TPS_PHASE looping over the 64 lane ids of a wave, a lane's registers that outlive a
+// phase kept per lane, and the gfx950 intrinsics and wave operations replaced by portable C (csrc/tps_wave.h).  It lets the kernel LOGIC be checked against the oracle in a
 // container without a GPU (tests/test_emulation.py).  It is never linked into the product
 // library and the product never loads it.
 #define TPS_EMU 1

@@ -23,56 +23,17 @@
 //   * tile_fused_s: the round-1/2 lane-strided tile, kept for tiles with non-ACGT letters and as recount fallback.
 //   * generic: any slide, up to 31 patterns, k up to 15; per-block masks in LDS, q+1 reads per window.
 //
-// The file is written against a tiny portability layer so that the SAME source also builds
-// as a sequential host emulation (tests/emu, -DTPS_EMU) for logic tests without a GPU.
+// The file is written against the platform layer of tps_wave.h (phases, per-lane state, wave operations), so that the SAME
+// statements also build as a sequential host emulation (tests/emu, -DTPS_EMU) for logic tests without a GPU: nothing below
+// that line distinguishes the two builds except the sites DESIGN.md lists ("One kernel text").
 // The emulation is test infrastructure only; the product library contains device code only.
 #pragma once
 #include <stdint.h>
 #include "../../include/topsicle_hip.h"
-
-#ifdef TPS_EMU
-#define TPS_DEV static inline
-#define TPS_HD static inline
-#define TPS_PHASE for (int tid = 0; tid < tps::NT; ++tid)
-#define TPS_SYNC() ((void)0)
-#define TPS_UNROLL
-#define TPS_NOVEC
-#define TPS_PIN_S(x) ((void)0)
-#define TPS_PIN_V(x) ((void)0)
-#else
-#define TPS_DEV __device__ __forceinline__
-#define TPS_HD __host__ __device__ inline
-// Every phase gets a FRESH, opaque copy of the lane id (an empty asm the optimiser cannot see through).
-// Without it LLVM hoists all lane-dependent address arithmetic of every phase out of the tile loop
-// and keeps it live across the whole kernel: measured 99 -> 42 VGPRs on the fused tile alone.
-__device__ __forceinline__ int tps_fresh_lane() {
-    int t = (int)(threadIdx.x & 63u);
-    asm volatile("" : "+v"(t));
-    return t;
-}
-#define TPS_PHASE for (int tid = tps_fresh_lane(), once_ = 1; once_; once_ = 0)
-// wave-level synchronisation: a wave's LDS operations execute in issue order, so making earlier LDS
-// writes visible to the other lanes of the SAME wave only needs the compiler not to reorder / cache
-// across this point (no s_barrier, no cross-wave skew)
-#define TPS_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier(); } while (0)
-#define TPS_UNROLL _Pragma("unroll")
-// short runtime-bounded loops: keep them as plain scalar loops (the vectoriser turns a 1-2 iteration loop
-// into prologue / vector body / epilogue control flow that costs more than the loop)
-#define TPS_NOVEC _Pragma("clang loop vectorize(disable) interleave(disable) unroll(disable)")
-// (__builtin_amdgcn_sched_barrier(0) was used here to bound register pressure; with ROCm 7.2 it made the
-// self-overlap + invalid-base instance of the fused tile nondeterministic on gfx950, and it is no longer
-// needed once every phase launders its lane id)
-// zero-cost "redefinition" of a wave-uniform value: it stays in an SGPR (or a VGPR lane) instead of being re-loaded from the
-// kernel-argument segment inside a loop (an s_load + s_waitcnt that also drains the LDS queue)
-#define TPS_PIN_S(x) asm volatile("" : "+s"(x))
-// the same for a per-lane value: it is computed HERE (the compiler otherwise sinks pure arithmetic past the wave barrier
-// of the next phase and keeps all its inputs alive across it)
-#define TPS_PIN_V(x) asm volatile("" : "+v"(x))
-#endif
+#include "tps_wave.h"
 
 namespace tps {
 
-constexpr int NT = 64;                            // lanes that cooperate on one read: one wave
 constexpr int WPG = 4;                            // independent waves (reads) per workgroup: the default, and the fixed size of the small kernels
 constexpr int WPG_MAX = 8;                        // the scan kernels take 4 .. 8 waves per workgroup (ScanArgs::wpg): a big table (k >= 6) is shared by more waves
 constexpr uint32_t FLAG_CONFLICT = 0x80000000u;   // generic path: bit 31 of a block mask
@@ -83,217 +44,8 @@ constexpr int COOP_MAX = 24;                      // fused tiles: up to this man
 
 typedef unsigned __int128 u128;
 
-// ------------------------------------------------------------------ portability layer
-#ifdef TPS_EMU
-TPS_DEV uint32_t alignbit(uint32_t hi, uint32_t lo, uint32_t sh) {
-    return (uint32_t)(((((uint64_t)hi) << 32) | lo) >> (sh & 31));
-}
-TPS_DEV uint32_t udot4(uint32_t a, uint32_t b) {
-    uint32_t s = 0;
-    for (int i = 0; i < 4; ++i) s += ((a >> (8 * i)) & 255u) * ((b >> (8 * i)) & 255u);
-    return s;
-}
-TPS_DEV uint32_t perm(uint32_t s0, uint32_t s1, uint32_t sel) {
-    uint32_t out = 0;
-    for (int i = 0; i < 4; ++i) {
-        uint32_t c = (sel >> (8 * i)) & 255u, byte;
-        if (c < 4) byte = (s1 >> (8 * c)) & 255u;
-        else if (c < 8) byte = (s0 >> (8 * (c - 4))) & 255u;
-        else byte = (c >= 13) ? 255u : 0u;
-        out |= byte << (8 * i);
-    }
-    return out;
-}
-TPS_DEV int popc(uint32_t x) { return __builtin_popcount(x); }
-TPS_DEV int ffs0(uint32_t x) { return __builtin_ctz(x); }
-TPS_DEV uint32_t uniform(uint32_t x) { return x; }
-TPS_DEV void lds_add(uint32_t* p, uint32_t v) { *p += v; }
-TPS_DEV void lds_or(uint32_t* p, uint32_t v) { *p |= v; }
-TPS_DEV uint32_t lds_add_ret(uint32_t* p, uint32_t v) { uint32_t o = *p; *p += v; return o; }
-TPS_DEV void lds_max_u64(uint64_t* p, uint64_t v) { if (v > *p) *p = v; }
-TPS_DEV void lds_max_i32(int32_t* p, int32_t v) { if (v > *p) *p = v; }
-struct u32x4 { uint32_t x, y, z, w; };
-struct u32x2 { uint32_t x, y; };
-TPS_DEV u32x4 load16(const uint8_t* p) { return *(const u32x4*)p; }
-TPS_DEV u32x2 load8(const uint8_t* p) { return *(const u32x2*)p; }
-TPS_DEV uint32_t bitrev32(uint32_t x) {
-    x = ((x >> 1) & 0x55555555u) | ((x & 0x55555555u) << 1);
-    x = ((x >> 2) & 0x33333333u) | ((x & 0x33333333u) << 2);
-    x = ((x >> 4) & 0x0F0F0F0Fu) | ((x & 0x0F0F0F0Fu) << 4);
-    return __builtin_bswap32(x);
-}
-#else
-TPS_DEV uint32_t alignbit(uint32_t hi, uint32_t lo, uint32_t sh) { return __builtin_amdgcn_alignbit(hi, lo, sh); }
-TPS_DEV uint32_t udot4(uint32_t a, uint32_t b) { return __builtin_amdgcn_udot4(a, b, 0u, false); }
-TPS_DEV uint32_t perm(uint32_t s0, uint32_t s1, uint32_t sel) { return __builtin_amdgcn_perm(s0, s1, sel); }
-TPS_DEV int popc(uint32_t x) { return __builtin_popcount(x); }
-TPS_DEV int ffs0(uint32_t x) { return __builtin_ctz(x); }
-// a value every lane of the wave agrees on (e.g. read from LDS): tell the compiler it is scalar
-TPS_DEV uint32_t uniform(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
-TPS_DEV void lds_add(uint32_t* p, uint32_t v) { atomicAdd(p, v); }
-TPS_DEV void lds_or(uint32_t* p, uint32_t v) { atomicOr(p, v); }
-TPS_DEV uint32_t lds_add_ret(uint32_t* p, uint32_t v) { return atomicAdd(p, v); }
-TPS_DEV void lds_max_u64(uint64_t* p, uint64_t v) { atomicMax((unsigned long long*)p, (unsigned long long)v); }
-TPS_DEV void lds_max_i32(int32_t* p, int32_t v) { atomicMax(p, v); }
-typedef uint4 u32x4;
-typedef uint2 u32x2;
-// 16-byte load that is KNOWN to hit global memory: the address was rebuilt from an integer (aligned
-// down), which makes the compiler fall back to FLAT loads -- those also count on lgkmcnt and would
-// stall every LDS wait behind the prefetch.  An explicit global address space keeps them on vmcnt.
-TPS_DEV u32x4 load16(const uint8_t* p) {
-    typedef unsigned int v4u __attribute__((ext_vector_type(4)));
-    typedef const __attribute__((address_space(1))) v4u* gptr_t;
-    const v4u t = *(gptr_t)(uintptr_t)p;
-    u32x4 r;
-    r.x = t.x; r.y = t.y; r.z = t.z; r.w = t.w;
-    return r;
-}
-TPS_DEV u32x2 load8(const uint8_t* p) {
-    typedef unsigned int v2u __attribute__((ext_vector_type(2)));
-    typedef const __attribute__((address_space(1))) v2u* gptr_t;
-    const v2u t = *(gptr_t)(uintptr_t)p;
-    u32x2 r;
-    r.x = t.x; r.y = t.y;
-    return r;
-}
-TPS_DEV uint32_t bitrev32(uint32_t x) { return __builtin_bitreverse32(x); }      // v_bfrev_b32
-#endif
-
-// table entry at byte offset `off` (already masked to the table size).  The table starts at the
-// workgroup's LDS offset 0, i.e. it is aligned to any power of two, so base | off == base + off and the
-// mask + base fold into one v_and_or_b32 -- where the base is a known 0 (every kernel's first table) into one v_and; with mask and
-// base both in SGPRs (the single table of the pair-table kernels: 8 lookups per tile at odd r, step 1's) it comes out as v_and +
-// v_or, a VOP3 instruction reading one scalar register only on gfx9.  The base pinned into a VGPR gives the one instruction, 6 VALU
-// per tile less -- and measures nothing at config 2 (55.0 / 54.8 against 54.8 / 55.0 us), +1 % on the kernels whose base is 0: not kept.
-// Nor does a compile-time table address help (tried: a fixed-size pair region, so that the single table starts at LDS byte 4096): the
-// base of the dynamic LDS array is resolved after instruction selection -- `| base` of the array's own start is folded late, any
-// other constant offset stays an instruction, and written as `+` even the start costs a `v_add_u32 0` per lookup.
-#ifdef TPS_EMU
-TPS_DEV uint32_t lut_at(const uint32_t* lut, uint32_t v4, uint32_t amask) { return *(const uint32_t*)((const char*)lut + (v4 & amask)); }
-#define lut_at_tile lut_at
-#else
-TPS_DEV uint32_t lut_at(const uint32_t* lut, uint32_t v4, uint32_t amask) {
-    typedef const __attribute__((address_space(3))) uint32_t* lptr_t;
-    const uint32_t base = (uint32_t)(uintptr_t)(lptr_t)lut;
-    return *(lptr_t)(uintptr_t)((v4 & amask) | base);
-}
-#ifdef TPS_DIAG_NOCONF
-/* diagnostic builds only (WRONG window sums, same control flow): the default tile's table gathers with every lane on its own
-   bank -- what do the gathers' bank conflicts cost? */
-TPS_DEV uint32_t lut_at_tile(const uint32_t* lut, uint32_t v4, uint32_t amask) {
-    typedef const __attribute__((address_space(3))) uint32_t* lptr_t;
-    const uint32_t base = (uint32_t)(uintptr_t)(lptr_t)lut;
-    return *(lptr_t)(uintptr_t)((((v4 & amask) >> 30) | ((threadIdx.x & 63u) << 2)) | base);
-}
-#else
-#define lut_at_tile lut_at
-#endif
-#endif
-
-#ifndef TPS_WIDE16_MODE
-#define TPS_WIDE16_MODE 1         // (0: A/B builds without the pin of lut16_at_wide)
-#endif
-// 16-bit table entry (LUT_M16 tables: one pattern mask per k-mer code) at byte offset `off2` (already masked to the table size)
-#ifdef TPS_EMU
-TPS_DEV uint32_t lut16_at(const uint32_t* lut, uint32_t v2, uint32_t amask1) { return *(const uint16_t*)((const char*)lut + (v2 & amask1)); }
-#define lut16_at_wide lut16_at
-#else
-TPS_DEV uint32_t lut16_at(const uint32_t* lut, uint32_t v2, uint32_t amask1) {
-    typedef const __attribute__((address_space(3))) uint16_t* lptr16_t;
-    const uint32_t base = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) uint32_t*)lut;
-    return *(lptr16_t)(uintptr_t)((v2 & amask1) | base);      // ds_read_u16: zero-extended
-}
-// ... for the sums tiles of the self-overlap tables (tile_lc_s<.., CD>), opaque to the optimiser: it otherwise narrows everything
-// computed from these values to 16-bit arithmetic and legalises that with one `v_and_b32 0xffff` per entry -- 6 of a block's 57 VALU
-// instructions (k = 5 sums 107.4 -> 105.7 us, k = 6 142.5 -> 140.6; the raw-row tiles' look-ups are better off without:
-// `_s6sorh` 211.6 -> 219.2 us with it, the waits move up to the loads)
-TPS_DEV uint32_t lut16_at_wide(const uint32_t* lut, uint32_t v2, uint32_t amask1) {
-    uint32_t h = lut16_at(lut, v2, amask1);
-#if TPS_WIDE16_MODE == 1
-    asm("" : "+v"(h));
-#endif
-    return h;
-}
-#endif
-
-// 16-bit candidate sums kept off-chip: explicit global address space (a generic pointer would become FLAT
-// instructions, which also count on the LDS counter)
-#ifdef TPS_EMU
-TPS_DEV void g16_store(uint64_t base, uint32_t i, uint32_t v) { ((uint16_t*)(uintptr_t)base)[i] = (uint16_t)v; }
-TPS_DEV uint32_t g16_load(uint64_t base, uint32_t i) { return ((const uint16_t*)(uintptr_t)base)[i]; }
-#else
-TPS_DEV void g16_store(uint64_t base, uint32_t i, uint32_t v) {
-    typedef __attribute__((address_space(1))) uint16_t* gp_t;
-    ((gp_t)(uintptr_t)base)[i] = (uint16_t)v;
-}
-TPS_DEV uint32_t g16_load(uint64_t base, uint32_t i) {
-    typedef const __attribute__((address_space(1))) uint16_t* gp_t;
-    return ((gp_t)(uintptr_t)base)[i];
-}
-#endif
-
-#ifdef TPS_EMU
-TPS_DEV void g32_store(uint64_t base, uint32_t i, uint32_t v) { ((uint32_t*)(uintptr_t)base)[i] = v; }
-TPS_DEV uint32_t g32_load(uint64_t base, uint32_t i) { return ((const uint32_t*)(uintptr_t)base)[i]; }
-TPS_DEV uint32_t g32_load_at(uint64_t base, uint32_t byte_off) { return *(const uint32_t*)(uintptr_t)(base + byte_off); }
-#else
-// ... at an unsigned 32-bit BYTE offset from a wave-uniform base: one scalar-base load, no 64-bit address arithmetic per lane
-TPS_DEV uint32_t g32_load_at(uint64_t base, uint32_t byte_off) {
-    typedef const __attribute__((address_space(1))) uint8_t* gb_t;
-    typedef const __attribute__((address_space(1))) uint32_t* gp_t;
-    return *(gp_t)((gb_t)(uintptr_t)base + byte_off);
-}
-TPS_DEV void g32_store(uint64_t base, uint32_t i, uint32_t v) {
-    typedef __attribute__((address_space(1))) uint32_t* gp_t;
-    ((gp_t)(uintptr_t)base)[i] = v;
-}
-TPS_DEV uint32_t g32_load(uint64_t base, uint32_t i) {
-    typedef const __attribute__((address_space(1))) uint32_t* gp_t;
-    return ((gp_t)(uintptr_t)base)[i];
-}
-#endif
-
-// high half of a 32 x 32-bit product (v_mul_hi_u32, full rate) and the sum of the four bytes of a word (v_sad_u8)
-TPS_DEV uint32_t mulhi32(uint32_t x, uint32_t y) { return (uint32_t)(((uint64_t)x * (uint64_t)y) >> 32); }
-#ifdef TPS_EMU
-TPS_DEV uint32_t mul24(uint32_t x, uint32_t y) { return (x & 0xFFFFFFu) * (y & 0xFFFFFFu); }
-#else
-TPS_DEV uint32_t mul24(uint32_t x, uint32_t y) { return (x & 0xFFFFFFu) * (y & 0xFFFFFFu); }      // (the masks let the compiler pick v_mul_u32_u24)
-#endif
-#ifdef TPS_EMU
-TPS_DEV uint32_t add_bytes(uint32_t v, uint32_t acc) { return acc + (v & 255u) + ((v >> 8) & 255u) + ((v >> 16) & 255u) + (v >> 24); }
-#else
-TPS_DEV uint32_t add_bytes(uint32_t v, uint32_t acc) { return __builtin_amdgcn_sad_u8(v, 0u, acc); }
-#endif
-
 constexpr int cgcd(int a, int b) { return b == 0 ? a : cgcd(b, a % b); }
 constexpr int clog2(int x) { return x <= 1 ? 0 : 1 + clog2(x / 2); }
-
-// diagnostics: thread 0 stores the shader clock at phase boundaries when ScanArgs::stamps is set
-// (TPS_ISA_MARKS, scripts/isa_budget.py: the same boundaries and the phases of the sums tiles as comments in the ISA -- a static
-// instruction budget per phase; never in the product library)
-#if defined(TPS_ISA_MARKS) && !defined(TPS_EMU)
-#define TPS_STAMP(i) asm volatile(";tps_stamp %0" ::"i"(i))
-#define TPS_ISA_MARK(id) asm volatile(";tps_mark %0" ::"i"(id))
-#define TPS_ISA_REGION(id) asm volatile(";tps_region %0" ::"i"(id))
-#elif defined(TPS_EMU) || !defined(TPS_STAMPS)
-#define TPS_STAMP(i) ((void)0)
-#define TPS_ISA_MARK(id) ((void)(id))
-#define TPS_ISA_REGION(id) ((void)(id))
-#else
-#define TPS_STAMP(i) do { if (a.stamps && (threadIdx.x & 63u) == 0) a.stamps[r * 16 + (i)] = __builtin_readcyclecounter(); } while (0)
-#define TPS_ISA_MARK(id) ((void)(id))
-#define TPS_ISA_REGION(id) ((void)(id))
-#endif
-// (TPS_ISA_REGION: the parts of a read's program OUTSIDE the tile phases, for the same static budget -- 1 tile set-up, 2 the
-// tile's staging store, 3 the next tile's prefetch, 4 the tile dispatch, 5 the change point's float32 prefilter, 6 its float64
-// stage and wave reduction, 7 the exact tournament and the result)
-// ... inside the per-pattern tiles (first tile of a read only): 6 = phase 1 done, 7 = windows done, 11 = rows out, 12 = candidates done
-#if defined(TPS_EMU) || !defined(TPS_STAMPS)
-#define TPS_PP_STAMP(i) ((void)0)
-#else
-#define TPS_PP_STAMP(i) do { if (w0 == 0 && a.stamps && (threadIdx.x & 63u) == 0) a.stamps[tc.rd * 16 + (i)] = __builtin_readcyclecounter(); } while (0)
-#endif
 
 // ------------------------------------------------------------------ kernel arguments
 struct PatInfo {
@@ -425,8 +177,8 @@ struct Lds {
     uint32_t* misc;
 };
 constexpr int XLANES = NT + 16;                  // most lanes an exchange row can hold: NT + halo lanes read past the tile end
-TPS_HD int64_t xchg_dw(const ScanArgs& a) {      // fused path: XPC (9 words per lane), XF, XT (xt_alias 1: XT lives elsewhere, 2: both do)
-    return 9ll * NT + (a.xt_alias == 1 ? 1ll : a.xt_alias == 2 ? 0ll : 2ll) * XLANES;
+TPS_HD int64_t xchg_dw(const ScanArgs& a) {      // fused path: XPC (9 words per lane), XF, XT (xt_alias 2: both live elsewhere)
+    return 9ll * NT + (a.xt_alias == 2 ? 0ll : 2ll) * XLANES;
 }
 // dwords of the workgroup's LDS table: 4^k entries of 4 bytes, or of 2 (lut16)
 TPS_HD int64_t lut_dw(const ScanArgs& a) { return a.lut16 ? ((((int64_t)a.lut_n + 1) / 2 + 3) & ~3ll) : (((int64_t)a.lut_n + 3) & ~3ll); }
@@ -499,50 +251,26 @@ constexpr int X_R = X_CB + NT;           // 16 x (u64, u64, i32): second-level r
 // Logical entry i lives at arr[i + (i >> pad_log2)]: one pad word per 2^pad_log2 entries keeps the
 // per-lane runs (lane l owns entries l*per .. l*per+per-1) on different LDS banks.
 TPS_DEV int padded(int i, int pad_log2) { return i + (i >> pad_log2); }
-#ifdef TPS_EMU
 TPS_DEV uint32_t wg_exclusive_scan(uint32_t* arr, int n, uint32_t* scratch, int pad_log2 = 30) {
     (void)scratch;
-    uint32_t run = 0;
-    for (int i = 0; i < n; ++i) { uint32_t t = arr[padded(i, pad_log2)]; arr[padded(i, pad_log2)] = run; run += t; }
-    return run;
-}
-#else
-TPS_DEV uint32_t wg_exclusive_scan(uint32_t* arr, int n, uint32_t* scratch, int pad_log2 = 30) {
-    (void)scratch;
-    const int lane = (int)(threadIdx.x & 63u);
     const int per = (n + NT - 1) / NT;
-    const int lo = lane * per, hi = (lo + per < n) ? lo + per : n;
-    uint32_t s = 0;
-    for (int i = lo; i < hi; ++i) s += arr[padded(i, pad_log2)];
-    // inclusive wave scan with DPP row shifts / broadcasts: six VALU adds, no LDS round trips
-    uint32_t inc = s;
-    inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x111, 0xf, 0xf, false);   // row_shr:1
-    inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x112, 0xf, 0xf, false);   // row_shr:2
-    inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x114, 0xf, 0xf, false);   // row_shr:4
-    inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x118, 0xf, 0xf, false);   // row_shr:8
-    inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x142, 0xa, 0xf, false);   // row_bcast:15 -> rows 1, 3
-    inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x143, 0xc, 0xf, false);   // row_bcast:31 -> rows 2, 3
-    const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
-    uint32_t run = inc - s;
-    for (int i = lo; i < hi; ++i) { uint32_t t = arr[padded(i, pad_log2)]; arr[padded(i, pad_log2)] = run; run += t; }
+    Lane<uint32_t> s;
+    TPS_LANES {
+        const int lo = tid * per, hi = (lo + per < n) ? lo + per : n;
+        uint32_t t = 0;
+        for (int i = lo; i < hi; ++i) t += arr[padded(i, pad_log2)];
+        TPS_AT(s) = t;
+    }
+    const Lane<uint32_t> inc = wave_incl_sum(s);
+    const uint32_t total = wave_read_lane(inc, 63);
+    TPS_LANES {
+        const int lo = tid * per, hi = (lo + per < n) ? lo + per : n;
+        uint32_t run = TPS_AT(inc) - TPS_AT(s);
+        for (int i = lo; i < hi; ++i) { uint32_t t = arr[padded(i, pad_log2)]; arr[padded(i, pad_log2)] = run; run += t; }
+    }
     TPS_SYNC();
     return total;
 }
-#endif
-
-// wave-wide maximum of an unsigned value (device only: DPP row shifts / broadcasts, no LDS round trip)
-#ifndef TPS_EMU
-TPS_DEV uint32_t wave_max_u32(uint32_t v) {
-    auto mx = [](uint32_t a, uint32_t b) { return a > b ? a : b; };
-    v = mx(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false));   // row_shr:1
-    v = mx(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false));   // row_shr:2
-    v = mx(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false));   // row_shr:4
-    v = mx(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false));   // row_shr:8
-    v = mx(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false));   // row_bcast:15 -> rows 1, 3
-    v = mx(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false));   // row_bcast:31 -> rows 2, 3
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
-}
-#endif
 
 // ------------------------------------------------------------------ staging: packed HBM -> LDS
 // The batch is resident in the packed format of tps_pack.h (2 bits per base, 16 bases per word, reads on 16-byte
@@ -627,13 +355,6 @@ TPS_DEV u32x2 stage_orient_inv(const Stage& st, const u32x2& v) {
     r.x = bitrev32(v.y); r.y = bitrev32(v.x);
     return r;
 }
-#ifdef TPS_EMU
-TPS_DEV void lds_store16(uint32_t* p, const u32x4& v) { p[0] = v.x; p[1] = v.y; p[2] = v.z; p[3] = v.w; }
-TPS_DEV void lds_store8(uint32_t* p, const u32x2& v) { p[0] = v.x; p[1] = v.y; }
-#else
-TPS_DEV void lds_store16(uint32_t* p, const u32x4& v) { *(u32x4*)p = v; }        // ds_write_b128 (p is 16-byte aligned)
-TPS_DEV void lds_store8(uint32_t* p, const u32x2& v) { *(u32x2*)p = v; }
-#endif
 
 // lane `tid` stages quads tid, tid+NT, ... of the `nqd` quads at seq2 / val (zeros past the staged range); up to four
 // 16-byte loads are in flight per lane before the first one is consumed.  The invalid words are only touched for reads
@@ -913,10 +634,6 @@ TPS_DEV void trc_count_packed(const ScanArgs& a, const Lds& l, const Stage& st_s
                     tr &= below(npos - 16 * c - 2 * d);
                     if (pat.n_periods == 1) qd &= below(npos - 16 * c - 2 * d); else qd &= below(npos - 16 * c - d);
                 }
-#ifndef TPS_TRC_PAIRWALK
-#define TPS_TRC_PAIRWALK 1        // 0: A/B builds with round 4's walk over all 16 positions of a chunk that holds a pair
-#endif
-#if TPS_TRC_PAIRWALK != 0 && !defined(TPS_EMU_OLD_PAIRWALK)
                 // a pair starts in this chunk (or the bases are periodic without a pattern): its pattern is looked up again, pair by pair --
                 // a lane holds one or two (a deleted base inside the telomere), where walking all 16 positions of the chunk with three masks
                 // each cost 160 instructions per pass whenever ANY lane of the wave had one: always, on telomeric heads at ONT error rates
@@ -932,24 +649,6 @@ TPS_DEV void trc_count_packed(const ScanArgs& a, const Lds& l, const Stage& st_s
                         if ((qd >> j2) & 1u) cf |= hj;
                     }
                 }
-#else
-                if (pr != 0u) {                        // a pair starts in this chunk (or the bases are periodic without a pattern)
-                    uint32_t xp[2] = {0u, 0u}, xt[2] = {0u, 0u};
-                    TPS_UNROLL
-                    for (int j = 0; j < 16; ++j) {
-                        const uint32_t hp = h[j] & (0u - ((pr >> (2 * j)) & 1u));
-                        const uint32_t ht = h[j] & (0u - ((tr >> (2 * j)) & 1u));
-                        xp[j >> 3] += fieldsq(hp);
-                        xt[j >> 3] += fieldsq(ht);
-                        cf |= h[j] & (0u - ((qd >> (2 * j)) & 1u));
-                    }
-                    TPS_UNROLL
-                    for (int half = 0; half < 2; ++half) {
-                        pe += xp[half] & 0x33333333u; po += (xp[half] >> 2) & 0x33333333u;
-                        te += xt[half] & 0x33333333u; to += (xt[half] >> 2) & 0x33333333u;
-                    }
-                }
-#endif
             }
         }
     }
@@ -1342,9 +1041,6 @@ TPS_DEV TileConst tile_const(const ScanArgs& a, int64_t r) {
     return t;
 }
 
-#ifndef TPS_RAW_M
-#define TPS_RAW_M 1           // 0: A/B builds without the every-second-row store of the strided scans (ScanArgs::raw_m)
-#endif
 template <int S>
 struct Geo {
     static constexpr int B = 8;                   // blocks (= windows) per lane
@@ -1375,17 +1071,12 @@ constexpr bool tile_full_default(int s) { return s >= 1; }
 // LDS slice of a wave in the fused kernels: everything whose size is known at compile time comes first, at
 // compile-time offsets from the slice base (one SGPR for all of it, offsets folded into the DS instructions);
 // only the candidate / tile sums, whose size depends on the longest read, follow.  Sizes = plan_geometry's.
-// XTA (the sums-only kernels of self-overlap tables, ScanArgs::xt_alias): XT -- written behind a tile's window phase, read by its
-// candidate phase -- shares its words with the head of the staged bases, which nothing reads after the tile's first phase
-// (tile_lc_s<.., CD>: the lanes' registers and the chain walks).  80 dwords per wave less: with the 16-bit table that is the fifth
-// 4-wave workgroup per CU at k = 6 (8 192 + 4 x 5 856 B = 31 616 <= 32 000).  The fallback tile (tile_fused_s: recounts read the
-// bases AFTER it has rewritten XT) gets XT words of its own behind everything else whenever it can run (ScanArgs::xt_own).
-// XM = 2 (the raw-row kernels, ScanArgs::xt_alias == 2): no XF / XT at all in the exchange region -- tile_pp_s keeps the lanes'
-// totals in the pad words of END; the fallback tile gets both behind everything else whenever it can run (xt_own).
-template <int S, bool FULL, int XM = 0>
+// The exchange region holds no XF / XT arrays (ScanArgs::xt_alias == 2, every fused kernel): tile_lc_s and tile_pp_s keep the
+// lanes' totals in the pad words of their 9-word rows; the fallback tile (tile_fused_s) gets both behind everything else whenever it
+// can run (ScanArgs::xt_own).
+template <int S, bool FULL>
 TPS_DEV Lds carve_fused(uint32_t* base, uint32_t* lut, const ScanArgs& a) {
-    constexpr bool XTA = XM == 1;
-    constexpr int BLK = 9 * NT + (XM == 0 ? 2 : XM == 1 ? 1 : 0) * XLANES, ROW = NT * Geo<S>::B + NT, SEQ = TileGeo<S, FULL>::SEQ;
+    constexpr int BLK = 9 * NT, ROW = NT * Geo<S>::B + NT, SEQ = TileGeo<S, FULL>::SEQ;
     const int VAL = a.val_on ? ((SEQ + 4 + 3) / 4) * 2 : 0;
     static_assert(BLK % 4 == 0 && ROW % 4 == 0 && MISC_DW % 4 == 0 && SEQ % 4 == 0, "seq2 must be 16-byte aligned");
     // seq_alias: the staged bases live in the LAST SEQ dwords of row[].  A tile's lanes read them into registers at the very
@@ -1400,8 +1091,6 @@ TPS_DEV Lds carve_fused(uint32_t* base, uint32_t* lut, const ScanArgs& a) {
     l.lshift = (a.lut16 && !a.lut_fields && !a.pair16) ? LUT_M16 : (a.lut_fields && a.lut16) ? LUT_F16 : a.lut_fields ? LUT_FIELDS : 16;     // (P16K kernels: scan_read sets LUT_M16 itself)
     l.blk = base;
     l.XPC = base;
-    l.XF = base + 9 * NT;
-    l.XT = l.XF + XLANES;                      // (XTA: set below)
     l.G = l.Gp = base; l.C0 = l.C1 = (uint16_t*)base;      // generic-path views: unused here
     l.row = base + BLK;
     l.misc = l.row + ROW;
@@ -1418,11 +1107,8 @@ TPS_DEV Lds carve_fused(uint32_t* base, uint32_t* lut, const ScanArgs& a) {
     l.Lc = p;
     l.Lc16 = (uint16_t*)p;
     l.Tc = p + ((a.lc16 && a.lc_global) ? 0 : ((a.lc_cap + 3) / 4) * 2);
-    if (XTA) l.XT = a.xt_own ? p + lc_dw(a) : l.seq2;
-    if (XM == 2) {                             // (only the fallback tile reads these; without xt_own it cannot run)
-        l.XF = p + lc_dw(a);
-        l.XT = l.XF + XLANES;
-    }
+    l.XF = p + lc_dw(a);                       // (only the fallback tile reads these; without xt_own it cannot run)
+    l.XT = l.XF + XLANES;
     return l;
 }
 
@@ -1440,20 +1126,7 @@ TPS_DEV Lds carve_fused(uint32_t* base, uint32_t* lut, const ScanArgs& a) {
 //   phase 3  (after the exclusive scan of row[]) candidate-strided: Lc[c] = left sum of window c * jump.
 // XS aliases row[]: the only reader of XS[w] is the lane that then writes row[w].
 // Windows beyond nw_tile (they need blocks of the next tile) are not produced.
-#ifdef TPS_EMU
-inline int& emu_counter(int i) { static int c[8] = {0, 0, 0, 0, 0, 0, 0, 0}; return c[i]; }   // tests: 0 = per-pattern tiles, 1 = windows recounted there, 4 = exact change-point tournaments, 5 = sums tiles of a self-overlap table with chains corrected, 6 = ... without a chain, 3 = sums tiles with the window phase in 16-bit pairs, 7 = sums tiles that store their candidates lane by lane
-#endif
 TPS_DEV uint32_t pack_hi_lo(uint32_t hi_src, uint32_t lo_src) { return perm(hi_src, lo_src, 0x07060100u); }
-// two 16-bit lanes in one word (lane 0 = bits 0 .. 15): lane-wise a - b; a + the low half of b in both
-#ifdef TPS_EMU
-TPS_DEV uint32_t pk_u16_sub(uint32_t a, uint32_t b) { return ((a - b) & 0xFFFFu) | (((a >> 16) - (b >> 16)) << 16); }
-TPS_DEV uint32_t pk_u16_add(uint32_t a, uint32_t b) { return ((a + b) & 0xFFFFu) | (((a >> 16) + b) << 16); }
-#else
-typedef unsigned short tps_u16x2 __attribute__((ext_vector_type(2)));
-TPS_DEV tps_u16x2 as_u16x2(uint32_t v) { return __builtin_bit_cast(tps_u16x2, v); }
-TPS_DEV uint32_t pk_u16_sub(uint32_t a, uint32_t b) { return __builtin_bit_cast(uint32_t, as_u16x2(a) - as_u16x2(b)); }                                          // v_pk_sub_u16
-TPS_DEV uint32_t pk_u16_add(uint32_t a, uint32_t b) { return __builtin_bit_cast(uint32_t, as_u16x2(a) + (tps_u16x2)((unsigned short)b)); }                     // v_pk_add_u16 op_sel_hi:[1,0]
-#endif
 
 // RAW: this instantiation can also produce the per-pattern counts (TPS_F_STORE_RAW); the kernels without it carry
 // no recount code at all unless the table has self-overlapping k-mers.
@@ -1461,7 +1134,7 @@ TPS_DEV uint32_t pk_u16_add(uint32_t a, uint32_t b) { return __builtin_bit_cast(
 // A window ends r positions into a block, so every block publishes its prefix words at that position; with r known at
 // compile time the capture is a plain copy at one unrolled position instead of two selects at every position (measured on
 // the slide-7 kernel, r = 4: 112 of ~565 instructions per tile).  scan_read switches on r once per tile.
-template <int S, bool SO, bool INV, int RPT, bool PAIR, bool RAW>
+template <int S, bool SO, bool INV, int RPT, bool RAW>
 TPS_DEV void tile_fused_s(const ScanArgs& a, const TileConst& tc, const Lds& l, int delta, int w0, int tile, int nw_tile,
                           int64_t out_base, uint64_t& s_total, int64_t r) {
     // RZ: the window has no partial block (W - k divisible by the slide), so nothing is captured mid-block
@@ -1494,53 +1167,7 @@ TPS_DEV void tile_fused_s(const ScanArgs& a, const TileConst& tc, const Lds& l, 
         uint32_t gs[B], c0s[B];                   // in the high half, ADD the match count in the low half
         uint32_t* xs = l.row + span * (B + 1);
         uint32_t* xpc = l.XPC + span * (B + 1);
-        if constexpr (PAIR) {
-            // Pair table: one lookup covers positions p and p+1 (entry = OR of their masks | sum of their
-            // counts), so a block costs S/2 lookups (+ one single for an odd slide).  Only tables
-            // without self-overlapping k-mers on tiles without invalid letters take this path.
-            static_assert(!SO && !INV, "pair lookups need per-position independence");
-            constexpr int NP = S / 2, NH = NP + (S & 1);
-            const uint32_t amask2 = (pat.kmask << 4) | 0xCu;     // (k+1)-mer code as a byte offset
-            const int rpe = rp & ~1;                              // capture point rounded down to a pair boundary
-            uint32_t hc[NH], hn[NH];
-            auto v4_at = [&](int p) -> uint32_t {
-                const int dw = p >> 4, bit = p & 15;
-                return bit ? alignbit(dw + 1 < WDW ? w[dw + 1] : 0u, w[dw], 2u * bit) : w[dw];
-            };
-            auto fetch = [&](int blk, uint32_t* hh) {
-                TPS_UNROLL
-                for (int j = 0; j < NP; ++j) hh[j] = lut_at(l.lut2, v4_at(blk * S + 2 * j), amask2);
-                if (S & 1) hh[NP] = lut_at(l.lut, v4_at(blk * S + S - 1), amask);
-            };
-            fetch(0, hc);
-            TPS_UNROLL
-            for (int blk = 0; blk < B; ++blk) {
-                if (blk + 1 < B) fetch(blk + 1, hn);
-                uint32_t g = 0;
-                c0s[blk] = cnt;
-                if (RZ) xpc[blk] = pack_hi_lo(run_or, cnt);
-                TPS_UNROLL
-                for (int j = 0; j < NH; ++j) {
-                    if (!RZ) {
-                        if (2 * j == rpe) {          // uniform: the window's partial block ends inside / before this pair
-                            uint32_t c1 = cnt, pp = run_or | g;
-                            if (rp & 1) {
-                                const uint32_t h1 = lut_at(l.lut, v4_at(blk * S + 2 * j), amask);
-                                c1 += h1;
-                                pp |= h1;
-                            }
-                            xpc[blk] = pack_hi_lo(pp, c1);
-                        }
-                    }
-                    g |= hc[j];
-                    cnt += hc[j];
-                }
-                gs[blk] = g;
-                run_or |= g;
-                TPS_UNROLL
-                for (int j = 0; j < NH; ++j) hc[j] = hn[j];
-            }
-        } else {
+        {
             // table lookups run one block ahead of their use (software pipeline, 2 S values in flight)
             uint32_t hc[S], hn[S];
             auto fetch = [&](int blk, uint32_t* hh, int cnt_) {
@@ -1637,10 +1264,7 @@ TPS_DEV void tile_fused_s(const ScanArgs& a, const TileConst& tc, const Lds& l, 
     if (w0 == 0) TPS_STAMP(6);
     if (w0 == 0) TPS_STAMP(7);
     const int rot = q & (B - 1), dl0 = q >> LOG2B;
-    uint32_t fo_a = 0, fo_b = 0;
-#ifdef TPS_EMU
-    uint32_t fo_keep[NT][2];
-#endif
+    Lane<uint32_t> fo_a(0), fo_b(0);
     TPS_PHASE {
         // A window's last (partial) block lies dl0 or dl0+1 lanes ahead of its first.  What it skips: the OR of
         // the whole lanes strictly in between (the next dl0-1, or dl0, lanes) and the matches of every lane from
@@ -1654,28 +1278,17 @@ TPS_DEV void tile_fused_s(const ScanArgs& a, const TileConst& tc, const Lds& l, 
             sumw += v;
         }
         const uint32_t vb = l.XF[tid + dl0];
-        fo_a = pack_hi_lo(orw, sumw);
-        fo_b = pack_hi_lo(orw | vb, sumw + vb);
-#ifdef TPS_EMU
-        fo_keep[tid][0] = fo_a; fo_keep[tid][1] = fo_b;
-#endif
+        TPS_AT(fo_a) = pack_hi_lo(orw, sumw);
+        TPS_AT(fo_b) = pack_hi_lo(orw | vb, sumw + vb);
     }
     TPS_SYNC();                                   // every lane has read its inputs: XF / XT are reused in place
     TPS_PHASE {
-#ifdef TPS_EMU
-        fo_a = fo_keep[tid][0]; fo_b = fo_keep[tid][1];
-#endif
-        l.XF[tid] = fo_a;
-        l.XT[tid] = fo_b;
+        l.XF[tid] = TPS_AT(fo_a);
+        l.XT[tid] = TPS_AT(fo_b);
     }
     TPS_SYNC();
-#ifdef TPS_EMU
-    uint32_t redo_keep[NT][1 + Geo<S>::B / 2];
-#else
-    uint32_t redo_flags = 0, redo_present[Geo<S>::B / 2];
-    TPS_UNROLL
-    for (int t = 0; t < Geo<S>::B / 2; ++t) redo_present[t] = 0;
-#endif
+    Lane<uint32_t> redo_flags(0);                    // bit u: window 64 u + lane is queued for the exact recount
+    LaneArr<uint32_t, Geo<S>::B / 2> redo_present = {};   // ... and the windows' presence masks, two per word
     TPS_PHASE {
         const uint32_t lane = (uint32_t)tid;
         const bool farl = (((lane & (B - 1)) + (uint32_t)rot) >> LOG2B) != 0;
@@ -1723,14 +1336,9 @@ TPS_DEV void tile_fused_s(const ScanArgs& a, const TileConst& tc, const Lds& l, 
                 const int nv = nfull + ((lane < npart) ? 1 : 0);
                 flags = nv >= B ? (1u << B) - 1u : (1u << nv) - 1u;
             }
-#ifdef TPS_EMU
-            redo_keep[tid][0] = flags;
-            for (int t = 0; t < B / 2; ++t) redo_keep[tid][1 + t] = present[t];
-#else
-            redo_flags = flags;
+            TPS_AT(redo_flags) = flags;
             TPS_UNROLL
-            for (int t = 0; t < B / 2; ++t) redo_present[t] = present[t];
-#endif
+            for (int t = 0; t < B / 2; ++t) TPS_AT(redo_present)[t] = present[t];
         }
     }
     if (SO || (RAW && a.raw)) {
@@ -1738,16 +1346,10 @@ TPS_DEV void tile_fused_s(const ScanArgs& a, const TileConst& tc, const Lds& l, 
         uint32_t* queue = l.XPC;                       // up to NT * B entries
         uint32_t* occ = l.XPC + NT * B;                // [P <= 15][4] occurrence bits of one window, + the correction
         TPS_PHASE {
-            uint32_t flags;
+            uint32_t flags = TPS_AT(redo_flags);
             uint32_t present[B / 2];
-#ifdef TPS_EMU
-            flags = redo_keep[tid][0];
-            for (int t = 0; t < B / 2; ++t) present[t] = redo_keep[tid][1 + t];
-#else
-            flags = redo_flags;
             TPS_UNROLL
-            for (int t = 0; t < B / 2; ++t) present[t] = redo_present[t];
-#endif
+            for (int t = 0; t < B / 2; ++t) present[t] = TPS_AT(redo_present)[t];
             while (flags) {
                 const int u = ffs0(flags);
                 flags &= flags - 1;
@@ -1916,76 +1518,6 @@ TPS_DEV void tile_candidates(const TileConst& tc, const Lds& l, int w0, int tile
 // Against tile_fused_s per tile and lane: 17 LDS stores instead of 35 (no XS, no rewritten XF / XT, no second copy of
 // S_w for the scan), 13 + the table gathers LDS loads instead of 37 + the gathers, three wave barriers instead of six,
 // two 16-byte stores to HBM instead of eight dword stores.
-#ifndef TPS_PP_RPT
-#define TPS_PP_RPT 1        // (0: A/B builds -- the per-pattern tiles read the window's partial-block position at run time, as before round 5)
-#endif
-#ifndef TPS_PP_PAIRF
-#define TPS_PP_PAIRF 1      // (0: A/B builds -- _s6r looks every position up by itself although the pair table of fields is loaded)
-#endif
-#ifndef TPS_XPAD
-#define TPS_XPAD 1          // (0: the default kernels keep XF / XT arrays in the exchange region -- A/B builds, with TPS_NO_XPAD=1 in the environment)
-#endif
-#ifndef TPS_LC_TILE
-#define TPS_LC_TILE 1
-#endif
-// Cache policy of the kernels' big output streams (S_w, raw rows: buffer stores): 2 = nt, non-temporal (gfx940+), 0 = default.
-// Nothing on the device reads these bytes again (the exact change-point tournament aside); streamed past the caches they cost
-// less HBM time: 10 000 x 25 kb reads with raw rows 192.7 -> 176.8 us per launch, config 2 57.4 -> 56.3 us (same box, A/B).
-#ifndef TPS_STORE_AUX
-#define TPS_STORE_AUX 2
-#endif
-// the lane's 8 window sums -> tile_out[8 lane .. 8 lane + 7] as 16-bit values, windows at or past nw_tile dropped
-// (g_store_sw8p: the same from the 4 words of 16-bit pairs, window 2 i in the low half of word i)
-#ifdef TPS_EMU
-TPS_DEV void g_store_sw8(uint16_t* tile_out, int lane, int nw_tile, const uint32_t* v) {
-    for (int i = 0; i < 8; ++i)
-        if (8 * lane + i < nw_tile) tile_out[8 * lane + i] = (uint16_t)v[i];
-}
-TPS_DEV void g_store_sw8p(uint16_t* tile_out, int lane, int nw_tile, const uint32_t* p) {
-    for (int i = 0; i < 8; ++i)
-        if (8 * lane + i < nw_tile) tile_out[8 * lane + i] = (uint16_t)(p[i >> 1] >> (16 * (i & 1)));
-}
-#else
-TPS_DEV void g_store_sw8(uint16_t* tile_out, int lane, int nw_tile, const uint32_t* v) {
-    // One buffer_store_dwordx4 (16 contiguous bytes per lane) through a raw buffer descriptor that ends behind the tile's last
-    // window: the hardware range-checks every dword of a multi-dword store on its own and drops the ones past the end (GCN3 /
-    // Vega ISA, "range checking": raw buffers, store_dword_x{2,3,4} per component) -- the lane that holds the tile's last windows
-    // needs no exec masking and no scalar fallback.  A dword is two windows: tiles start at even windows (plan_geometry keeps
-    // the windows per tile even, a read's region starts at a multiple of 8), and the odd last window of a read takes the padding
-    // slot behind it along.  The descriptor is wave-uniform (SGPRs only).
-    typedef unsigned int v4u __attribute__((ext_vector_type(4)));
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)tile_out, 0, ((nw_tile + 1) & ~1) * 2, 0x00020000);
-    v4u t;
-    t.x = v[0] | (v[1] << 16); t.y = v[2] | (v[3] << 16); t.z = v[4] | (v[5] << 16); t.w = v[6] | (v[7] << 16);      // (v_lshl_or_b32; every S_w < 2^16)
-    __builtin_amdgcn_raw_buffer_store_b128(t, rs, lane * 16, 0, TPS_STORE_AUX);
-}
-TPS_DEV void g_store_sw8p(uint16_t* tile_out, int lane, int nw_tile, const uint32_t* p) {
-    typedef unsigned int v4u __attribute__((ext_vector_type(4)));
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)tile_out, 0, ((nw_tile + 1) & ~1) * 2, 0x00020000);
-    v4u t;
-    t.x = p[0]; t.y = p[1]; t.z = p[2]; t.w = p[3];
-    __builtin_amdgcn_raw_buffer_store_b128(t, rs, lane * 16, 0, TPS_STORE_AUX);
-}
-#endif
-// 16 bytes -> base[cdw .. cdw + 3] (dwords), the dwords at or past n_dw dropped: one range-checked buffer_store_dwordx4 at a
-// dword-aligned address instead of four dword stores and a tail case
-#ifdef TPS_EMU
-TPS_DEV void g_store16_clamped(uint32_t* base, int n_dw, int cdw, const u32x4& t) {
-    const uint32_t v[4] = {t.x, t.y, t.z, t.w};
-    for (int i = 0; i < 4; ++i)
-        if (cdw + i < n_dw) base[cdw + i] = v[i];
-}
-#else
-TPS_DEV void g_store16_clamped(uint32_t* base, int n_dw, int cdw, const u32x4& t) {
-    typedef unsigned int v4u __attribute__((ext_vector_type(4)));
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, n_dw * 4, 0x00020000);
-    v4u x;
-    x.x = t.x; x.y = t.y; x.z = t.z; x.w = t.w;
-#ifndef TPS_NO_RAW_STORE                              /* (diagnostic builds only: what do the raw-row stores cost?) */
-    __builtin_amdgcn_raw_buffer_store_b128(x, rs, cdw * 4, 0, TPS_STORE_AUX);
-#endif
-}
-#endif
 // ROTZ: q (the window's whole blocks) is a multiple of 8 -- every window ends in the same block-in-lane it starts in, dl0
 // lanes on: no per-window choice between the near and the far end lane (the default geometry: W = 100, k = 4, slide 6).
 // CD > 0: the table's self-overlapping k-mers share the ONE period CD (2 CD >= k), sums only.  re.finditer counts leftmost
@@ -2012,15 +1544,14 @@ TPS_DEV void tile_lc_s(const ScanArgs& a, const TileConst& tc, const Lds& l, int
     // (P16_: the pair-table kernels of k = 5 tables -- pair and single table both in that format, ScanArgs::pair16)
     constexpr bool M16 = CD > 0 || P16_;
     constexpr int LS = M16 ? 1 : 2;               // log2(bytes per table entry)
-    // XPAD (the default kernels, round 4): a lane's OR | matches (XF) and its exclusive prefix in the tile (XT) live in the pad words of
-    // its XPC and row[] rows (9 words per lane, the ninth unused) -- no XF / XT arrays in the wave's slice (carve_fused<.., XM = 2>)
-    // (round 5: the chain-corrected tiles too -- nothing of theirs touches the pad words: the window phase and the difference array
-    // index row[] / XPC by PADDED window, the zeroing of the difference array comes before xt_at is written -- which frees the 80
-    // dwords of XF per wave that stood between the k = 6 sums kernel and three 8-wave workgroups per CU: 6 waves per SIMD)
-    constexpr bool XPAD = TPS_XPAD != 0;
+    // A lane's OR | matches (XF) and its exclusive prefix in the tile (XT) live in the pad words of its XPC and row[] rows (9 words
+    // per lane, the ninth unused) -- no XF / XT arrays in the wave's slice (carve_fused).  Nothing of the chain-corrected tiles
+    // touches the pad words either: the window phase and the difference array index row[] / XPC by PADDED window, the zeroing of
+    // the difference array comes before xt_at is written -- which frees the 80 dwords of XF per wave that stood between the k = 6
+    // sums kernel and three 8-wave workgroups per CU: 6 waves per SIMD
     typedef Geo<S> g_;
-    auto xf_at = [&](int lane_) -> uint32_t& { return XPAD ? l.XPC[lane_ * (g_::B + 1) + g_::B] : l.XF[lane_]; };
-    auto xt_at = [&](int lane_) -> uint32_t& { return XPAD ? l.row[lane_ * (g_::B + 1) + g_::B] : l.XT[lane_]; };
+    auto xf_at = [&](int lane_) -> uint32_t& { return l.XPC[lane_ * (g_::B + 1) + g_::B]; };
+    auto xt_at = [&](int lane_) -> uint32_t& { return l.row[lane_ * (g_::B + 1) + g_::B]; };
     constexpr int B = g_::B, LOG2B = g_::LOG2B, POS = g_::POS;
     constexpr int LB = CD;                        // CD: the lane's registers start CD positions before its first one (look-back of the pair test)
     constexpr int WDW = (LB + POS + 13 + 15) / 16;
@@ -2034,15 +1565,10 @@ TPS_DEV void tile_lc_s(const ScanArgs& a, const TileConst& tc, const Lds& l, int
     const uint32_t amask = pat.kmask << LS;
     // what a lane keeps about its blocks (table entries are mask << 16 | count: the OR of entries is right in its high half,
     // their sum in its low half -- the other halves are garbage that the window arithmetic never looks at)
-    uint32_t sfx[B], c0s[B], xf_own = 0;         // OR of this and the lane's later blocks; matches before the block; the lane's OR | matches
-#ifdef TPS_EMU
-    uint32_t sfx_keep[NT][B], c0_keep[NT][B], xf_keep[NT];
-#endif
-    uint32_t lane_chain = 0;                      // CD: this lane found the head of a chain of three or more (it added steps to the difference array)
-    uint32_t pair_lo = 0, pair_hi = 0;            // CD: bit e = some pattern occurs at the lane's position e and CD before it (a pair, filed under its SECOND element)
-#ifdef TPS_EMU
-    uint32_t pair_keep[NT][2];
-#endif
+    LaneArr<uint32_t, B> sfx_, c0s_;                // OR of this and the lane's later blocks; matches before the block
+    Lane<uint32_t> xf_own(0);                     // the lane's OR | matches
+    uint32_t lane_chain = 0;                      // CD: some lane found the head of a chain of three or more (steps were added to the difference array)
+    Lane<uint32_t> pair_lo_(0), pair_hi_(0);        // CD: bit e = some pattern occurs at the lane's position e and CD before it (a pair, filed under its SECOND element)
     // (CD) a chain of three or more occurrences CD apart, first element at tile position tp (it may lie before the tile), pattern
     // mask pm: the pair count takes n - 1 off a window that holds n consecutive elements, finditer counts ceil(n / 2) = n - (n - 1)
     // + floor((n - 1) / 2) -- the steps of floor((n - 1) / 2), window by window, go to the difference array (any length, exact)
@@ -2102,7 +1628,7 @@ TPS_DEV void tile_lc_s(const ScanArgs& a, const TileConst& tc, const Lds& l, int
         };
         uint32_t cnt = 0, run_or = 0;
         uint32_t gs[B];
-        pair_lo = pair_hi = 0;                    // (per lane)
+        TPS_AT(pair_lo_) = TPS_AT(pair_hi_) = 0;
         uint32_t* xpc = l.XPC + span * (B + 1);
         if constexpr (PAIR) {
             constexpr int NP = S / 2, NH = NP + (S & 1);
@@ -2111,15 +1637,15 @@ TPS_DEV void tile_lc_s(const ScanArgs& a, const TileConst& tc, const Lds& l, int
             uint32_t hc[NH], hn[NH];
             auto fetch = [&](int blk, uint32_t* hh) {
                 TPS_UNROLL
-                for (int j = 0; j < NP; ++j) hh[j] = M16 ? lut16_at(l.lut2, v4_at(blk * S + 2 * j), amask2) : lut_at_tile(l.lut2, v4_at(blk * S + 2 * j), amask2);
-                if (S & 1) hh[NP] = M16 ? lut16_at(l.lut, v4_at(blk * S + S - 1), amask) : lut_at_tile(l.lut, v4_at(blk * S + S - 1), amask);
+                for (int j = 0; j < NP; ++j) hh[j] = M16 ? lut16_at(l.lut2, v4_at(blk * S + 2 * j), amask2) : lut_at(l.lut2, v4_at(blk * S + 2 * j), amask2);
+                if (S & 1) hh[NP] = M16 ? lut16_at(l.lut, v4_at(blk * S + S - 1), amask) : lut_at(l.lut, v4_at(blk * S + S - 1), amask);
             };
             fetch(0, hc);
             TPS_UNROLL
             for (int blk = 0; blk < B; ++blk) {
                 if (blk + 1 < B) fetch(blk + 1, hn);
                 uint32_t g = 0;
-                c0s[blk] = cnt;
+                TPS_AT(c0s_)[blk] = cnt;
                 if (RZ) xpc[blk] = M16 ? ((run_or << 16) | cnt) : pack_hi_lo(run_or, cnt);
                 TPS_UNROLL
                 for (int j = 0; j < NH; ++j) {
@@ -2179,15 +1705,15 @@ TPS_DEV void tile_lc_s(const ScanArgs& a, const TileConst& tc, const Lds& l, int
                         TPS_UNROLL
                         for (int i = 0; i < S; ++i) {
                             const uint32_t pr = (hc[i] & (i >= CD ? hc[i - CD] : hb[i])) ? 1u : 0u;
-                            if (blk * S + i < 32) pair_lo |= pr << ((blk * S + i) & 31);
-                            else pair_hi |= pr << ((blk * S + i) & 31);
+                            if (blk * S + i < 32) TPS_AT(pair_lo_) |= pr << ((blk * S + i) & 31);
+                            else TPS_AT(pair_hi_) |= pr << ((blk * S + i) & 31);
                         }
                     }
                     TPS_UNROLL
                     for (int i = 0; i < CD; ++i) hb[i] = hc[S - CD + i];
                 }
                 uint32_t g = 0;
-                c0s[blk] = cnt;
+                TPS_AT(c0s_)[blk] = cnt;
                 uint32_t c1 = cnt, pp = run_or;
                 // CD >= S - 2 (slide 6: k = 6 with CD = 5, k = 5 with CD = 4): two occurrences of a pattern are CD apart (the table's one
                 // period) or at least k > CD, so a block of S <= CD + 2 positions holds a pattern at most twice -- CD apart, or at its
@@ -2236,16 +1762,11 @@ TPS_DEV void tile_lc_s(const ScanArgs& a, const TileConst& tc, const Lds& l, int
         TPS_UNROLL
         for (int j = B - 1; j >= 0; --j) {
             sf = M16 ? ((gs[j] << 16) | sf) : (sf | gs[j]);      // (the window phase wants the masks in the high half)
-            sfx[j] = sf;
+            TPS_AT(sfx_)[j] = sf;
         }
-        xf_own = M16 ? (sf | cnt) : pack_hi_lo(sf, cnt);
-        xf_at(span) = xf_own;
-        if constexpr (CD > 0) { TPS_PIN_V(pair_lo); TPS_PIN_V(pair_hi); }
-#ifdef TPS_EMU
-        for (int j = 0; j < B; ++j) { sfx_keep[tid][j] = sfx[j]; c0_keep[tid][j] = c0s[j]; }
-        xf_keep[tid] = xf_own;
-        pair_keep[tid][0] = pair_lo; pair_keep[tid][1] = pair_hi;
-#endif
+        TPS_AT(xf_own) = M16 ? (sf | cnt) : pack_hi_lo(sf, cnt);
+        xf_at(span) = TPS_AT(xf_own);
+        if constexpr (CD > 0) { TPS_PIN_V(TPS_AT(pair_lo_)); TPS_PIN_V(TPS_AT(pair_hi_)); }
     }
     if constexpr (CD > 0) {
         // Pairs (round 4).  A pair -- the same pattern at e - CD and e, filed under e -- lies inside a window iff
@@ -2260,25 +1781,15 @@ TPS_DEV void tile_lc_s(const ScanArgs& a, const TileConst& tc, const Lds& l, int
         // (Round 3 walked every chain from its head: five dependent LDS round trips and two atomics per pair, ~30 pairs per
         // telomeric tile at ONT error rates -- a third of the k = 6 kernel's instructions.)
         constexpr int PS = 8;
-#ifdef TPS_EMU
-        bool tile_pairs = false;
-        for (int t = 0; t < NT; ++t) tile_pairs = tile_pairs || (pair_keep[t][0] | pair_keep[t][1]) != 0u;
-#else
-        const bool tile_pairs = __builtin_amdgcn_ballot_w64((pair_lo | pair_hi) != 0u) != 0;
-#endif
+        Lane<bool> has_pair;
+        TPS_LANES { TPS_AT(has_pair) = (TPS_AT(pair_lo_) | TPS_AT(pair_hi_)) != 0u; }
+        const bool tile_pairs = wave_ballot(has_pair) != 0;
         if (tile_pairs) {
             TPS_SYNC();                               // (every lane's words are published: the atomics below add to them)
-            uint32_t head3_lo = 0, head3_hi = 0;      // second elements of the first pair of a chain of three or more
-#ifdef TPS_EMU
-            uint32_t head3_keep[NT][2];
-#endif
+            Lane<uint32_t> head3_lo(0), head3_hi(0);  // second elements of the first pair of a chain of three or more
             TPS_PHASE {
-#ifdef TPS_EMU
-                pair_lo = pair_keep[tid][0]; pair_hi = pair_keep[tid][1];
-                for (int j = 0; j < B; ++j) c0s[j] = c0_keep[tid][j];
-                xf_own = xf_keep[tid];
-#endif
                 const int lane = tid;
+                const uint32_t pair_lo = TPS_AT(pair_lo_), pair_hi = TPS_AT(pair_hi_);
                 auto below = [&](int n) -> uint32_t {     // pairs at positions < n (n constant after unrolling, 0 <= n <= 64)
                     if (n <= 0) return 0u;
                     if (n >= 64) return (uint32_t)(popc(pair_lo) + popc(pair_hi));
@@ -2291,26 +1802,19 @@ TPS_DEV void tile_lc_s(const ScanArgs& a, const TileConst& tc, const Lds& l, int
                     for (int blk = 0; blk < B; ++blk) {
                         const uint32_t pe = below(blk * S + (RZ ? 0 : RPT));      // (RPT is a compile-time constant in these tiles)
                         if (pe) lds_add(&xpc[blk], pe << PS);
-                        c0s[blk] += below(blk * S + CD) << PS;
+                        TPS_AT(c0s_)[blk] += below(blk * S + CD) << PS;
                     }
                     const uint32_t pt = below(64) << PS;
-                    xf_own += pt;
+                    TPS_AT(xf_own) += pt;
                     lds_add(&xf_at(lane), pt);
                 }
                 // chains of three or more: pair bits CD apart.  The neighbours' bits close the lane's ends (nothing before the
                 // tile's first lane: what lies there is in none of its windows; nothing behind the last: nor is that)
-                uint32_t prev_hi, next_lo;
-#ifdef TPS_EMU
-                prev_hi = lane > 0 ? pair_keep[lane - 1][1] : 0u;
-                const uint32_t prev_lo_ = lane > 0 ? pair_keep[lane - 1][0] : 0u;
-                next_lo = lane + 1 < NT ? pair_keep[lane + 1][0] : 0u;
-#else
-                prev_hi = (uint32_t)__builtin_amdgcn_ds_bpermute(((lane + NT - 1) & (NT - 1)) << 2, (int)pair_hi);
-                const uint32_t prev_lo_ = (uint32_t)__builtin_amdgcn_ds_bpermute(((lane + NT - 1) & (NT - 1)) << 2, (int)pair_lo);
-                next_lo = (uint32_t)__builtin_amdgcn_ds_bpermute(((lane + 1) & (NT - 1)) << 2, (int)pair_lo);
+                uint32_t prev_hi = wave_shuffle(pair_hi_, lane, (lane + NT - 1) & (NT - 1));
+                const uint32_t prev_lo_ = wave_shuffle(pair_lo_, lane, (lane + NT - 1) & (NT - 1));
+                uint32_t next_lo = wave_shuffle(pair_lo_, lane, (lane + 1) & (NT - 1));
                 if (lane == 0) prev_hi = 0u;
                 if (lane == NT - 1) next_lo = 0u;
-#endif
                 const uint64_t pm64 = ((uint64_t)pair_hi << 32) | pair_lo;
                 const uint64_t pv64 = lane > 0 ? (((uint64_t)prev_hi << 32) | prev_lo_) : 0ull;
                 // bit e of `before`: a pair at e - CD (the previous lane's last CD positions for e < CD); of `after`: one at e + CD
@@ -2318,19 +1822,11 @@ TPS_DEV void tile_lc_s(const ScanArgs& a, const TileConst& tc, const Lds& l, int
                 const uint64_t after = (pm64 >> CD) | ((uint64_t)(next_lo & ((1u << CD) - 1u)) << (POS - CD));
                 const uint64_t lim = POS >= 64 ? ~0ull : ((1ull << POS) - 1ull);
                 const uint64_t h3 = pm64 & ~before & after & lim;
-                head3_lo = (uint32_t)h3; head3_hi = (uint32_t)(h3 >> 32);
-#ifdef TPS_EMU
-                for (int j = 0; j < B; ++j) c0_keep[tid][j] = c0s[j];
-                xf_keep[tid] = xf_own;
-                head3_keep[tid][0] = head3_lo; head3_keep[tid][1] = head3_hi;
-#endif
+                TPS_AT(head3_lo) = (uint32_t)h3; TPS_AT(head3_hi) = (uint32_t)(h3 >> 32);
             }
-#ifdef TPS_EMU
-            bool tile_long = false;
-            for (int t = 0; t < NT; ++t) tile_long = tile_long || (head3_keep[t][0] | head3_keep[t][1]) != 0u;
-#else
-            const bool tile_long = __builtin_amdgcn_ballot_w64((head3_lo | head3_hi) != 0u) != 0;
-#endif
+            Lane<bool> has_head3;
+            TPS_LANES { TPS_AT(has_head3) = (TPS_AT(head3_lo) | TPS_AT(head3_hi)) != 0u; }
+            const bool tile_long = wave_ballot(has_head3) != 0;
             if (tile_long) {
                 TPS_PHASE {
                     TPS_UNROLL
@@ -2349,21 +1845,16 @@ TPS_DEV void tile_lc_s(const ScanArgs& a, const TileConst& tc, const Lds& l, int
                         each_lane(te - CD, c);
                     }
                 };
-#ifdef TPS_EMU
-                for (int src = 0; src < NT; ++src)
-                    one_owner(src, head3_keep[src][0], head3_keep[src][1], [&](int tp, int c) { for (int ln = 0; ln < NT; ++ln) chain_windows(tp, c, ln); });
-#else
                 {
-                    const int ln = tps_fresh_lane();
-                    uint64_t owners = __builtin_amdgcn_ballot_w64((head3_lo | head3_hi) != 0u);
+                    const int ln = tps_fresh_lane();      // (one opaque lane id for all the chains' phases)
+                    uint64_t owners = wave_ballot(has_head3);
                     while (owners) {
                         const int src = __builtin_ctzll(owners);
                         owners &= owners - 1ull;
-                        const uint32_t h_lo = (uint32_t)__builtin_amdgcn_readlane((int)head3_lo, src), h_hi = (uint32_t)__builtin_amdgcn_readlane((int)head3_hi, src);
-                        one_owner(src, h_lo, h_hi, [&](int tp, int c) { chain_windows(tp, c, ln); });
+                        const uint32_t h_lo = wave_read_lane(head3_lo, src), h_hi = wave_read_lane(head3_hi, src);
+                        one_owner(src, h_lo, h_hi, [&](int tp, int c) { TPS_PHASE_WITH(ln) chain_windows(tp, c, tid); });
                     }
                 }
-#endif
                 lane_chain = 1u;                      // (uniform: some lane added steps)
             }
         }
@@ -2374,16 +1865,15 @@ TPS_DEV void tile_lc_s(const ScanArgs& a, const TileConst& tc, const Lds& l, int
     const int rot = ROTZ ? 0 : (q & (B - 1)), dl0 = q >> LOG2B;
     const int brk = B - rot;                      // windows j >= brk end one lane further on
     constexpr bool SWP = CD == 0 && !M16 && ROTZ;     // (round 6) the window phase in 16-bit pairs (below)
-    uint32_t sw[B], swp[B / 2], ltot = 0;           // (SWP) swp[i]: S_w of windows 2 i and 2 i + 1 as the 16-bit pair the store writes
-#ifdef TPS_EMU
-    uint32_t sw_keep[NT][B], swp_keep[NT][B / 2], tot_keep[NT];
-#endif
+    LaneArr<uint32_t, B> sw_;                     // the lane's 8 window sums
+    LaneArr<uint32_t, B / 2> swp_;                // (SWP) swp[i]: S_w of windows 2 i and 2 i + 1 as the 16-bit pair the store writes
+    Lane<uint32_t> ltot(0);                       // ... and their total
     TPS_PHASE {
-#ifdef TPS_EMU
-        for (int j = 0; j < B; ++j) { sfx[j] = sfx_keep[tid][j]; c0s[j] = c0_keep[tid][j]; }
-        xf_own = xf_keep[tid];
-#endif
         const int lane = tid;
+        uint32_t* const sw = TPS_AT(sw_);
+        uint32_t* const swp = TPS_AT(swp_);
+        const uint32_t* const sfx = TPS_AT(sfx_);
+        const uint32_t* const c0s = TPS_AT(c0s_);
         // the far-end words first: one LDS round trip for the lane's 8 windows (rows past the tile's windows read in-bounds
         // garbage: what they turn into is never stored and never counted)
         const uint32_t* pe = l.XPC + (lane + dl0) * (B + 1) + rot;
@@ -2392,7 +1882,7 @@ TPS_DEV void tile_lc_s(const ScanArgs& a, const TileConst& tc, const Lds& l, int
         for (int j = 0; j < B; ++j) ev[j] = pe[j + ((!ROTZ && j >= brk) ? 1 : 0)];       // (the pad word between two lanes' blocks)
         // whole lanes a window skips: OR of the lanes strictly in between, matches of every lane from its own up to the
         // one before the last -- for both possible lane distances
-        uint32_t orw = 0, sumw = xf_own;
+        uint32_t orw = 0, sumw = TPS_AT(xf_own);
         TPS_NOVEC
         for (int t = 1; t < dl0; ++t) {
             const uint32_t v = xf_at(lane + t);
@@ -2412,9 +1902,7 @@ TPS_DEV void tile_lc_s(const ScanArgs& a, const TileConst& tc, const Lds& l, int
         orb |= ~am;
         uint32_t run = 0;
         if constexpr (SWP) {
-#ifdef TPS_EMU
-            if (tid == 0) ++emu_counter(3);
-#endif
+            if (tid == 0) TPS_EMU_COUNT(3);
             // (round 6) the home shape: every window has the same far lane, so two windows' counts go through one packed
             // 16-bit subtract and add (v_pk_sub / v_pk_add_u16 on the low halves: exact modulo 2^16, as the & 0xFFFF was) and
             // leave as the 16-bit pair the S_w store writes (g_store_sw8p); the absent patterns go into the low window's half
@@ -2441,101 +1929,57 @@ TPS_DEV void tile_lc_s(const ScanArgs& a, const TileConst& tc, const Lds& l, int
             run += sw[j];
         }
         }
-        ltot = run;
-#ifdef TPS_EMU
-        for (int j = 0; j < B; ++j) sw_keep[tid][j] = sw[j];
-        if (SWP) for (int j = 0; j < B / 2; ++j) swp_keep[tid][j] = swp[j];
-        tot_keep[tid] = ltot;
-#endif
+        TPS_AT(ltot) = run;
     }
     TPS_ISA_MARK(MK + 3);                         // 3: lane scan, S_w out, prefixes (and the lanes' own candidates)
     if constexpr (CD > 0) {
         // a chain somewhere in the tile: the windows give back what the chains' skipped occurrences added -- the prefix sum of
         // the difference array, lane-contiguous like the windows themselves
-#ifdef TPS_EMU
-        const bool tile_chain = lane_chain != 0;
-        if (tile_chain) {
-            ++emu_counter(5);
-            uint32_t acc = 0;
-            for (int t = 0; t < NT; ++t) {
-                uint32_t tot = 0;
-                for (int j = 0; j < B; ++j) { acc += l.row[t * (B + 1) + j]; sw_keep[t][j] += acc; tot += sw_keep[t][j]; }
-                tot_keep[t] = tot;
-            }
-        } else {
-            ++emu_counter(6);
-        }
-#else
         const bool tile_chain = lane_chain != 0;          // (uniform)
         if (tile_chain) {
-            uint32_t pd[B], dt = 0;
+            TPS_EMU_COUNT(5);
+            LaneArr<uint32_t, B> pd;
+            Lane<uint32_t> dt(0);
             TPS_PHASE {
                 const uint32_t* pr = l.row + tid * (B + 1);
                 TPS_UNROLL
-                for (int j = 0; j < B; ++j) { dt += pr[j]; pd[j] = dt; }
+                for (int j = 0; j < B; ++j) { TPS_AT(dt) += pr[j]; TPS_AT(pd)[j] = TPS_AT(dt); }
             }
-            uint32_t inc = dt;
-            inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x111, 0xf, 0xf, false);   // row_shr:1
-            inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x112, 0xf, 0xf, false);   // row_shr:2
-            inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x114, 0xf, 0xf, false);   // row_shr:4
-            inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x118, 0xf, 0xf, false);   // row_shr:8
-            inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x142, 0xa, 0xf, false);   // row_bcast:15 -> rows 1, 3
-            inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x143, 0xc, 0xf, false);   // row_bcast:31 -> rows 2, 3
-            const uint32_t dbase = inc - dt;
-            uint32_t run = 0;
-            TPS_UNROLL
-            for (int j = 0; j < B; ++j) { sw[j] += dbase + pd[j]; run += sw[j]; }
-            ltot = run;
+            const Lane<uint32_t> dbase = wave_excl_sum(dt);
+            TPS_LANES {
+                uint32_t run = 0;
+                TPS_UNROLL
+                for (int j = 0; j < B; ++j) { TPS_AT(sw_)[j] += TPS_AT(dbase) + TPS_AT(pd)[j]; run += TPS_AT(sw_)[j]; }
+                TPS_AT(ltot) = run;
+            }
+        } else {
+            TPS_EMU_COUNT(6);
         }
-#endif
     }
     // exclusive scan of the lane totals over the wave (lanes past the tile's last window add garbage behind every valid window)
-    uint32_t lexc = 0;
-#ifdef TPS_EMU
-    uint32_t exc_keep[NT];
-    { uint32_t acc = 0; for (int t = 0; t < NT; ++t) { exc_keep[t] = acc; acc += tot_keep[t]; } }
-#else
-    {
-        uint32_t inc = ltot;
-        inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x111, 0xf, 0xf, false);   // row_shr:1
-        inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x112, 0xf, 0xf, false);   // row_shr:2
-        inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x114, 0xf, 0xf, false);   // row_shr:4
-        inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x118, 0xf, 0xf, false);   // row_shr:8
-        inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x142, 0xa, 0xf, false);   // row_bcast:15 -> rows 1, 3
-        inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x143, 0xc, 0xf, false);   // row_bcast:31 -> rows 2, 3
-        lexc = inc - ltot;
-    }
-#endif
+    const Lane<uint32_t> lexc = wave_excl_sum(ltot);
     // (round 6) the sums-only tiles with absolute 32-bit candidate sums off chip: every lane stores its own candidates' left
     // sums right behind its prefixes -- no candidate-strided pass over row[] (the lc16 and LDS-Lc layouts, jump < 4 and the
     // chain-corrected / 16-bit-table tiles keep that pass)
     bool lane_cands = false;
     if constexpr (CD == 0 && !M16) lane_cands = tc.lc_g != 0ull && !tc.lc16 && tc.jump >= 4u;     // (uniform)
     TPS_PHASE {
-#ifdef TPS_EMU
-        for (int j = 0; j < B; ++j) sw[j] = sw_keep[tid][j];
-        if (SWP) for (int j = 0; j < B / 2; ++j) swp[j] = swp_keep[tid][j];
-        lexc = exc_keep[tid];
-#endif
         const int lane = tid;
-#ifndef TPS_NO_SW_STORE                               /* (diagnostic builds only: what do the S_w stores cost?) */
-        if constexpr (SWP) g_store_sw8p(tc.sw16 + w0, lane, nw_tile, swp);
+        const uint32_t* const sw = TPS_AT(sw_);
+        if constexpr (SWP) g_store_sw8p(tc.sw16 + w0, lane, nw_tile, TPS_AT(swp_));
         else g_store_sw8(tc.sw16 + w0, lane, nw_tile, sw);
-#endif
         // what the candidate phase reads: every window's exclusive prefix inside its LANE (padded layout) and every lane's
         // exclusive prefix inside the tile
         uint32_t* pr = l.row + lane * (B + 1);
         uint32_t run = 0;
         TPS_UNROLL
         for (int j = 0; j < B; ++j) { pr[j] = run; run += sw[j]; }
-        xt_at(lane) = lexc;
+        xt_at(lane) = TPS_AT(lexc);
         if (lane_cands) {
-#ifdef TPS_EMU
-            if (tid == 0) ++emu_counter(7);
-#endif
+            if (tid == 0) TPS_EMU_COUNT(7);
             // (round 6) the change-point candidates among the lane's own windows, read back from its own row (no barrier): the
             // first is window f = c jump - (w0 + 8 lane) of the lane, the second f + jump; jump >= 4 leaves no room for a third
-            const uint32_t carry = (uint32_t)s_total + lexc;
+            const uint32_t carry = (uint32_t)s_total + TPS_AT(lexc);
             const uint32_t wl = (uint32_t)(lane * B), wa = (uint32_t)w0 + wl;
             const uint32_t c = mulhi32(wa + tc.jump - 1u, tc.jump_magic);     // (div_jump without its jump = 1 case)
             const uint32_t f = c * tc.jump - wa;
@@ -2680,14 +2124,17 @@ TPS_DEV bool tile_pp_s(const ScanArgs& a, const TileConst& tc, const Lds& l, int
         for (int i = 0; i < DH; ++i) cv = (pos - (delta - DH) == i) ? cold[i] : cv;
         return w0 != 0 && ((cv >> (2 * fidx)) & 1u) != 0;
     };
-#ifdef TPS_EMU
-    uint32_t keep[NT][2 * B + 3];
-    if (CD == 0) ++emu_counter(0);
-#endif
-    uint32_t ve[B], vo[B], chm = 0, chw = 0, unc = 0;
-    uint32_t chain_any = 0;                       // CD: (field at p) & (field at p + CD), OR over the lane's positions
+    if (CD == 0) TPS_EMU_COUNT(0);
+    // what a lane keeps from phase 1: V[b] (nibbles, even / odd patterns), the blocks whose start-skip chain goes on (chm) and their
+    // fields (chw), unc = its state before its first position is not known
+    LaneArr<uint32_t, B> ve_, vo_;
+    Lane<uint32_t> chm_(0), chw_(0), unc_(0);
+    Lane<uint32_t> chain_any_(0);                 // CD: (field at p) & (field at p + CD), OR over the lane's positions
     TPS_PHASE {
         const int span = tid;
+        uint32_t* const ve = TPS_AT(ve_);
+        uint32_t* const vo = TPS_AT(vo_);
+        uint32_t &chm = TPS_AT(chm_), &chw = TPS_AT(chw_), &unc = TPS_AT(unc_), &chain_any = TPS_AT(chain_any_);
         const int p0 = delta + span * POS;        // >= 16
         const int bo = 2 * (p0 - LBK) - LS;       // the lane's registers start LBK positions before its first one (p0 >= 64)
         const uint32_t sh2 = (uint32_t)(bo & 31);
@@ -2833,56 +2280,41 @@ TPS_DEV bool tile_pp_s(const ScanArgs& a, const TileConst& tc, const Lds& l, int
         TPS_PIN_V(chm); TPS_PIN_V(chw); TPS_PIN_V(unc);
         TPS_UNROLL
         for (int i = 0; i < B; ++i) { TPS_PIN_V(ve[i]); TPS_PIN_V(vo[i]); }
-#ifdef TPS_EMU
-        for (int i = 0; i < B; ++i) { keep[tid][i] = ve[i]; keep[tid][B + i] = vo[i]; }
-        keep[tid][2 * B] = chm; keep[tid][2 * B + 1] = unc; keep[tid][2 * B + 2] = chw;
-        chm = 0; unc = 0; chw = 0;
-#endif
     }
     TPS_SYNC();
     TPS_PP_STAMP(6);
     if constexpr (CD > 0) {
-#ifdef TPS_EMU
-        const bool chained = chain_any != 0;      // (the emulation's phase loop has OR-ed every lane into the one variable)
-#else
-        const bool chained = __builtin_amdgcn_ballot_w64(chain_any != 0) != 0;
-#endif
+        Lane<bool> has_chain;
+        TPS_LANES { TPS_AT(has_chain) = TPS_AT(chain_any_) != 0; }
+        const bool chained = wave_ballot(has_chain) != 0;
         if (chained) return true;
-#ifdef TPS_EMU
-        ++emu_counter(0);
-        ++emu_counter(7);
-#endif
+        TPS_EMU_COUNT(0);
+        TPS_EMU_COUNT(7);
     }
     // lanes whose look-back could not fix their state: every window that touches one of them is recounted
     uint64_t unc_mask = 0;
     if (D > 0) {
-#ifdef TPS_EMU
-        for (int t = 0; t < NT; ++t) unc_mask |= (uint64_t)(keep[t][2 * B + 1] != 0) << t;
-        emu_counter(2) += __builtin_popcountll(unc_mask);
-#else
-        unc_mask = __builtin_amdgcn_ballot_w64(unc != 0);
-#endif
+        Lane<bool> is_unc;
+        TPS_LANES { TPS_AT(is_unc) = TPS_AT(unc_) != 0; }
+        unc_mask = wave_ballot(is_unc);
+        TPS_EMU_COUNT_N(2, __builtin_popcountll(unc_mask));
     }
     const int rot = q & (B - 1), dl0 = q >> 3;
-#ifdef TPS_EMU
-    uint32_t sw_keep[NT][B];
-    uint32_t rows_keep[NT][B][4];
-#endif
-    uint32_t swv[B], rows[B][3], rx[B / 2], todo = 0;     // rx: bytes 12-13 of the rows (14 patterns), two rows per word
-#ifdef TPS_EMU
-    uint32_t todo_keep[NT];
-    for (int t = 0; t < NT; ++t) todo_keep[t] = 0;
-#endif
+    LaneArr<uint32_t, B> swv_;                    // the lane's window sums
+    LaneArr<uint32_t[3], B> rows_;                // ... and raw rows: word i = patterns 4 i .. 4 i + 3
+    LaneArr<uint32_t, B / 2> rx_;                 // rx: bytes 12-13 of the rows (14 patterns), two rows per word
+    Lane<uint32_t> todo_(0);
     // raw rows (P <= 14 bytes: plan_geometry) always leave through LDS, coalesced: rows of 4, 8 or 12 bytes packed and in
     // whole cache lines; the others padded to 16 bytes in LDS and copied out in 16-bit units (P even) or bytes (P odd)
     const bool staged = a.raw != nullptr && (pat.P & 3) == 0;
     const bool staged16 = a.raw != nullptr && (pat.P & 3) != 0;
     TPS_PHASE {
-#ifdef TPS_EMU
-        for (int i = 0; i < B; ++i) { ve[i] = keep[tid][i]; vo[i] = keep[tid][B + i]; }
-        chm = keep[tid][2 * B]; chw = keep[tid][2 * B + 2];
-#endif
         const int lane = tid;
+        const uint32_t* const ve = TPS_AT(ve_);
+        const uint32_t* const vo = TPS_AT(vo_);
+        uint32_t* const swv = TPS_AT(swv_);
+        uint32_t (*const rows)[3] = TPS_AT(rows_);
+        uint32_t* const rx = TPS_AT(rx_);
         bool redo_all = false;
         if (D > 0) redo_all = ((unc_mask >> lane) & ((2ull << (dl0 + 1)) - 1ull)) != 0;
         // the far-end words of the lane's 8 windows: one LDS round trip (windows past the tile read in-bounds garbage: their rows
@@ -2899,10 +2331,7 @@ TPS_DEV bool tile_pp_s(const ScanArgs& a, const TileConst& tc, const Lds& l, int
         if (D > 0) {
             // windows to repair after the fast pass: bits 0-7 recount (the lane's state before its first position is not
             // known), bits 8-15 chain parity
-            todo = redo_all ? 0xFFu : (chm << 8);
-#ifdef TPS_EMU
-            todo_keep[tid] = todo;
-#endif
+            TPS_AT(todo_) = redo_all ? 0xFFu : (TPS_AT(chm_) << 8);
         }
         const int nv = nw_tile - lane * B;         // windows of this lane inside the tile (<= 0: none)
         // NW byte words per row: the fields are laid out so that word i holds patterns 4 i .. 4 i + 3 (pp_field) -- a list of at
@@ -2956,10 +2385,6 @@ TPS_DEV bool tile_pp_s(const ScanArgs& a, const TileConst& tc, const Lds& l, int
                 for (int i = 0; i < 3; ++i) rows[j][i] = c[i];        // the row as it is: word i = patterns 4 i .. 4 i + 3
                 if (j & 1) rx[j >> 1] = pack_hi_lo(c[3] << 16, rx[j >> 1]);
                 else rx[j >> 1] = c[3] & 0xFFFFu;
-#ifdef TPS_EMU
-                sw_keep[tid][j] = swv[j];
-                for (int i = 0; i < 4; ++i) rows_keep[tid][j][i] = c[i];
-#endif
             }
         };
         if (pat.P <= 12) windows(IntC<3>{});
@@ -2968,42 +2393,34 @@ TPS_DEV bool tile_pp_s(const ScanArgs& a, const TileConst& tc, const Lds& l, int
     }
     TPS_SYNC();                                   // every END word has been read: both halves of END are free
     TPS_PP_STAMP(7);
-    bool rows_done = false;
-    if constexpr (TPS_RAW_M != 0) {
-        if (staged && a.raw_m == 2) {
-            // Strided scans (round 5): this scan runs at HALF the requested slide and only the even windows are wanted -- tiles start at
-            // even windows, so a lane keeps its rows 0, 2, 4, 6: 4 P contiguous bytes per lane in the requested slide's layout, all 64
-            // lanes in ONE pass through the (free) END area, copied out in 16-byte pieces like the full rows below.
-            rows_done = true;
-            const int pd = pat.P >> 2;            // dwords per row: 1, 2 or 3
-            uint32_t* buf = l.XPC;
-            uint32_t* gout = (uint32_t*)(a.raw + (a.raw_win_off[tc.rd] + (w0 >> 1)) * (int64_t)pat.P);
-            TPS_PHASE {
-                uint32_t* dst = buf + tid * 4 * pd;
-#ifdef TPS_EMU
-                for (int j = 0; j < B; ++j) for (int i = 0; i < 3; ++i) rows[j][i] = rows_keep[tid][j][i];
-#endif
+    if (staged && a.raw_m == 2) {
+        // Strided scans (round 5): this scan runs at HALF the requested slide and only the even windows are wanted -- tiles start at
+        // even windows, so a lane keeps its rows 0, 2, 4, 6: 4 P contiguous bytes per lane in the requested slide's layout, all 64
+        // lanes in ONE pass through the (free) END area, copied out in 16-byte pieces like the full rows below.
+        const int pd = pat.P >> 2;            // dwords per row: 1, 2 or 3
+        uint32_t* buf = l.XPC;
+        uint32_t* gout = (uint32_t*)(a.raw + (a.raw_win_off[tc.rd] + (w0 >> 1)) * (int64_t)pat.P);
+        TPS_PHASE {
+            uint32_t* dst = buf + tid * 4 * pd;
+            uint32_t (*const rows)[3] = TPS_AT(rows_);
+            TPS_UNROLL
+            for (int j = 0; j < 4; ++j) {
                 TPS_UNROLL
-                for (int j = 0; j < 4; ++j) {
-                    TPS_UNROLL
-                    for (int i = 0; i < 3; ++i)
-                        if (i < pd) dst[j * pd + i] = rows[2 * j][i];
-                }
+                for (int i = 0; i < 3; ++i)
+                    if (i < pd) dst[j * pd + i] = rows[2 * j][i];
             }
-            TPS_SYNC();
-            TPS_PHASE {
-                const int nvalid = ((nw_tile + 1) >> 1) * pd;       // dwords of the tile's even windows
-                const int npass = (nvalid + 4 * NT - 1) / (4 * NT);  // uniform
-                TPS_NOVEC
-                for (int it = 0; it < npass; ++it) {
-                    const int cdw = 4 * tid + it * 4 * NT;
-                    g_store16_clamped(gout, nvalid, cdw, *(const u32x4*)(buf + cdw));
-                }
-            }
-            TPS_SYNC();
         }
-    }
-    if (rows_done) {
+        TPS_SYNC();
+        TPS_PHASE {
+            const int nvalid = ((nw_tile + 1) >> 1) * pd;       // dwords of the tile's even windows
+            const int npass = (nvalid + 4 * NT - 1) / (4 * NT);  // uniform
+            TPS_NOVEC
+            for (int it = 0; it < npass; ++it) {
+                const int cdw = 4 * tid + it * 4 * NT;
+                g_store16_clamped(gout, nvalid, cdw, *(const u32x4*)(buf + cdw));
+            }
+        }
+        TPS_SYNC();
     } else if (staged) {
         // Raw rows leave through LDS: a lane's 8 rows are 8 P contiguous bytes in HBM, LPP lanes per pass mirror a
         // contiguous stretch of the output in the (now free) END / totals area, and all 64 lanes copy it out in
@@ -3018,9 +2435,7 @@ TPS_DEV bool tile_pp_s(const ScanArgs& a, const TileConst& tc, const Lds& l, int
             TPS_PHASE {
                 if (tid >= l0 && tid < l0 + LPP) {
                     uint32_t* dst = buf + (tid - l0) * B * pd;
-#ifdef TPS_EMU
-                    for (int j = 0; j < B; ++j) for (int i = 0; i < 3; ++i) rows[j][i] = rows_keep[tid][j][i];
-#endif
+                    uint32_t (*const rows)[3] = TPS_AT(rows_);
                     if (pd == 3) {
                         TPS_UNROLL
                         for (int g = 0; g < 6; ++g) {
@@ -3063,14 +2478,12 @@ TPS_DEV bool tile_pp_s(const ScanArgs& a, const TileConst& tc, const Lds& l, int
             TPS_PHASE {
                 if (tid >= l0 && tid < l0 + LPP) {
                     uint32_t* dst = buf + (tid - l0) * B * 4;
+                    uint32_t (*const rows)[3] = TPS_AT(rows_);
+                    const uint32_t* const rx = TPS_AT(rx_);
                     TPS_UNROLL
                     for (int j = 0; j < B; ++j) {
                         u32x4 t;
-#ifdef TPS_EMU
-                        t.x = rows_keep[tid][j][0]; t.y = rows_keep[tid][j][1]; t.z = rows_keep[tid][j][2]; t.w = rows_keep[tid][j][3] & 0xFFFFu;
-#else
                         t.x = rows[j][0]; t.y = rows[j][1]; t.z = rows[j][2]; t.w = (rx[j >> 1] >> (16 * (j & 1))) & 0xFFFFu;
-#endif
                         *(u32x4*)(dst + 4 * j) = t;
                     }
                 }
@@ -3109,12 +2522,7 @@ TPS_DEV bool tile_pp_s(const ScanArgs& a, const TileConst& tc, const Lds& l, int
     // S_w takes the place of END's odd half (the candidate phase and the repairs read it there)
     TPS_PHASE {
         TPS_UNROLL
-        for (int j = 0; j < B; ++j) {
-#ifdef TPS_EMU
-            swv[j] = sw_keep[tid][j];
-#endif
-            l.row[tid * (B + 1) + j] = swv[j];
-        }
+        for (int j = 0; j < B; ++j) l.row[tid * (B + 1) + j] = TPS_AT(swv_)[j];
         if constexpr (CD > 0) {
             // what a chained successor wants from this (chain-free) tile: no pick before its first position matters -- a pair
             // across that position would lie inside this tile -- and nothing is uncertain
@@ -3127,36 +2535,28 @@ TPS_DEV bool tile_pp_s(const ScanArgs& a, const TileConst& tc, const Lds& l, int
     TPS_SYNC();
     if (D > 0) {
         // Repairs (rare, lane-divergent): results are in memory by now -- S_w in row[] and HBM, raw rows in HBM.
-#ifndef TPS_EMU
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");      // this wave's own raw-row stores before its byte updates
-#endif
+        TPS_FENCE_WG();                               // this wave's own raw-row stores before its byte updates
         TPS_PHASE {
-#ifdef TPS_EMU
-            todo = todo_keep[tid];
-            chw = keep[tid][2 * B + 2];
-#endif
             const int lane = tid;
+            uint32_t todo = TPS_AT(todo_);
+            const uint32_t chw = TPS_AT(chw_);
             while (todo) {
                 const int bit = ffs0(todo);
                 todo &= todo - 1u;
                 const int j = bit & 7, wl = lane * B + j;
                 if (wl >= nw_tile) continue;
                 uint8_t* raw_row = a.raw ? a.raw + (out_base + w0 + wl) * (int64_t)pat.P : nullptr;
-                if (TPS_RAW_M != 0 && a.raw && a.raw_m == 2)      // strided scans: only the even windows have a row, in the requested slide's layout
+                if (a.raw && a.raw_m == 2)      // strided scans: only the even windows have a row, in the requested slide's layout
                     raw_row = ((w0 + wl) & 1) ? nullptr : a.raw + (a.raw_win_off[tc.rd] + ((w0 + wl) >> 1)) * (int64_t)pat.P;
                 uint32_t sw = l.row[lane * (B + 1) + j];
                 if (bit < 8) {
-#ifdef TPS_EMU
-                    ++emu_counter(1);
-#endif
+                    TPS_EMU_COUNT(1);
                     sw = window_exact(a, l, delta, wl, pat.all_mask, 0u, raw_row, true);
                 } else {
                     // The window starts on a canonically skipped occurrence x whose chain goes on: it picks x, x + 2D, ...
                     // = one more than canonical iff the chain has an odd number of elements from x (inside the window).
                     // The start skip was added; take it back for an even count.
-#ifdef TPS_EMU
-                    ++emu_counter(3);
-#endif
+                    TPS_EMU_COUNT(3);
                     // chw is the union over the lane's flagged blocks, so x's own place in its chain is walked too: n earlier
                     // links (odd = canonically skipped = a start skip of this window), m elements from x inside the window.
                     const int a0 = delta + wl * S;
@@ -3183,9 +2583,7 @@ TPS_DEV bool tile_pp_s(const ScanArgs& a, const TileConst& tc, const Lds& l, int
                         }
                     }
                     if (lost) {
-#ifdef TPS_EMU
-                        ++emu_counter(1);
-#endif
+                        TPS_EMU_COUNT(1);
                         sw = window_exact(a, l, delta, wl, pat.all_mask, 0u, raw_row, true);
                     }
                 }
@@ -3243,21 +2641,6 @@ TPS_DEV double score_f64(int64_t d, uint64_t den) {
 TPS_DEV double gain_from(int64_t d, uint64_t den, int n, int n_patterns) {
     double x = (double)d;
     return x * x / ((double)n * (double)den) / ((double)n_patterns * (double)n_patterns);
-}
-
-// max of a non-negative f64 (as its bit pattern) over the workgroup into *slot (LDS, pre-zeroed):
-// wave-level butterfly first so that only one LDS atomic per wave is issued.
-TPS_DEV void wg_max_bits(uint64_t bits, uint64_t* slot) {
-#ifndef TPS_EMU
-    TPS_UNROLL
-    for (int d = 32; d >= 1; d >>= 1) {
-        uint32_t lo = __shfl_xor((uint32_t)bits, d), hi = __shfl_xor((uint32_t)(bits >> 32), d);
-        uint64_t o = ((uint64_t)hi << 32) | lo;
-        bits = o > bits ? o : bits;
-    }
-    if ((threadIdx.x & 63) != 0) return;
-#endif
-    lds_max_u64(slot, bits);
 }
 
 // Exact tournament over all candidates (slow path), scratch xs (XS_DW dwords).  Called by the
@@ -3348,14 +2731,12 @@ TPS_DEV void binseg_wg(const ST* S, int n, int jump, int min_size, int n_pattern
     }
     TPS_SYNC();
     const uint64_t tot = wg_exclusive_scan(bs, NT, &misc[M_SCAN]);
-    // per-thread best and runner-up scores over its candidates; they stay in registers on the
-    // device and in bs-adjacent scratch (xs) in the emulation, where phases are separate loops
-#ifdef TPS_EMU
-    double* keep = (double*)xs;                   // 3 doubles per thread: best, second, (double)best_b
-#endif
-    double best = -1.0, second = -1.0;
-    int best_b = -1;
+    // per-thread best and runner-up scores over its candidates
+    Lane<double> best_(-1.0), second_(-1.0);
+    Lane<int> best_b_(-1);
     TPS_PHASE {
+        double &best = TPS_AT(best_), &second = TPS_AT(second_);
+        int& best_b = TPS_AT(best_b_);
         const int lo = tid * cl, hi = lo + cl < n ? lo + cl : n;
         uint64_t run = bs[tid];
         best = -1.0; second = -1.0; best_b = -1;
@@ -3380,15 +2761,11 @@ TPS_DEV void binseg_wg(const ST* S, int n, int jump, int min_size, int n_pattern
         uint64_t bits = 0;
         if (best >= 0.0) __builtin_memcpy(&bits, &best, 8);   // non-negative doubles order like integers
         wg_max_bits(bits, (uint64_t*)&misc[M_MAXSC]);
-#ifdef TPS_EMU
-        keep[3 * tid] = best; keep[3 * tid + 1] = second; keep[3 * tid + 2] = (double)best_b;
-#endif
     }
     TPS_SYNC();
     TPS_PHASE {
-#ifdef TPS_EMU
-        best = keep[3 * tid]; second = keep[3 * tid + 1]; best_b = (int)keep[3 * tid + 2];
-#endif
+        const double best = TPS_AT(best_), second = TPS_AT(second_);
+        const int best_b = TPS_AT(best_b_);
         double m;
         __builtin_memcpy(&m, &misc[M_MAXSC], 8);
         const double thr = m * (1.0 - 1e-14);
@@ -3418,17 +2795,14 @@ template <typename ST>
 TPS_DEV void binseg_from_lc(const ScanArgs& a, const Lds& l, uint64_t lc_g, const ST* S_global, int n, uint64_t tot, int jump,
                             int min_size, int n_patterns, uint32_t* misc, uint32_t* xs, int& bkp, double& gain, bool& tie) {
     const int ncand = (n - 1) / jump;              // candidates b = c*jump, 1 <= c <= ncand  (b < n)
-#ifdef TPS_EMU
-    double* keep = (double*)xs;
-#endif
     // Per lane: the best candidate as a FRACTION (num = D^2, den = b (n - b)); candidates are compared by
     // cross-multiplication, so the f64 division happens once per lane instead of once per candidate.
     // `amb` = another candidate of this lane lies within 1e-13 (relative) of the lane's best: if that
     // best is also the global one, float64 cannot be trusted to separate them -> exact path.
-    double best = -1.0;
-    int best_b = -1;
-    bool amb = false;
-    uint64_t bits = 0;
+    Lane<double> best_(-1.0);
+    Lane<int> best_b_(-1);
+    Lane<bool> amb_(false);
+    Lane<uint64_t> bits_(0);
     // admissible candidates: b = c * jump with b >= min_size and n - b >= min_size
     const int c_min = (min_size + jump - 1) / jump > 1 ? (min_size + jump - 1) / jump : 1;
     const int c_max = (n - min_size) / jump < ncand ? (n - min_size) / jump : ncand;
@@ -3440,37 +2814,32 @@ TPS_DEV void binseg_from_lc(const ScanArgs& a, const Lds& l, uint64_t lc_g, cons
     // candidate in single precision from the EXACT D (float64 fma, then rounded once), the wave maximum, and only
     // candidates within 1e-4 of it -- two orders of magnitude more than single precision can be off -- go through the
     // float64 fraction comparison below (41 instructions per candidate; the prefilter costs about a third of that).
-#ifndef TPS_PREFILTER_LEAN
-#define TPS_PREFILTER_LEAN 1      // (0: A/B builds with the round-6 prefilter -- float64 D, masked loads)
-#endif
     // Where n T < 2^31 (wave-uniform; config 2: n = 2 467, T of the order of 3e5) both products of D and D itself fit a signed
     // 32-bit integer: D is then computed exactly in integers -- b and T b advance by a uniform step from slot to slot -- and
     // v_cvt_f32_i32 rounds it to nearest-even exactly as the float64 fma's result is rounded by v_cvt_f32_f64: the same d32, bit
     // for bit, without two conversions to float64, a multiply and an fma per candidate.  Slots past c_max load candidate c_max
     // (an index clamp instead of a masked load with its zeroed register; their score is replaced by -1 as before).
-    const bool int_d = TPS_PREFILTER_LEAN != 0 && (double)tot * (double)n < 2147483648.0;
+    const bool int_d = (double)tot * (double)n < 2147483648.0;
     constexpr int LCV = 16;
     const bool prefilter = !a.lc16 && lc_g && exact53 && c_max - c_min < LCV * NT;
     int nslot = c_max >= c_min ? (c_max - c_min + NT) / NT : 0;          // candidate slots per lane that any lane uses
     TPS_PIN_S(nslot);
     auto tile_sum = [&](int c) { return l.Tc[(uint32_t)(((uint64_t)(uint32_t)(c * jump) * a.tw_magic) >> 32)]; };
     // per lane: its best single-precision score with that candidate's index and left sum, and its second-best score
-    float p_s1 = -1.0f, p_s2 = -1.0f, thr32 = -1.0f;
-    uint32_t p_lc = 0;
-    int p_c = -1;
+    Lane<float> p_s1_(-1.0f), p_s2_(-1.0f);
+    Lane<uint32_t> p_lc_(0);
+    Lane<int> p_c_(-1);
+    float thr32 = -1.0f;
     bool crowded = false;                          // some lane holds a second candidate within the prefilter's margin
-#ifdef TPS_EMU
-    static thread_local float ps1_keep[NT], ps2_keep[NT];
-    static thread_local uint32_t plc_keep[NT];
-    static thread_local int pc_keep[NT];
-    float emu_m32 = 0.0f;
-#endif
     TPS_ISA_REGION(5);
     if (prefilter) {
         // (one phase per variant, each with its own laundered lane id: written as two branches of one phase the slots' shared index
         // arithmetic and compares of all sixteen slots are hoisted in front of the branch, used or not)
         auto prefilter_phase = [&](auto lean_) {
         TPS_PHASE {
+            float &p_s1 = TPS_AT(p_s1_), &p_s2 = TPS_AT(p_s2_);
+            uint32_t& p_lc = TPS_AT(p_lc_);
+            int& p_c = TPS_AT(p_c_);
             p_s1 = -1.0f; p_s2 = -1.0f; p_lc = 0; p_c = -1;
             // four slots at a time behind ONE uniform test (nslot lives in an SGPR): slots no lane uses cost nothing;
             // the four loads of a group are requested before the first one is used
@@ -3500,11 +2869,7 @@ TPS_DEV void binseg_from_lc(const ScanArgs& a, const Lds& l, uint64_t lc_g, cons
                         d32 = (float)__builtin_fma(-totf, bf, nf * (double)lcv[i]);
                     }
                     const float den32 = (float)b * (float)(n - b);
-#ifdef TPS_EMU
-                    float s_ = d32 * d32 * (1.0f / den32);
-#else
-                    float s_ = d32 * d32 * __builtin_amdgcn_rcpf(den32);
-#endif
+                    float s_ = d32 * d32 * rcp_f32(den32);
                     s_ = c <= c_max ? s_ : -1.0f;
                     const bool gt = s_ > p_s1;                    // (an exact tie becomes the runner-up: conservative)
                     const float lose = gt ? p_s1 : s_;
@@ -3518,38 +2883,30 @@ TPS_DEV void binseg_from_lc(const ScanArgs& a, const Lds& l, uint64_t lc_g, cons
             if (nslot > 4) group(1);
             if (nslot > 8) group(2);
             if (nslot > 12) group(3);
-#ifdef TPS_EMU
-            ps1_keep[tid] = p_s1; ps2_keep[tid] = p_s2; plc_keep[tid] = p_lc; pc_keep[tid] = p_c;
-            emu_m32 = p_s1 > emu_m32 ? p_s1 : emu_m32;
-#endif
         }
         };
         if (int_d) prefilter_phase(IntC<1>());
         else prefilter_phase(IntC<0>());
         float m32;
-#ifdef TPS_EMU
-        m32 = emu_m32;
-#else
         {
-            const float nn = p_s1 > 0.0f ? p_s1 : 0.0f;
-            uint32_t mb;
-            __builtin_memcpy(&mb, &nn, 4);          // non-negative floats order like integers
-            mb = wave_max_u32(mb);
+            Lane<uint32_t> key;
+            TPS_LANES {
+                const float nn = TPS_AT(p_s1_) > 0.0f ? TPS_AT(p_s1_) : 0.0f;
+                __builtin_memcpy(&TPS_AT(key), &nn, 4);      // non-negative floats order like integers
+            }
+            const uint32_t mb = wave_max_u32(key);
             __builtin_memcpy(&m32, &mb, 4);
         }
-#endif
         thr32 = m32 * (1.0f - 1e-4f);
-#ifdef TPS_EMU
-        for (int t = 0; t < NT; ++t) crowded = crowded || (ps2_keep[t] >= thr32 && ps2_keep[t] >= 0.0f);
-#else
-        crowded = __builtin_amdgcn_ballot_w64(p_s2 >= thr32 && p_s2 >= 0.0f) != 0;
-#endif
+        Lane<bool> close2;
+        TPS_LANES { TPS_AT(close2) = TPS_AT(p_s2_) >= thr32 && TPS_AT(p_s2_) >= 0.0f; }
+        crowded = wave_ballot(close2) != 0;
     }
     TPS_ISA_REGION(6);
     TPS_PHASE {
         double bn = -1.0, bd = 1.0;
-        best_b = -1;
-        amb = false;
+        int best_b = -1;
+        bool amb = false;
         auto offer = [&](int c, uint32_t lc) {
             const int b = c * jump;
             const double bf = (double)b;
@@ -3565,10 +2922,7 @@ TPS_DEV void binseg_from_lc(const ScanArgs& a, const Lds& l, uint64_t lc_g, cons
             if (take) { bn = num; bd = den; best_b = b; }
         };
         if (prefilter) {
-#ifdef TPS_EMU
-            p_s1 = ps1_keep[tid]; p_lc = plc_keep[tid]; p_c = pc_keep[tid];
-#endif
-            if (p_c >= 0 && p_s1 >= thr32) offer(p_c, p_lc);
+            if (TPS_AT(p_c_) >= 0 && TPS_AT(p_s1_) >= thr32) offer(TPS_AT(p_c_), TPS_AT(p_lc_));
         } else if (a.lc16 && lc_g && c_max - c_min < LCV * NT) {
             // off-chip 16-bit sums: all of the lane's values are requested before the first one is used
             uint32_t lcv[LCV];
@@ -3591,46 +2945,44 @@ TPS_DEV void binseg_from_lc(const ScanArgs& a, const Lds& l, uint64_t lc_g, cons
                 offer(c, lc);
             }
         }
-        best = best_b >= 0 ? bn / bd : -1.0;
-        bits = 0;
+        const double best = best_b >= 0 ? bn / bd : -1.0;
+        uint64_t bits = 0;
         if (best >= 0.0) __builtin_memcpy(&bits, &best, 8);   // non-negative doubles order like integers
-#ifdef TPS_EMU
-        keep[3 * tid] = best; keep[3 * tid + 1] = amb ? 1.0 : 0.0; keep[3 * tid + 2] = (double)best_b;
-#endif
+        TPS_AT(best_) = best; TPS_AT(best_b_) = best_b; TPS_AT(amb_) = amb; TPS_AT(bits_) = bits;
     }
     // wave-wide: the best score, how many candidates float64 cannot separate from it, the largest b holding it
     double m;
     uint32_t ntie = 0;
     int32_t bestb = -1;
-#ifdef TPS_EMU
-    m = 0.0;
-    for (int t = 0; t < NT; ++t) if (keep[3 * t] > m) m = keep[3 * t];
-    for (int t = 0; t < NT; ++t) {
-        const double bt = keep[3 * t];
-        if (bt >= m * (1.0 - 1e-14) && bt >= 0.0) ntie += keep[3 * t + 1] != 0.0 ? 2u : 1u;
-        if (bt == m && (int)keep[3 * t + 2] >= 0 && (int)keep[3 * t + 2] > bestb) bestb = (int)keep[3 * t + 2];
-    }
-#else
     {
-        const uint32_t hi = (uint32_t)(bits >> 32);
-        const uint32_t mh = wave_max_u32(hi);
-        const uint32_t ml = wave_max_u32(hi == mh ? (uint32_t)bits : 0u);
+        Lane<uint32_t> key;
+        TPS_LANES { TPS_AT(key) = (uint32_t)(TPS_AT(bits_) >> 32); }
+        const uint32_t mh = wave_max_u32(key);
+        TPS_LANES { TPS_AT(key) = (uint32_t)(TPS_AT(bits_) >> 32) == mh ? (uint32_t)TPS_AT(bits_) : 0u; }
+        const uint32_t ml = wave_max_u32(key);
         const uint64_t mbits = ((uint64_t)mh << 32) | ml;
         __builtin_memcpy(&m, &mbits, 8);
-        const bool n1 = best >= m * (1.0 - 1e-14) && best >= 0.0;
-        ntie = (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(n1)) +
-               (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(n1 && amb));
-        bestb = (int32_t)wave_max_u32((best == m && best_b >= 0) ? (uint32_t)best_b + 1u : 0u) - 1;
+        Lane<bool> n1, n1_amb;
+        TPS_LANES {
+            const double best = TPS_AT(best_);
+            const bool amb = TPS_AT(amb_), near = best >= m * (1.0 - 1e-14) && best >= 0.0;
+            TPS_AT(n1) = near;
+            TPS_AT(n1_amb) = near && amb;
+        }
+        ntie = (uint32_t)__builtin_popcountll(wave_ballot(n1)) + (uint32_t)__builtin_popcountll(wave_ballot(n1_amb));
+        TPS_LANES {
+            const double best = TPS_AT(best_);
+            const int best_b = TPS_AT(best_b_);
+            TPS_AT(key) = (best == m && best_b >= 0) ? (uint32_t)best_b + 1u : 0u;
+        }
+        bestb = (int32_t)wave_max_u32(key) - 1;
     }
-#endif
     (void)misc;
     TPS_ISA_REGION(7);
     if (crowded) ntie = 2u;                        // the prefilter kept one candidate per lane: a second one that close needs the full comparison
     tie = ntie > 1u;
     if (ntie > 1u) {                               // float noise cannot separate them: exact integers decide
-#ifdef TPS_EMU
-        ++emu_counter(4);
-#endif
+        TPS_EMU_COUNT(4);
         Cand ex = binseg_exact_wg(S_global, n, jump, min_size, xs);
         bkp = ex.b;
         gain = ex.b < 0 ? 0.0 : gain_from((int64_t)ex.d, ex.den, n, n_patterns);
@@ -3652,11 +3004,9 @@ TPS_DEV void binseg_from_lc(const ScanArgs& a, const Lds& l, uint64_t lc_g, cons
 template <int SV, bool SO, bool PAIR = false, bool RAW = true, bool FULL = tile_full_default(SV), int DCLASS = 0>
 TPS_DEV void scan_read(const ScanArgs& a, int64_t r, uint32_t* lds_base, uint32_t* lut) {
     constexpr bool M16K = SV != 0 && SO && !RAW;       // sums-only kernels of self-overlap tables: 16-bit table, XT aliased (lut16 / xt_alias)
-    // (XM = 2 also for the default kernels: every tile of theirs is a tile_lc_s<.., CD = 0>, which keeps XF / XT in the pad words too)
-    constexpr int XM = (SV != 0 && (RAW || ((M16K || !SO) && TPS_LC_TILE != 0 && TPS_XPAD != 0))) ? 2 : 0;
     constexpr bool F16K = SV != 0 && SO && RAW && DCLASS == 3;     // raw rows of a big self-overlap table: 16-bit field-index table (_s*sorh)
     constexpr bool P16K = SV != 0 && !SO && !RAW && PAIR && DCLASS == 4;      // pair-table kernels of k = 5 tables: 16-bit pair + single table (_s*q)
-    Lds l_ = SV ? carve_fused<SV ? SV : 5, FULL, XM>(lds_base, lut, a) : carve(lds_base, lut, a);
+    Lds l_ = SV ? carve_fused<SV ? SV : 5, FULL>(lds_base, lut, a) : carve(lds_base, lut, a);
     if constexpr (P16K) l_.lshift = LUT_M16;
     const Lds l = l_;
     const PatInfo& pat = a.pat;
@@ -3720,7 +3070,7 @@ TPS_DEV void scan_read(const ScanArgs& a, int64_t r, uint32_t* lds_base, uint32_
         if constexpr (SV != 0) packed1 = clean && trc_packed_ok(a, st_s.n - pat.k + 1);
         uint32_t ks = 0, ke = 0;
         bool decided = false;
-#if !defined(TPS_EMU) && !defined(TPS_NO_DECIDE_FAST)           /* (TPS_NO_DECIDE_FAST: A/B builds) */
+#ifndef TPS_EMU              /* (trc_decide_packed is device-only: DESIGN.md, "One kernel text") */
         if constexpr (SV != 0 && !SO && !RAW) {
             if (packed1) {
                 trc_decide_packed<P16K ? 2 : 0>(a, l, st_s, st_e, r, ks, ke);
@@ -3853,15 +3203,11 @@ TPS_DEV void scan_read(const ScanArgs& a, int64_t r, uint32_t* lds_base, uint32_
             // Software prefetch: the 16-byte load(s) of the NEXT tile are issued right after the current tile has been
             // copied into LDS and complete while it is being scanned, so a wave pays the HBM latency once per read
             // instead of once per tile.  One quad (64 bases) per lane covers a tile up to slide 7.
-            u32x4 pf[PF];
-            u32x2 pv[PF];
+            LaneArr<u32x4, PF> pf_;
+            LaneArr<u32x2, PF> pv_;
             // (ORIENT kernels: the invalid words are loaded for the staged quads of reads that have any, and the store below reads them
             // for exactly those -- no zeroing per tile)
-            for (int u = 0; u < PF; ++u) pv[u].x = pv[u].y = 0;
-#ifdef TPS_EMU
-            u32x4 pf_keep[NT][PF];
-            u32x2 pv_keep[NT][PF];
-#endif
+            TPS_LANES { for (int u = 0; u < PF; ++u) TPS_AT(pv_)[u].x = TPS_AT(pv_)[u].y = 0; }
             // The lane's byte offset into a tile's quads depends on the read's orientation alone: one VGPR per read, made opaque so
             // that it is neither recomputed per tile (a shift, a subtract and a select in every prefetch) nor folded back into it.
             // Only in the default kernels with one quad per lane and tile (no self-overlap, no raw rows, slide <= 7).  The raw-row
@@ -3870,31 +3216,26 @@ TPS_DEV void scan_read(const ScanArgs& a, int64_t r, uint32_t* lds_base, uint32_
             // per lane (slide 8 and up) the second set of loop-carried registers made `_s8so` / `_s8sol` spill.  They keep round 6's code.
             const bool rv = tail == 1;
             constexpr bool ORIENT = !RAW && !SO && PF == 1;
-#ifdef TPS_EMU
-#define TPS_PF_OFF(tid_) stage_lane_off(rv, tid_)
-#else
-            uint32_t pf_off = 0;
+            Lane<uint32_t> pf_off(0);
             if constexpr (ORIENT) {
-                pf_off = stage_lane_off(rv, (int)(threadIdx.x & 63u));
-                TPS_PIN_V(pf_off);
+                TPS_LANES {
+                    TPS_AT(pf_off) = stage_lane_off(rv, tid);
+                    TPS_PIN_V(TPS_AT(pf_off));
+                }
             }
-#define TPS_PF_OFF(tid_) (ORIENT ? pf_off : stage_lane_off(rv, tid_))
-#endif
-            auto pf_load = [&](const Stage& stn, int tid_) {
+            auto pf_load = [&](const Stage& stn, int tid) {
+                u32x4* const pf = TPS_AT(pf_);
+                u32x2* const pv = TPS_AT(pv_);
                 TPS_UNROLL
                 for (int u = 0; u < PF; ++u) {
-                    const int c = tid_ + u * NT;
+                    const int c = tid + u * NT;
                     pf[u].x = pf[u].y = pf[u].z = pf[u].w = 0;
                     if constexpr (!ORIENT) pv[u].x = pv[u].y = 0;
                     if (c < stn.nq) {
-                        const uint32_t off = TPS_PF_OFF(tid_);
+                        const uint32_t off = ORIENT ? TPS_AT(pf_off) : stage_lane_off(rv, tid);
                         pf[u] = load16(stage_base(stn, u * NT) + off);
                         if (has_inv) pv[u] = load8(stage_inv_base(stn, u * NT) + (off >> 1));
                     }
-#ifdef TPS_EMU
-                    pf_keep[tid_][u] = pf[u];
-                    pv_keep[tid_][u] = pv[u];
-#endif
                 }
             };
             TPS_ISA_REGION(1);
@@ -3913,13 +3254,11 @@ TPS_DEV void scan_read(const ScanArgs& a, int64_t r, uint32_t* lds_base, uint32_
                 // by the last phase of every tile -- no extra phase and barrier per tile for that)
                 // (the read's orientation is wave-uniform: a forward tail's quads go to LDS as they were loaded)
                 TPS_PHASE {
+                    const u32x4* const pf = TPS_AT(pf_);
+                    const u32x2* const pv = TPS_AT(pv_);
                     TPS_UNROLL
                     for (int u = 0; u < PF; ++u) {
                         const int c = tid + u * NT;
-#ifdef TPS_EMU
-                        pf[u] = pf_keep[tid][u];
-                        pv[u] = pv_keep[tid][u];
-#endif
                         if (c < t_::NQ) {              // every quad of the tile buffer is written (zeros past the staged range)
                             if constexpr (!ORIENT) lds_store16(l.seq2 + SEQ_LEAD + 4 * c, stage_orient(st, pf[u]));
                             else if (rv) lds_store16(l.seq2 + SEQ_LEAD + 4 * c, stage_reversed(pf[u]));
@@ -3962,7 +3301,7 @@ TPS_DEV void scan_read(const ScanArgs& a, int64_t r, uint32_t* lds_base, uint32_
                             // default window: CCCTAA at k = 5 (period 4, r = 95 % S; _s*sor) and k = 6 (period 5, r = 94 % S; _s*sorh) -- takes
                             // instantiations with r as a compile-time constant; every other period / window the run-time ones)
                             constexpr int HD = F16K ? 5 : 4, HR = (F16K ? 94 : 95) % SP;
-                            const bool home = TPS_PP_RPT != 0 && a.pp_d == HD && tc.r == HR;
+                            const bool home = a.pp_d == HD && tc.r == HR;
                             bool chained = true;
                             if (a.so_fast && !pp_expect) {
                                 if (home) chained = tile_pp_s<SP, 0, HD, F16K, HR>(a, tc, l, fdelta, w0, tile, nw_tile, out_base, s_total);
@@ -3989,10 +3328,10 @@ TPS_DEV void scan_read(const ScanArgs& a, int64_t r, uint32_t* lds_base, uint32_
                             pp_expect = a.so_fast != 2 && (s_total - s_before) > (uint64_t)nw_tile * (uint64_t)(pat.P + 4);
                         } else {
                             constexpr int HR4 = 96 % SP;       // k = 4 at the default window
-                            if constexpr (PAIR && (HR4 & 1) == 0 && TPS_PP_PAIRF != 0) {
+                            if constexpr (PAIR && (HR4 & 1) == 0) {
                                 if (tc.r == HR4 && a.pair_n != 0) { tile_pp_s<SP, 0, 0, false, HR4, true>(a, tc, l, fdelta, w0, tile, nw_tile, out_base, s_total); continue; }
                             }
-                            if (TPS_PP_RPT != 0 && tc.r == HR4) tile_pp_s<SP, 0, 0, false, HR4>(a, tc, l, fdelta, w0, tile, nw_tile, out_base, s_total);
+                            if (tc.r == HR4) tile_pp_s<SP, 0, 0, false, HR4>(a, tc, l, fdelta, w0, tile, nw_tile, out_base, s_total);
                             else tile_pp_s<SP, 0>(a, tc, l, fdelta, w0, tile, nw_tile, out_base, s_total);
                         }
                         continue;
@@ -4022,19 +3361,18 @@ TPS_DEV void scan_read(const ScanArgs& a, int64_t r, uint32_t* lds_base, uint32_
                     }
                 }
                 constexpr int SF = SV ? SV : 1;
-                constexpr bool LC = TPS_LC_TILE != 0 && !SO && !RAW;     // the default kernels: lane-contiguous windows (tile_lc_s)
+                constexpr bool LC = !SO && !RAW;     // the default kernels: lane-contiguous windows (tile_lc_s)
                 if (uniform(l.misc[M_INVALID]) != 0) {
                     if constexpr (LC) tile_lc_s<SF, true, -1, false, false, 0, P16K>(a, tc, l, fdelta, w0, tile, nw_tile, out_base, s_total, r);
-                    else tile_fused_s<SF, SO, true, -1, false, RAW>(a, tc, l, fdelta, w0, tile, nw_tile, out_base, s_total, r);
+                    else tile_fused_s<SF, SO, true, -1, RAW>(a, tc, l, fdelta, w0, tile, nw_tile, out_base, s_total, r);
                 } else if constexpr (SO || RAW) {
                     // (these kernels reach the plain tile only as a fallback: one instantiation with r read at run time)
-                    // (the raw-row kernels' pair table holds FIELDS, for tile_pp_s only: their fallback tile looks positions up one by one)
-                    if (tc.r == 0) tile_fused_s<SF, SO, false, 0, PAIR && !RAW, RAW>(a, tc, l, fdelta, w0, tile, nw_tile, out_base, s_total, r);
-                    else tile_fused_s<SF, SO, false, -1, PAIR && !RAW, RAW>(a, tc, l, fdelta, w0, tile, nw_tile, out_base, s_total, r);
+                    // (the raw-row kernels' pair table holds FIELDS, for tile_pp_s only: the fallback tile looks positions up one by one)
+                    if (tc.r == 0) tile_fused_s<SF, SO, false, 0, RAW>(a, tc, l, fdelta, w0, tile, nw_tile, out_base, s_total, r);
+                    else tile_fused_s<SF, SO, false, -1, RAW>(a, tc, l, fdelta, w0, tile, nw_tile, out_base, s_total, r);
                 } else {
-#define TPS_TILE_RP(N) case N: if constexpr (N < SF) { if constexpr (LC) { if ((tc.q & 7) == 0) tile_lc_s<SF, false, (N < SF ? N : 0), PAIR, true, 0, P16K>(a, tc, l, fdelta, w0, tile, nw_tile, out_base, s_total, r); \
-                                                                          else tile_lc_s<SF, false, (N < SF ? N : 0), PAIR, false, 0, P16K>(a, tc, l, fdelta, w0, tile, nw_tile, out_base, s_total, r); } \
-                                                       else tile_fused_s<SF, SO, false, (N < SF ? N : 0), PAIR, RAW>(a, tc, l, fdelta, w0, tile, nw_tile, out_base, s_total, r); } break;
+#define TPS_TILE_RP(N) case N: if constexpr (N < SF) { if ((tc.q & 7) == 0) tile_lc_s<SF, false, (N < SF ? N : 0), PAIR, true, 0, P16K>(a, tc, l, fdelta, w0, tile, nw_tile, out_base, s_total, r); \
+                                                       else tile_lc_s<SF, false, (N < SF ? N : 0), PAIR, false, 0, P16K>(a, tc, l, fdelta, w0, tile, nw_tile, out_base, s_total, r); } break;
                     switch (tc.r) {
                         TPS_TILE_RP(0) TPS_TILE_RP(1) TPS_TILE_RP(2) TPS_TILE_RP(3) TPS_TILE_RP(4) TPS_TILE_RP(5) TPS_TILE_RP(6) TPS_TILE_RP(7)
                         TPS_TILE_RP(8) TPS_TILE_RP(9) TPS_TILE_RP(10) TPS_TILE_RP(11)
@@ -4044,7 +3382,6 @@ TPS_DEV void scan_read(const ScanArgs& a, int64_t r, uint32_t* lds_base, uint32_
                 }
                 if (w0 == 0) TPS_STAMP(8);
             }
-#undef TPS_PF_OFF
         }
     }
     res.n_win = n_win;
@@ -4054,11 +3391,7 @@ TPS_DEV void scan_read(const ScanArgs& a, int64_t r, uint32_t* lds_base, uint32_
         int bkp;
         double gain;
         bool tie = false;
-#ifndef TPS_EMU
-        // same wave, same CU: workgroup scope orders this wave's S_w / off-chip candidate-sum stores before its own
-        // loads (an agent-scope fence writes the L2 back: measured 5x slower)
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-#endif
+        TPS_FENCE_WG();                            // this wave's S_w / off-chip candidate-sum stores before its own loads
         const uint64_t lc_g = a.lc_global ? (uint64_t)(uintptr_t)(a.lc_scratch + r * (int64_t)a.lc_stride) : 0ull;
         if constexpr (SV != 0)
             binseg_from_lc(a, l, lc_g, (const uint16_t*)(a.sums16 + (a.win_off16 ? a.win_off16[r] : 0)), n_win, s_total, prm.jump, prm.min_size, pat.P,
@@ -4178,9 +3511,7 @@ TPS_DEV void stride_read(const StrideArgs& a, int64_t r, uint32_t* smem, uint16_
         if (s16) {
             binseg_wg((const uint16_t*)s16, n, a.jump, a.min_size, a.n_patterns, bs, misc, xs, bkp, gain, tie);
         } else {
-#ifndef TPS_EMU
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");      // this wave's own stores above, read back below
-#endif
+            TPS_FENCE_WG();                        // this wave's own stores above, read back below
             binseg_wg(a.sums + lo, n, a.jump, a.min_size, a.n_patterns, bs, misc, xs, bkp, gain, tie);
         }
         res.bkp = bkp;
@@ -4205,11 +3536,6 @@ constexpr int FOLLOW_MAX_SPAN = 4096;                      // hi - lo
 constexpr int FOLLOW_SEQ_DW = 4 * ((63 + FOLLOW_MAX_SPAN + 63) / 64) + 8;
 constexpr int FOLLOW_PW = FOLLOW_MAX_SPAN / 32;
 constexpr int FOLLOW_LDS_DW = FOLLOW_SEQ_DW + FOLLOW_SEQ_DW / 2 + 4 + 15 * FOLLOW_PW + 4;   // seq2, val, flag, occurrence / pick bits
-#ifdef TPS_EMU
-TPS_DEV void hist_add(unsigned long long* p) { *p += 1ull; }
-#else
-TPS_DEV void hist_add(unsigned long long* p) { atomicAdd(p, 1ull); }
-#endif
 TPS_DEV void followers_read(const FollowArgs& a, int64_t r, uint32_t* lds) {
     uint32_t* seq2 = lds;
     uint16_t* val = (uint16_t*)(lds + FOLLOW_SEQ_DW);

@@ -63,23 +63,14 @@
             tps::scan_read<SV, SO, PAIR, RAW, FULL, DCLASS>(a, r, slice, lut);                             \
         }                                                                                                  \
     }
-#ifndef TPS_R_MINW
 #define TPS_R_MINW 5      // waves per SIMD the raw-row kernels of tables without self-overlap are compiled for: 96 VGPRs with 7 spilled and 32 B
-#endif                    // of scratch instead of 106 and none -- k = 4 with raw rows 171.2 -> 165.8 us (143.4 against 149.6 per batch on two streams);
+                          // of scratch instead of 106 and none -- k = 4 with raw rows 171.2 -> 165.8 us (143.4 against 149.6 per batch on two streams);
                           // the fifth wave is worth more than the spills cost, as in the self-overlap raw kernels.  Slide 8 would spill 64: it stays at 3
-#ifndef TPS_S8SOR_MINW
 #define TPS_S8SOR_MINW 4  // ... of the slide-8 self-overlap raw-row kernel: 113 VGPRs; compiled for 5 it spills 94 VGPRs to 68 B of scratch (k = 5 at slide 8: 168.6 -> 163.8 us)
-#endif
-#ifndef TPS_SOR_MINW
 #define TPS_SOR_MINW 5
-#endif
-#ifndef TPS_SOL_MINW
 #define TPS_SOL_MINW 6     // waves per SIMD the sums kernels of self-overlap periods 2 .. 4 (k = 5) are compiled for: 80 VGPRs without a spill, and their LDS (25 472 B per workgroup) allows the sixth: k = 5 sums 106.0 -> 102.0 us, 97 -> 90 per batch on two streams
-#endif
-#ifndef TPS_SO_MINW
 #define TPS_SO_MINW 6     // waves per SIMD the sums-only self-overlap kernels are compiled for (round 5: 80 VGPRs, no VGPR spill; with the lane totals in the
                           // pad words a k = 6 wave slice is 5 536 B: 8 192 + 8 x 5 536 = 52 480 B -> three 8-wave workgroups = 24 waves per CU instead of 20)
-#endif
 #define TPS_SCAN_KERNEL(NAME, SV, SO, PAIR, RAW, MINW) TPS_SCAN_KERNEL_F(NAME, SV, SO, PAIR, RAW, MINW, tps::tile_full_default(SV), 0)
 #define TPS_SCAN_KERNEL_D(NAME, SV, SO, PAIR, RAW, MINW, DCLASS) TPS_SCAN_KERNEL_F(NAME, SV, SO, PAIR, RAW, MINW, tps::tile_full_default(SV), DCLASS)
 

@@ -20,7 +20,7 @@
 //     stores one byte -- a row is one contiguous piece of HBM;
 //   * the change point is binseg_wg on the stored sums, in the same launch (the standalone kernel's arithmetic, TPS_RES_TIE alike).
 //
-// Compiles under TPS_EMU like tps_device.h (tests/emu/emu_wide.cpp).
+// Written against tps_wave.h like tps_device.h: the same text compiles under TPS_EMU (tests/emu/emu_wide.cpp).
 #pragma once
 #include "tps_device.h"
 
@@ -100,17 +100,6 @@ TPS_DEV WideLds wide_carve(uint32_t* base, const uint32_t* img, const WideArgs& 
     l.pg = (const uint8_t*)(img + WIDE_TAB_DW + WIDE_GM_DW);
     return l;
 }
-
-#ifdef TPS_EMU
-TPS_DEV u32x4 lds_load16(const uint32_t* p) { u32x4 v; v.x = p[0]; v.y = p[1]; v.z = p[2]; v.w = p[3]; return v; }
-TPS_DEV void g8_store(uint64_t base, uint32_t i, uint32_t v) { ((uint8_t*)(uintptr_t)base)[i] = (uint8_t)v; }
-#else
-TPS_DEV u32x4 lds_load16(const uint32_t* p) { return *(const u32x4*)p; }          // ds_read_b128 (p is 16-byte aligned)
-TPS_DEV void g8_store(uint64_t base, uint32_t i, uint32_t v) {
-    typedef __attribute__((address_space(1))) uint8_t* gp_t;
-    ((gp_t)(uintptr_t)base)[i] = (uint8_t)v;
-}
-#endif
 
 // group + 1 of the k-mer whose code is the low 2k bits of hi:lo, 0 if the list does not hold it
 TPS_DEV uint32_t wide_gid1(const WidePat& pat, const uint32_t* tab, uint32_t lo, uint32_t hi) {
@@ -364,10 +353,7 @@ TPS_DEV void wide_read(const WideArgs& a, int64_t r, uint32_t* lds_base, const u
         int bkp;
         double gain;
         bool tie = false;
-#ifndef TPS_EMU
-        // same wave, same CU: workgroup scope orders this wave's S_w stores before its own loads
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-#endif
+        TPS_FENCE_WG();                                    // this wave's S_w stores before its own loads
         uint32_t* xs = l.cnt;                              // (the counters are done: XS_DW + MISC_DW + NT dwords fit their region)
         uint32_t* bmisc = xs + ((XS_DW + 1) / 2) * 2;
         uint32_t* bs = bmisc + MISC_DW;
