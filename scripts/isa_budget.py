@@ -30,11 +30,13 @@ STAMPS = {0: "entry", 1: "step1_stage_count", 2: "step1_decide", 3: "step1_decid
           6: "tile_loop", 7: "tile_loop", 8: "tile_loop", 9: "change_point", 10: "results"}
 # a written lower bound per tile-lane phase of the home instantiation (slide 6, pair table, 8 blocks, 8 windows per lane):
 # phase 1: 24 pair lookups (an address each) + 8 block ORs and count adds; windows: per window a 3-input NOR and a popcount,
-# per window pair one packed subtract + add of the counts; scan: 6 DPP steps and 8 prefix adds; candidates: two stores' sums
+# per window pair one packed subtract + add of the counts; scan: 6 DPP steps and 8 prefix adds; candidates: the lane's first
+# candidate (window address, magic division: add, mulhi) and its window (mul, sub), the second one's window and whether it is
+# the lane's own (add, compare, two selects), two row addresses, two sums, two store offsets = 15
 # (the strided pass: none -- the lanes' own candidates need no second pass)
-LOWER = {1: 24 + 16, 2: 8 * 2 + 4 * 2, 3: 6 + 8 + 2, 4: 2, 6: 0, 5: 0}
+LOWER = {1: 24 + 16, 2: 8 * 2 + 4 * 2, 3: 6 + 8 + 15, 4: 2, 6: 0, 5: 0}
 REGIONS = {1: "tile_setup", 2: "stage_store", 3: "prefetch", 4: "tile_dispatch", 5: "binseg_prefilter", 6: "binseg_f64_reduce",
-           7: "binseg_exact_result"}
+           7: "binseg_exact_result", 8: "binseg_one_lane"}
 # written floors of the regions, VALU per wave and execution (static rows hold BOTH sides of every branch, so a row can lie
 # above its floor by the side a read does not take):
 # 1 tile set-up: the first prefetch (a lane id, a compare, four zeros) -- everything else is wave-uniform: 6
@@ -42,13 +44,18 @@ REGIONS = {1: "tile_setup", 2: "stage_store", 3: "prefetch", 4: "tile_dispatch",
 #   tail (4 words x bfrev, two shifts, bfi): 2 forward, 18 reverse
 # 3 prefetch: the compare against the staged quads and four zeros under the masked load; the address is per read: 5
 # 4 dispatch: the invalid flag's LDS read and its readfirstlane; the switch is scalar: 2
-# 5 prefilter, per group of four candidates: an address and a compare per load (8), per candidate D (mul, sub, cvt), the
-#   denominator (2 cvt, mul), rcp, two multiplies, the select of unused slots, compare + four selects + max for best /
-#   runner-up (17) = 76; + the wave maximum (6 DPP steps, a readlane) and the ballot's compare: 9
+# 5 prefilter, integer route, per candidate of a full group: D (24-bit multiply-add, its addend's step, cvt), the denominator
+#   (b's step, subtract, multiply), rcp, two multiplies, compare + med3 + three selects for best / runner-up = 14, 56 per group;
+#   the group that holds the last used slot adds an offset, a clamp, a compare and a select per candidate: 72; + per read the
+#   lane's first candidate (index, offset, b, -T b: 6), its index rebuilt from the slot (3), the wave maximum (6 DPP steps, a
+#   readlane), the threshold and the two ballots' compares: 20.  Static rows hold four groups of both kinds and the four checked
+#   groups of the float64 route; a config-2 read runs one full and one checked group: 56 + 72 + 20 = 148
+# 8 one-lane finish: two readlanes, D (2 cvt, mul, fma), numerator and denominator (3), three float64 divisions (the score
+#   and the gain's two, about 11 each): 42
 # 6 one float64 candidate per lane (41, the fraction comparison as written) + one division (about 12) + three wave maxima
-#   (21) + two ballots' compares: 76
-# 7 the exact tournament never runs without a tie; the result store is one lane's: 0
-REGION_LOWER = {1: 6, 2: 2, 3: 5, 4: 2, 5: 76 + 9, 6: 76, 7: 0}
+#   (21) + two ballots' compares: 76 -- only reads with two or more close lanes, a crowded lane or no prefilter come here
+# 7 the exact tournament never runs without a tie; the gain's two divisions are counted with the finish that ran: 0
+REGION_LOWER = {1: 6, 2: 2, 3: 5, 4: 2, 5: 56 + 72 + 20, 6: 76, 7: 0, 8: 42}
 
 
 def compile_isa(src, group, out):

@@ -106,16 +106,13 @@ struct ScanArgs {
     int32_t lc_cap;              // capacity of the candidate-prefix array Lc (u32 entries) = max n_win / jump + 1
     uint32_t jump_magic;         // ceil(2^32 / jump): w / jump == mulhi(w, jump_magic) for w < 2^20; 0 for jump == 1 (see div_jump)
     int32_t q, r, lw;            // window = q full blocks + r positions; lw = W - k start positions
-    // fused path, 16-bit candidate sums: Lc16[c] = left sum of candidate c counted from its tile's first
-    // window, Tc[t] = sum of S_w before tile t; tile of window w = mulhi(w, tw_magic)
-    int32_t lc16;                // 1 = Lc16 + Tc instead of the u32 Lc
-    int32_t lc_global;           // 1 = the candidate sums (Lc16, or the generic kernel's 32-bit Lc) live off-chip in lc_scratch (lc_stride entries per read): 1 kB of L2 traffic per
-    int32_t lc_stride;           //        read instead of 1 kB of LDS per wave -> one more resident workgroup per CU
+    // the candidate sums Lc[c] = sum of S_w over w < c * jump (absolute, 32 bits) live off-chip in lc_scratch: lc_stride 16-bit units
+    // per read, written once and read once by the read's own wave (L2 traffic instead of LDS per wave)
+    int32_t lc_global;           // 1 for every plan (plan_geometry); the host allocates lc_scratch by it
+    int32_t lc_stride;
     uint16_t* lc_scratch;
     int32_t pair_n;              // 0, or 4^(k+1): entries of the pair table (two adjacent positions per lookup)
-    int32_t tile_cap;            // entries of Tc (tiles of the longest read)
     int32_t tw;                  // windows per fused tile
-    uint32_t tw_magic;           // ceil(2^32 / tw)
     int32_t tile_full;           // fused tiles: 1 = all 64 lanes hold windows' blocks (8 more windows per tile), 0 = the last lane is halo
     int32_t wpg;                 // waves (reads) per workgroup of this launch, 4 .. WPG_MAX
     int32_t pp_d;                // per-pattern tiles (tile_pp_s): -1 = not eligible, 0 = no self-overlapping k-mer,
@@ -170,9 +167,6 @@ struct Lds {
     // after phase 1b XF / XT hold, per START lane: OR of the whole lanes a window skips | matches they add,
     // for the near (XF) and the far (XT) end lane
     uint32_t* Tot;     // per span: matches in the span, then exclusive prefix over spans
-    uint32_t* Lc;      // Lc[c] = sum of S_w over w < c * jump: left sums of the change-point candidates
-    uint16_t* Lc16;    // (lc16) the same, counted from the first window of the candidate's tile
-    uint32_t* Tc;      // (lc16) sum of S_w before each tile
     uint32_t* row;     // WIN_U * NT dwords: one group of window sums, scanned in place
     uint32_t* misc;
 };
@@ -190,10 +184,6 @@ TPS_HD int64_t blk_region_dw(const ScanArgs& a) {
     return (need + 3) & ~3ll;
 }
 TPS_HD int64_t val_dw(const ScanArgs& a) { return a.val_on ? ((a.seq_dw + 4 + 3) / 4) * 2 : 0; }   // u16 per 16 positions (+ look-ahead), even (seq_dw is a multiple of 4); none for a batch without invalid letters
-TPS_HD int64_t lc_dw(const ScanArgs& a) {          // even dword counts keep misc 8-byte aligned
-    if (a.lc16) return (a.lc_global ? 0 : ((a.lc_cap + 3) / 4) * 2) + ((a.tile_cap + 1) / 2) * 2;
-    return a.lc_global ? 0 : ((a.lc_cap + 1) / 2) * 2;        // generic kernel: absolute 32-bit sums, also off-chip by default
-}
 TPS_HD int64_t row_dw(const ScanArgs& a) {
     const int64_t fused = a.variant ? ((int64_t)NT << a.blk_log2) + NT : 0;      // + one pad word per lane
     return fused > WIN_U * NT ? fused : WIN_U * NT;
@@ -208,10 +198,6 @@ TPS_DEV Lds carve(uint32_t* base, uint32_t* lut, const ScanArgs& a) {
     l.seq2 = p; p += a.seq_dw;
     l.val = (uint16_t*)p;  p += val_dw(a);
     l.Tot = p;  p += a.tot_dw;
-    l.Lc = p;
-    l.Lc16 = (uint16_t*)p;
-    l.Tc = p + ((a.lc16 && a.lc_global) ? 0 : ((a.lc_cap + 3) / 4) * 2);
-    p += lc_dw(a);
     l.row = p;  p += row_dw(a);
     l.misc = p;
     l.G = l.blk;
@@ -224,7 +210,7 @@ TPS_DEV Lds carve(uint32_t* base, uint32_t* lut, const ScanArgs& a) {
     return l;
 }
 TPS_HD int64_t lds_dwords(const ScanArgs& a) {
-    return (int64_t)a.blk_dw + (a.seq_alias ? 0 : a.seq_dw) + val_dw(a) + a.tot_dw + lc_dw(a) + row_dw(a) + MISC_DW +
+    return (int64_t)a.blk_dw + (a.seq_alias ? 0 : a.seq_dw) + val_dw(a) + a.tot_dw + row_dw(a) + MISC_DW +
            ((a.xt_alias && a.xt_own) ? (a.xt_alias == 2 ? 2 : 1) * XLANES : 0);   // per wave; + the table per workgroup
 }
 // LDS dwords of a whole workgroup: the shared table + WPG wave slices (each rounded to 16 bytes)
@@ -1008,8 +994,7 @@ TPS_DEV void candidates_group(const ScanArgs& a, const Lds& l, uint64_t lc_g, in
             const uint32_t w = (uint32_t)(w0 + wl);
             const uint32_t c = div_jump(w, a.jump_magic);
             if (c * jump == w && (int)c < a.lc_cap) {
-                if (lc_g) g32_store(lc_g, c, carry + l.row[u * NT + tid]);
-                else l.Lc[c] = carry + l.row[u * NT + tid];
+                g32_store(lc_g, c, carry + l.row[u * NT + tid]);
             }
         }
     }
@@ -1024,20 +1009,20 @@ TPS_DEV void candidates_group(const ScanArgs& a, const Lds& l, uint64_t lc_g, in
 // per-read copies of the plan constants the fused tile needs (pinned: see TPS_PIN_S)
 struct TileConst {
     int32_t q, r;
-    uint32_t jump, jump_magic, lc_cap, lc16;
-    uint64_t lc_g;               // this read's off-chip candidate sums: Lc16, or absolute 32-bit sums (0 = they live in LDS)
+    uint32_t jump, jump_magic, lc_cap;
+    uint64_t lc_g;               // this read's off-chip candidate sums (absolute, 32 bits)
     uint16_t* sw16;              // this read's window sums (16-bit, ScanArgs::sums16)
     int64_t rd;                  // (diagnostics build: the read index, for the clock stamps of the per-pattern tiles)
 };
 TPS_DEV TileConst tile_const(const ScanArgs& a, int64_t r) {
     TileConst t;
-    t.lc_g = a.lc_global ? (uint64_t)(uintptr_t)(a.lc_scratch + r * (int64_t)a.lc_stride) : 0ull;
+    t.lc_g = (uint64_t)(uintptr_t)(a.lc_scratch + r * (int64_t)a.lc_stride);
     t.sw16 = a.sums16 + (a.win_off16 ? a.win_off16[r] : 0);
     t.rd = r;
     t.q = (int32_t)uniform((uint32_t)a.q); t.r = (int32_t)uniform((uint32_t)a.r);
     t.jump = uniform((uint32_t)a.prm.jump); t.jump_magic = uniform(a.jump_magic);
-    t.lc_cap = uniform((uint32_t)a.lc_cap); t.lc16 = uniform((uint32_t)a.lc16);
-    TPS_PIN_S(t.q); TPS_PIN_S(t.r); TPS_PIN_S(t.jump); TPS_PIN_S(t.jump_magic); TPS_PIN_S(t.lc_cap); TPS_PIN_S(t.lc16);
+    t.lc_cap = uniform((uint32_t)a.lc_cap);
+    TPS_PIN_S(t.q); TPS_PIN_S(t.r); TPS_PIN_S(t.jump); TPS_PIN_S(t.jump_magic); TPS_PIN_S(t.lc_cap);
     return t;
 }
 
@@ -1104,10 +1089,7 @@ TPS_DEV Lds carve_fused(uint32_t* base, uint32_t* lut, const ScanArgs& a) {
     }
     l.val = (uint16_t*)p;
     p += VAL;
-    l.Lc = p;
-    l.Lc16 = (uint16_t*)p;
-    l.Tc = p + ((a.lc16 && a.lc_global) ? 0 : ((a.lc_cap + 3) / 4) * 2);
-    l.XF = p + lc_dw(a);                       // (only the fallback tile reads these; without xt_own it cannot run)
+    l.XF = p;                                  // (only the fallback tile reads these; without xt_own it cannot run)
     l.XT = l.XF + XLANES;
     return l;
 }
@@ -1442,21 +1424,13 @@ TPS_DEV void tile_fused_s(const ScanArgs& a, const TileConst& tc, const Lds& l, 
         TPS_PHASE {
             const uint32_t carry = (uint32_t)s_total;
             if (tid == 0) { l.misc[M_INVALID] = 0; l.misc[M_NTIE] = 0; }      // for the next tile's staging
-            if (tc.lc16 && tid == 0) l.Tc[tile] = carry;
             uint32_t c = c_lo + (uint32_t)tid;
             uint32_t w = c * jump - (uint32_t)w0;         // tile-local window index of candidate c
             TPS_NOVEC
             for (int t = 0; t < passes; ++t) {
                 if (c < c_hi) {
                     const uint32_t pre = l.row[w + (w >> LOG2B)];
-                    if (tc.lc16) {
-                        if (tc.lc_g) g16_store(tc.lc_g, c, pre);
-                        else l.Lc16[c] = (uint16_t)pre;
-                    } else if (tc.lc_g) {
-                        g32_store(tc.lc_g, c, carry + pre);
-                    } else {
-                        l.Lc[c] = carry + pre;
-                    }
+                    g32_store(tc.lc_g, c, carry + pre);
                 }
                 c += NT;
                 w += NT * jump;
@@ -1480,21 +1454,13 @@ TPS_DEV void tile_candidates(const TileConst& tc, const Lds& l, int w0, int tile
     TPS_PHASE {
         const uint32_t carry = (uint32_t)s_total;
         if (tid == 0) { l.misc[M_INVALID] = 0; l.misc[M_NTIE] = 0; }      // for the next tile's staging
-        if (tc.lc16 && tid == 0) l.Tc[tile] = carry;
         uint32_t c = c_lo + (uint32_t)tid;
         uint32_t w = c * jump - (uint32_t)w0;
         TPS_NOVEC
         for (int t = 0; t < passes; ++t) {
             if (c < c_hi) {
                 const uint32_t pre = l.row[w + (w >> LOG2B)];
-                if (tc.lc16) {
-                    if (tc.lc_g) g16_store(tc.lc_g, c, pre);
-                    else l.Lc16[c] = (uint16_t)pre;
-                } else if (tc.lc_g) {
-                    g32_store(tc.lc_g, c, carry + pre);
-                } else {
-                    l.Lc[c] = carry + pre;
-                }
+                g32_store(tc.lc_g, c, carry + pre);
             }
             c += NT;
             w += NT * jump;
@@ -1958,11 +1924,14 @@ TPS_DEV void tile_lc_s(const ScanArgs& a, const TileConst& tc, const Lds& l, int
     }
     // exclusive scan of the lane totals over the wave (lanes past the tile's last window add garbage behind every valid window)
     const Lane<uint32_t> lexc = wave_excl_sum(ltot);
-    // (round 6) the sums-only tiles with absolute 32-bit candidate sums off chip: every lane stores its own candidates' left
-    // sums right behind its prefixes -- no candidate-strided pass over row[] (the lc16 and LDS-Lc layouts, jump < 4 and the
-    // chain-corrected / 16-bit-table tiles keep that pass)
+    // (round 6) the sums-only tiles: every lane stores its own candidates' left sums right behind its prefixes -- no
+    // candidate-strided pass over row[] (jump < 4 and the chain-corrected / 16-bit-table tiles keep that pass)
     bool lane_cands = false;
-    if constexpr (CD == 0 && !M16) lane_cands = tc.lc_g != 0ull && !tc.lc16 && tc.jump >= 4u;     // (uniform)
+    if constexpr (CD == 0 && !M16) lane_cands = tc.jump >= 4u;     // (uniform)
+    // change-point candidates of this tile: c with w0 <= c * jump < w0 + nw_tile, and below the scratch block's capacity
+    const uint32_t c_lo = div_jump((uint32_t)w0 + tc.jump - 1u, tc.jump_magic);
+    uint32_t c_hi = div_jump((uint32_t)(w0 + nw_tile) + tc.jump - 1u, tc.jump_magic);
+    if (c_hi > tc.lc_cap) c_hi = tc.lc_cap;
     TPS_PHASE {
         const int lane = tid;
         const uint32_t* const sw = TPS_AT(sw_);
@@ -1978,14 +1947,32 @@ TPS_DEV void tile_lc_s(const ScanArgs& a, const TileConst& tc, const Lds& l, int
         if (lane_cands) {
             if (tid == 0) TPS_EMU_COUNT(7);
             // (round 6) the change-point candidates among the lane's own windows, read back from its own row (no barrier): the
-            // first is window f = c jump - (w0 + 8 lane) of the lane, the second f + jump; jump >= 4 leaves no room for a third
-            const uint32_t carry = (uint32_t)s_total + TPS_AT(lexc);
-            const uint32_t wl = (uint32_t)(lane * B), wa = (uint32_t)w0 + wl;
-            const uint32_t c = mulhi32(wa + tc.jump - 1u, tc.jump_magic);     // (div_jump without its jump = 1 case)
-            const uint32_t f = c * tc.jump - wa;
-            if (f < (uint32_t)B && wl + f < (uint32_t)nw_tile && c < tc.lc_cap) g32_store(tc.lc_g, c, carry + pr[f]);
-            const uint32_t f2 = f + tc.jump;
-            if (f2 < (uint32_t)B && wl + f2 < (uint32_t)nw_tile && c + 1u < tc.lc_cap) g32_store(tc.lc_g, c + 1u, carry + pr[f2]);
+            // first is window f = c jump - (w0 + 8 lane) of the lane, the second f + jump; jump >= 4 leaves no room for a third.
+            // Both go out through one range-checked descriptor over the read's first c_hi entries (g32_store_clamped): a candidate
+            // is inside the tile, w0 + 8 lane + f < w0 + nw_tile, exactly when c jump < w0 + nw_tile, i.e. c < c_hi, and c_hi is
+            // already cut at lc_cap -- the hardware's bound stands for both compares.  What is left per lane is whether the window
+            // is one of its eight: the first always is up to jump 8 (f < jump); a candidate that is not gets an index from c_hi
+            // on, which the descriptor drops, and reads its row at a clamped index.  No exec-masked region: both row reads are
+            // issued before either store.  (Two bodies behind a uniform branch: as one, the compiler turns the jump > 8 case into
+            // five selects that every jump pays.)
+            auto own_candidates = [&](auto bigj_) {
+                const uint32_t carry = (uint32_t)s_total + TPS_AT(lexc);
+                const uint32_t wa = (uint32_t)w0 + (uint32_t)(lane * B);
+                const uint32_t c = mulhi32(wa + tc.jump - 1u, tc.jump_magic);     // (div_jump without its jump = 1 case)
+                const uint32_t f = c * tc.jump - wa, f2 = f + tc.jump;
+                uint32_t i1 = c, r1 = f;
+                if constexpr (decltype(bigj_)::value != 0) {
+                    i1 = f < (uint32_t)B ? c : c_hi;
+                    r1 = f < (uint32_t)B ? f : (uint32_t)(B - 1);
+                }
+                const uint32_t i2 = (f2 < (uint32_t)B ? c : c_hi) + 1u;
+                const uint32_t r2 = f2 < (uint32_t)B ? f2 : (uint32_t)(B - 1);
+                const uint32_t v1 = pr[r1], v2 = pr[r2];
+                g32_store_clamped(tc.lc_g, c_hi, i1, carry + v1);
+                g32_store_clamped(tc.lc_g, c_hi, i2, carry + v2);
+            };
+            if (tc.jump > (uint32_t)B) own_candidates(IntC<1>());       // (uniform)
+            else own_candidates(IntC<0>());
         }
     }
     TPS_SYNC();
@@ -1994,31 +1981,20 @@ TPS_DEV void tile_lc_s(const ScanArgs& a, const TileConst& tc, const Lds& l, int
     // the tile's total = the prefix at its first window that is NOT part of it (nw_tile <= 512 - q - 1: a written entry)
     const uint32_t gsum = uniform(l.row[nw_tile + (nw_tile >> LOG2B)] + xt_at(nw_tile >> LOG2B));
     {
-        // change-point candidates of this tile: c with w0 <= c * jump < w0 + nw_tile, 64 per pass
+        // the candidate-strided pass, 64 candidates at a time
         const uint32_t jump = tc.jump;
-        const uint32_t c_lo = div_jump((uint32_t)w0 + jump - 1u, tc.jump_magic);
-        uint32_t c_hi = div_jump((uint32_t)(w0 + nw_tile) + jump - 1u, tc.jump_magic);
-        if (c_hi > tc.lc_cap) c_hi = tc.lc_cap;
         const int passes = (c_hi > c_lo && !lane_cands) ? (int)((c_hi - c_lo + NT - 1) / NT) : 0;     // (lane_cands: stored above)
         TPS_ISA_MARK(MK + 6);                     // 6: the candidate-strided pass itself
         TPS_PHASE {
             const uint32_t carry = (uint32_t)s_total;
             if (tid == 0) { l.misc[M_INVALID] = 0; l.misc[M_NTIE] = 0; }      // for the next tile's staging
-            if (tc.lc16 && tid == 0) l.Tc[tile] = carry;
             uint32_t c = c_lo + (uint32_t)tid;
             uint32_t w = c * jump - (uint32_t)w0;         // tile-local window index of candidate c
             TPS_NOVEC
             for (int t = 0; t < passes; ++t) {
                 if (c < c_hi) {
                     const uint32_t pre = l.row[w + (w >> LOG2B)] + xt_at((int)(w >> LOG2B));
-                    if (tc.lc16) {
-                        if (tc.lc_g) g16_store(tc.lc_g, c, pre);
-                        else l.Lc16[c] = (uint16_t)pre;
-                    } else if (tc.lc_g) {
-                        g32_store(tc.lc_g, c, carry + pre);
-                    } else {
-                        l.Lc[c] = carry + pre;
-                    }
+                    g32_store(tc.lc_g, c, carry + pre);
                 }
                 c += NT;
                 w += NT * jump;
@@ -2810,21 +2786,30 @@ TPS_DEV void binseg_from_lc(const ScanArgs& a, const Lds& l, uint64_t lc_g, cons
     // fused geometry's window sizes); otherwise through int64 like the standalone path
     const bool exact53 = (double)n * 4294967296.0 < 9007199254740992.0 && (double)tot * (double)n < 9007199254740992.0;
     const double nf = (double)n, totf = (double)tot;
-    // Float32 prefilter (off-chip 16-bit sums, the fused kernels' normal case): the score D^2 / (b (n - b)) of every
-    // candidate in single precision from the EXACT D (float64 fma, then rounded once), the wave maximum, and only
-    // candidates within 1e-4 of it -- two orders of magnitude more than single precision can be off -- go through the
-    // float64 fraction comparison below (41 instructions per candidate; the prefilter costs about a third of that).
-    // Where n T < 2^31 (wave-uniform; config 2: n = 2 467, T of the order of 3e5) both products of D and D itself fit a signed
-    // 32-bit integer: D is then computed exactly in integers -- b and T b advance by a uniform step from slot to slot -- and
-    // v_cvt_f32_i32 rounds it to nearest-even exactly as the float64 fma's result is rounded by v_cvt_f32_f64: the same d32, bit
-    // for bit, without two conversions to float64, a multiply and an fma per candidate.  Slots past c_max load candidate c_max
-    // (an index clamp instead of a masked load with its zeroed register; their score is replaced by -1 as before).
-    const bool int_d = (double)tot * (double)n < 2147483648.0;
+    // Float32 prefilter: the score D^2 / (b (n - b)) of every candidate in single precision from the EXACT D (rounded once),
+    // the wave maximum, and only candidates within 1e-4 of it -- two orders of magnitude more than single precision can be
+    // off -- go on to float64 (below).  Each lane walks its candidates c_min + lane + 64 j, slot by slot, and keeps its best
+    // score with that candidate's slot and left sum, and its second-best score.
+    //   D.  Where n T < 2^31 and T < 2^24 (wave-uniform; config 2: n = 2 467, T of the order of 3e5) both products of D and D itself
+    // fit a signed 32-bit integer, and D is ONE 24-bit multiply-add: n L_b + (-T b), the addend advancing by the uniform -64 jump T
+    // from slot to slot.  Its factors fit 24 bits: n < 2^21 (exact53), L_b <= T; and T < 2^24 always holds for the fused kernels once
+    // n T < 2^31 -- every S_w < 2^16, so T < 2^16 n and T^2 < 2^16 n T < 2^47.  v_cvt_f32_i32 rounds D to nearest-even exactly as the
+    // float64 fma's result is rounded by v_cvt_f32_f64 on the other route: the same d32, bit for bit.
+    //   b (n - b).  b advances as a float by the exact constant 64 jump, and n - b is one float subtraction: all three are integers
+    // below 2^24 (b <= n < 2^21), so they are the very values the conversions of the integers b and n - b gave.
+    //   The runner-up is med3(best, runner-up, s) taken before the best is updated: runner-up <= best always holds, so the median is
+    // max(runner-up, min(best, s)) -- the loser of the comparison, or the old runner-up (a score EQUAL to the best becomes the
+    // runner-up: conservative).
+    //   Unused slots.  The lanes' candidates are consecutive, so every lane's slots before the last one any lane uses (nslot - 1) are
+    // full: a group of four slots in front of that one (nslot lives in an SGPR: one uniform test per group) neither clamps its loads
+    // nor tests its lanes.  The group that holds slot nslot - 1 clamps its loads at c_max and replaces the score of a lane past c_max
+    // by -1, straight-line for all four slots: written as uniform branches per slot (full / last / skipped) the selects of best and
+    // runner-up came out as exec-masked moves between a dozen basic blocks.  The float64 route, rare, has checked groups only.
+    const bool int_d = (double)tot * (double)n < 2147483648.0 && tot < (1ull << 24);
     constexpr int LCV = 16;
-    const bool prefilter = !a.lc16 && lc_g && exact53 && c_max - c_min < LCV * NT;
+    const bool prefilter = exact53 && c_max - c_min < LCV * NT;
     int nslot = c_max >= c_min ? (c_max - c_min + NT) / NT : 0;          // candidate slots per lane that any lane uses
     TPS_PIN_S(nslot);
-    auto tile_sum = [&](int c) { return l.Tc[(uint32_t)(((uint64_t)(uint32_t)(c * jump) * a.tw_magic) >> 32)]; };
     // per lane: its best single-precision score with that candidate's index and left sum, and its second-best score
     Lane<float> p_s1_(-1.0f), p_s2_(-1.0f);
     Lane<uint32_t> p_lc_(0);
@@ -2833,60 +2818,74 @@ TPS_DEV void binseg_from_lc(const ScanArgs& a, const Lds& l, uint64_t lc_g, cons
     bool crowded = false;                          // some lane holds a second candidate within the prefilter's margin
     TPS_ISA_REGION(5);
     if (prefilter) {
-        // (one phase per variant, each with its own laundered lane id: written as two branches of one phase the slots' shared index
-        // arithmetic and compares of all sixteen slots are hoisted in front of the branch, used or not)
-        auto prefilter_phase = [&](auto lean_) {
+        // (one phase per route, each with its own laundered lane id: written as two branches of one phase the slots' shared index
+        // arithmetic is hoisted in front of the branch, used or not)
+        auto prefilter_phase = [&](auto intd_) {
         TPS_PHASE {
+            constexpr bool INTD = decltype(intd_)::value != 0;
             float &p_s1 = TPS_AT(p_s1_), &p_s2 = TPS_AT(p_s2_);
             uint32_t& p_lc = TPS_AT(p_lc_);
-            int& p_c = TPS_AT(p_c_);
-            p_s1 = -1.0f; p_s2 = -1.0f; p_lc = 0; p_c = -1;
-            // four slots at a time behind ONE uniform test (nslot lives in an SGPR): slots no lane uses cost nothing;
-            // the four loads of a group are requested before the first one is used
-            auto group = [&](int g) {
-                constexpr bool LEAN = decltype(lean_)::value != 0;
+            p_s1 = -1.0f; p_s2 = -1.0f; p_lc = 0;
+            int p_j = -1;                                 // the slot of the lane's best candidate (its index is rebuilt from it at the end)
+            const int c0 = c_min + tid;                   // the lane's candidate of slot 0
+            const uint32_t off0 = 4u * (uint32_t)c0;      // ... and its byte offset: slot j adds the constant 256 j
+            const float nf32 = (float)n, bstep = (float)(NT * jump);
+            float bf = (float)(c0 * jump);
+            const uint32_t ntb_step = 0u - (uint32_t)tot * (uint32_t)(NT * jump);
+            uint32_t ntb = 0u - (uint32_t)tot * (uint32_t)(c0 * jump);       // -T b (modulo 2^32, like D's products)
+            // one candidate: slot j, left sum lc; LAST = the slot may hold lanes past c_max
+            auto slot = [&](int j, uint32_t lc, auto last_) {
+                float d32;
+                if constexpr (INTD) {
+                    d32 = (float)(int32_t)(mul24((uint32_t)n, lc) + ntb);      // exact: |D| < 2^31
+                    ntb += ntb_step;
+                } else {
+                    d32 = (float)__builtin_fma(-totf, (double)bf, nf * (double)lc);
+                }
+                const float den32 = bf * (nf32 - bf);
+                bf += bstep;
+                float s_ = d32 * d32 * rcp_f32(den32);
+                if constexpr (decltype(last_)::value != 0) s_ = tid <= c_max - c_min - j * NT ? s_ : -1.0f;
+                const bool gt = s_ > p_s1;
+                p_s2 = med3_f32(p_s1, p_s2, s_);
+                p_lc = gt ? lc : p_lc;
+                p_j = gt ? j : p_j;
+                p_s1 = gt ? s_ : p_s1;
+            };
+            // four slots at a time behind ONE uniform test: slots no lane uses cost nothing; the four loads of a group are
+            // requested before the first one is used.  CHECKED = the group may hold lanes past c_max.
+            auto group = [&](int g, auto checked_) {
+                constexpr bool CHECKED = decltype(checked_)::value != 0;
                 uint32_t lcv[4];
                 TPS_UNROLL
                 for (int i = 0; i < 4; ++i) {
-                    const int c = c_min + tid + (4 * g + i) * NT;
-                    if constexpr (LEAN) lcv[i] = g32_load_at(lc_g, 4u * (uint32_t)(c <= c_max ? c : c_max));
-                    else lcv[i] = c <= c_max ? g32_load(lc_g, (uint32_t)c) : 0u;
+                    const uint32_t joff = 4u * NT * (uint32_t)(4 * g + i);
+                    if constexpr (CHECKED) lcv[i] = g32_load_at(lc_g, off0 + joff < 4u * (uint32_t)c_max ? off0 + joff : 4u * (uint32_t)c_max);
+                    else lcv[i] = g32_load_at(lc_g + joff, off0);          // (the slot's constant goes into the instruction's offset)
                 }
-                const int b0 = (c_min + tid + 4 * g * NT) * jump;
-                const uint32_t tb0 = (uint32_t)tot * (uint32_t)b0, tb_step = (uint32_t)tot * (uint32_t)(NT * jump);
                 TPS_UNROLL
-                for (int i = 0; i < 4; ++i) {
-                    const int c = c_min + tid + (4 * g + i) * NT;
-                    const int b = LEAN ? b0 + i * (NT * jump) : c * jump;
-                    float d32;
-                    if constexpr (LEAN) {
-                        // (T b made opaque: an add per slot; folded into the product it becomes a 64-bit multiply-add per candidate)
-                        uint32_t tb = tb0 + (uint32_t)i * tb_step;
-                        TPS_PIN_V(tb);
-                        d32 = (float)(int32_t)((uint32_t)n * lcv[i] - tb);     // exact: |D| < 2^31
-                    } else {
-                        const double bf = (double)b;
-                        d32 = (float)__builtin_fma(-totf, bf, nf * (double)lcv[i]);
-                    }
-                    const float den32 = (float)b * (float)(n - b);
-                    float s_ = d32 * d32 * rcp_f32(den32);
-                    s_ = c <= c_max ? s_ : -1.0f;
-                    const bool gt = s_ > p_s1;                    // (an exact tie becomes the runner-up: conservative)
-                    const float lose = gt ? p_s1 : s_;
-                    p_s2 = lose > p_s2 ? lose : p_s2;
-                    p_lc = gt ? lcv[i] : p_lc;
-                    p_c = gt ? c : p_c;
-                    p_s1 = gt ? s_ : p_s1;
-                }
+                for (int i = 0; i < 4; ++i) slot(4 * g + i, lcv[i], checked_);
             };
-            if (nslot > 0) group(0);
-            if (nslot > 4) group(1);
-            if (nslot > 8) group(2);
-            if (nslot > 12) group(3);
+            if constexpr (INTD) {
+                if (nslot > 4) group(0, IntC<0>()); else if (nslot > 0) group(0, IntC<1>());
+                if (nslot > 8) group(1, IntC<0>()); else if (nslot > 4) group(1, IntC<1>());
+                if (nslot > 12) group(2, IntC<0>()); else if (nslot > 8) group(2, IntC<1>());
+                if (nslot > 12) group(3, IntC<1>());
+            } else {
+                if (nslot > 0) group(0, IntC<1>());
+                if (nslot > 4) group(1, IntC<1>());
+                if (nslot > 8) group(2, IntC<1>());
+                if (nslot > 12) group(3, IntC<1>());
+            }
+            TPS_AT(p_c_) = p_j >= 0 ? c0 + p_j * NT : -1;
         }
         };
-        if (int_d) prefilter_phase(IntC<1>());
-        else prefilter_phase(IntC<0>());
+        if (int_d) {
+            prefilter_phase(IntC<1>());
+        } else {
+            TPS_EMU_COUNT(11);
+            prefilter_phase(IntC<0>());
+        }
         float m32;
         {
             Lane<uint32_t> key;
@@ -2901,83 +2900,95 @@ TPS_DEV void binseg_from_lc(const ScanArgs& a, const Lds& l, uint64_t lc_g, cons
         Lane<bool> close2;
         TPS_LANES { TPS_AT(close2) = TPS_AT(p_s2_) >= thr32 && TPS_AT(p_s2_) >= 0.0f; }
         crowded = wave_ballot(close2) != 0;
+        if (crowded) TPS_EMU_COUNT(10);
     }
-    TPS_ISA_REGION(6);
-    TPS_PHASE {
-        double bn = -1.0, bd = 1.0;
-        int best_b = -1;
-        bool amb = false;
-        auto offer = [&](int c, uint32_t lc) {
-            const int b = c * jump;
-            const double bf = (double)b;
-            double dd;
-            if (exact53) dd = __builtin_fma(-totf, bf, nf * (double)lc);
-            else dd = (double)((int64_t)n * (int64_t)lc - (int64_t)tot * (int64_t)b);
-            const double num = dd * dd, den = bf * (nf - bf);
-            const double t1 = num * bd, t2 = bn * den;         // num / den  vs  bn / bd
-            const double diff = t1 - t2;
-            const bool near = __builtin_fabs(diff) <= 1e-13 * t2;   // false while bn < 0
-            const bool take = diff >= 0.0;                     // ties -> the later (larger) candidate
-            amb = near || (amb && !take);
-            if (take) { bn = num; bd = den; best_b = b; }
-        };
-        if (prefilter) {
-            if (TPS_AT(p_c_) >= 0 && TPS_AT(p_s1_) >= thr32) offer(TPS_AT(p_c_), TPS_AT(p_lc_));
-        } else if (a.lc16 && lc_g && c_max - c_min < LCV * NT) {
-            // off-chip 16-bit sums: all of the lane's values are requested before the first one is used
-            uint32_t lcv[LCV];
-            TPS_UNROLL
-            for (int i = 0; i < LCV; ++i) {
-                const int c = c_min + tid + i * NT;
-                lcv[i] = c <= c_max ? g16_load(lc_g, (uint32_t)c) : 0u;
-            }
-            TPS_UNROLL
-            for (int i = 0; i < LCV; ++i) {
-                const int c = c_min + tid + i * NT;
-                if (c <= c_max) offer(c, tile_sum(c) + lcv[i]);
-            }
-        } else {
-            TPS_NOVEC
-            for (int c = c_min + tid; c <= c_max; c += NT) {
-                uint32_t lc;
-                if (a.lc16) lc = tile_sum(c) + (lc_g ? g16_load(lc_g, (uint32_t)c) : (uint32_t)l.Lc16[c]);
-                else lc = lc_g ? g32_load(lc_g, (uint32_t)c) : l.Lc[c];
-                offer(c, lc);
-            }
-        }
-        const double best = best_b >= 0 ? bn / bd : -1.0;
-        uint64_t bits = 0;
-        if (best >= 0.0) __builtin_memcpy(&bits, &best, 8);   // non-negative doubles order like integers
-        TPS_AT(best_) = best; TPS_AT(best_b_) = best_b; TPS_AT(amb_) = amb; TPS_AT(bits_) = bits;
+    // The lanes whose kept candidate lies within the margin.  Exactly one, and no lane with a second one that close (almost every
+    // read): that candidate is the answer and nothing needs comparing or reducing -- one float64 score, evaluated by the wave as a
+    // whole with offer()'s expressions.  It is what the stage below returns for such a read: one lane offers, so its fraction is
+    // bn / bd = num / den and the wave maximum is that quotient; `amb` stays false (the first offer compares against bn = -1:
+    // t2 < 0); one lane is `near` the maximum: ntie = 1, no tie.  A read whose best score is 0 (m32 = 0, thr32 = 0) has every
+    // lane that holds a candidate close and takes the stage below unless it has only one candidate -- which is then the answer.
+    uint64_t close = 0;
+    if (prefilter) {
+        Lane<bool> cl;
+        TPS_LANES { TPS_AT(cl) = TPS_AT(p_c_) >= 0 && TPS_AT(p_s1_) >= thr32; }
+        close = wave_ballot(cl);
     }
-    // wave-wide: the best score, how many candidates float64 cannot separate from it, the largest b holding it
+    // the best score, how many candidates float64 cannot separate from it, the largest b holding it
     double m;
     uint32_t ntie = 0;
     int32_t bestb = -1;
-    {
-        Lane<uint32_t> key;
-        TPS_LANES { TPS_AT(key) = (uint32_t)(TPS_AT(bits_) >> 32); }
-        const uint32_t mh = wave_max_u32(key);
-        TPS_LANES { TPS_AT(key) = (uint32_t)(TPS_AT(bits_) >> 32) == mh ? (uint32_t)TPS_AT(bits_) : 0u; }
-        const uint32_t ml = wave_max_u32(key);
-        const uint64_t mbits = ((uint64_t)mh << 32) | ml;
-        __builtin_memcpy(&m, &mbits, 8);
-        Lane<bool> n1, n1_amb;
-        TPS_LANES {
-            const double best = TPS_AT(best_);
-            const bool amb = TPS_AT(amb_), near = best >= m * (1.0 - 1e-14) && best >= 0.0;
-            TPS_AT(n1) = near;
-            TPS_AT(n1_amb) = near && amb;
+    if (!crowded && close != 0 && (close & (close - 1)) == 0) {
+        TPS_ISA_REGION(8);
+        TPS_EMU_COUNT(8);
+        const int src = __builtin_ctzll(close);
+        const int b = wave_read_lane(p_c_, src) * jump;
+        const uint32_t lc = wave_read_lane(p_lc_, src);
+        const double bf = (double)b;
+        const double dd = __builtin_fma(-totf, bf, nf * (double)lc);       // (the prefilter ran: exact53)
+        const double num = dd * dd, den = bf * (nf - bf);
+        m = num / den;
+        ntie = 1u;
+        bestb = b;
+    } else {
+        TPS_ISA_REGION(6);
+        TPS_EMU_COUNT(9);
+        TPS_PHASE {
+            double bn = -1.0, bd = 1.0;
+            int best_b = -1;
+            bool amb = false;
+            auto offer = [&](int c, uint32_t lc) {
+                const int b = c * jump;
+                const double bf = (double)b;
+                double dd;
+                if (exact53) dd = __builtin_fma(-totf, bf, nf * (double)lc);
+                else dd = (double)((int64_t)n * (int64_t)lc - (int64_t)tot * (int64_t)b);
+                const double num = dd * dd, den = bf * (nf - bf);
+                const double t1 = num * bd, t2 = bn * den;         // num / den  vs  bn / bd
+                const double diff = t1 - t2;
+                const bool near = __builtin_fabs(diff) <= 1e-13 * t2;   // false while bn < 0
+                const bool take = diff >= 0.0;                     // ties -> the later (larger) candidate
+                amb = near || (amb && !take);
+                if (take) { bn = num; bd = den; best_b = b; }
+            };
+            if (prefilter) {
+                if (TPS_AT(p_c_) >= 0 && TPS_AT(p_s1_) >= thr32) offer(TPS_AT(p_c_), TPS_AT(p_lc_));
+            } else {
+                // (no prefilter: more than 1 024 candidates, or products of D past 2^53)
+                TPS_NOVEC
+                for (int c = c_min + tid; c <= c_max; c += NT) offer(c, g32_load(lc_g, (uint32_t)c));
+            }
+            const double best = best_b >= 0 ? bn / bd : -1.0;
+            uint64_t bits = 0;
+            if (best >= 0.0) __builtin_memcpy(&bits, &best, 8);   // non-negative doubles order like integers
+            TPS_AT(best_) = best; TPS_AT(best_b_) = best_b; TPS_AT(amb_) = amb; TPS_AT(bits_) = bits;
         }
-        ntie = (uint32_t)__builtin_popcountll(wave_ballot(n1)) + (uint32_t)__builtin_popcountll(wave_ballot(n1_amb));
-        TPS_LANES {
-            const double best = TPS_AT(best_);
-            const int best_b = TPS_AT(best_b_);
-            TPS_AT(key) = (best == m && best_b >= 0) ? (uint32_t)best_b + 1u : 0u;
+        // wave-wide
+        {
+            Lane<uint32_t> key;
+            TPS_LANES { TPS_AT(key) = (uint32_t)(TPS_AT(bits_) >> 32); }
+            const uint32_t mh = wave_max_u32(key);
+            TPS_LANES { TPS_AT(key) = (uint32_t)(TPS_AT(bits_) >> 32) == mh ? (uint32_t)TPS_AT(bits_) : 0u; }
+            const uint32_t ml = wave_max_u32(key);
+            const uint64_t mbits = ((uint64_t)mh << 32) | ml;
+            __builtin_memcpy(&m, &mbits, 8);
+            Lane<bool> n1, n1_amb;
+            TPS_LANES {
+                const double best = TPS_AT(best_);
+                const bool amb = TPS_AT(amb_), near = best >= m * (1.0 - 1e-14) && best >= 0.0;
+                TPS_AT(n1) = near;
+                TPS_AT(n1_amb) = near && amb;
+            }
+            ntie = (uint32_t)__builtin_popcountll(wave_ballot(n1)) + (uint32_t)__builtin_popcountll(wave_ballot(n1_amb));
+            TPS_LANES {
+                const double best = TPS_AT(best_);
+                const int best_b = TPS_AT(best_b_);
+                TPS_AT(key) = (best == m && best_b >= 0) ? (uint32_t)best_b + 1u : 0u;
+            }
+            bestb = (int32_t)wave_max_u32(key) - 1;
         }
-        bestb = (int32_t)wave_max_u32(key) - 1;
     }
-    (void)misc;
+    (void)misc; (void)a; (void)l;
     TPS_ISA_REGION(7);
     if (crowded) ntie = 2u;                        // the prefilter kept one candidate per lane: a second one that close needs the full comparison
     tie = ntie > 1u;

@@ -260,7 +260,7 @@ inline std::string plan_geometry_core(ScanArgs& a, const tps_params& prm, int k,
                        (P <= 15 || p16_ok) && a.q >= 8 && sw16_ok &&
                        a.q / 8 + 2 < (XLANES - NT) && max_period <= std::min(prm.slide, 6) &&
                        2 * a.head_dw <= fused_seq_dw(prm.slide);   // the two step-1 heads fit the tile buffer (TileGeo::SEQ)
-    a.lc16 = 0; a.tile_cap = 0; a.tw = 0; a.tw_magic = 0; a.pair_n = 0; a.lc_global = 0; a.lc_stride = 0; a.pp_d = -1; a.so_fast = 0; a.seq_alias = 0; a.lut_fields = 0; a.tile_full = 0;
+    a.tw = 0; a.pair_n = 0; a.lc_global = 0; a.lc_stride = 0; a.pp_d = -1; a.so_fast = 0; a.seq_alias = 0; a.lut_fields = 0; a.tile_full = 0;
     a.lut16 = 0; a.xt_alias = 0; a.xt_own = 0; a.pair16 = 0;
     if (fused) {
         // per-pattern tiles (tile_pp_s): one-hot 2-bit fields per pattern need distinct k-mers, raw rows of at most 14 bytes
@@ -315,12 +315,11 @@ inline std::string plan_geometry_core(ScanArgs& a, const tps_params& prm, int k,
         // windows per tile: every lane's 8 blocks hold window starts, a window spans q + 1 blocks; EVEN, because the fused
         // kernels store S_w as 16-bit values in whole dwords (g_store_sw8): no tile but a read's last ends inside a dword
         a.tw = ((int)NT * 8 - a.q - 1) & ~1;
-        a.tw_magic = (uint32_t)(((1ull << 32) + (uint64_t)a.tw - 1) / (uint64_t)a.tw);
-        a.tile_cap = (int)((max_nwin + a.tw - 1) / a.tw) + 1;
         // The candidates' left sums live off-chip (L2-resident scratch, written once and read once by the same wave) as
         // absolute 32-bit sums: 4 bytes per candidate instead of the 2 of the tile-relative 16-bit form, but the
         // change-point step then needs no per-candidate tile lookup (mul, mulhi, LDS read, add) and no Tc array in LDS.
-        // (The tile-relative 16-bit and the in-LDS layouts of rounds 1 - 2 are gone with their switches.)
+        // (The tile-relative 16-bit and the in-LDS layouts of rounds 1 - 2 are gone, switches and code: this is the one layout
+        // every kernel, the generic one included, writes and the change-point step reads.)
         // Round 4, the 40 MB this round trip adds to a config-2 launch's 128 MB at the memory side -- three ways around it, measured
         // (A/B on one box each, us per launch) and dropped:  (i) the block indexed by the HARDWARE WAVE SLOT (s_getreg HW_ID / XCC_ID:
         // 12 MB rewritten in place launch after launch instead of 20 MB per batch): 55.3 -> 54.4, config 4's sample 67.7 -> 66.7 -- but
@@ -332,7 +331,6 @@ inline std::string plan_geometry_core(ScanArgs& a, const tps_params& prm, int k,
         // a scalar branch to one v_mov per pass; 57 -> 73 VGPRs, still six waves per SIMD; emulation and all GPU tests green --
         // 58.2 against 54.8 (and 56.6 with the registers compiled in but switched off): the longer live ranges and the 16-way uniform
         // dispatch in the tile loop and the change-point step cost more than the round trip, which rides the Infinity Cache.
-        a.lc16 = 0;
         a.lc_global = 1;
         a.lc_stride = 2 * ((a.lc_cap + 1) & ~1);        // in 16-bit units
         // pair table (two positions per lookup) while it is small: k <= 4 -> at most 4 KB per workgroup
@@ -373,7 +371,7 @@ inline std::string plan_geometry_core(ScanArgs& a, const tps_params& prm, int k,
         if (wg_lds_dwords(a) <= budget_dw) return "";
         // does not fit (very long maxlengthtelo: the candidate sums of 4 reads outgrow LDS): the generic kernel,
         // whose tile size adapts, takes over
-        a.lc16 = 0; a.tile_cap = 0; a.tw = 0; a.tw_magic = 0; a.pair_n = 0; a.lc_global = 0; a.lc_stride = 0; a.pp_d = -1; a.so_fast = 0; a.seq_alias = 0; a.lut_fields = 0;
+        a.tw = 0; a.pair_n = 0; a.lc_global = 0; a.lc_stride = 0; a.pp_d = -1; a.so_fast = 0; a.seq_alias = 0; a.lut_fields = 0;
         a.lut16 = 0; a.xt_alias = 0; a.xt_own = 0; a.pair16 = 0;
     }
     a.variant = 0;

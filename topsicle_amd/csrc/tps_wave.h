@@ -88,8 +88,8 @@ __device__ __forceinline__ int tps_fresh_lane() {
 #define TPS_ISA_REGION(id) ((void)(id))
 #endif
 // (TPS_ISA_REGION: the parts of a read's program OUTSIDE the tile phases, for the same static budget -- 1 tile set-up, 2 the
-// tile's staging store, 3 the next tile's prefetch, 4 the tile dispatch, 5 the change point's float32 prefilter, 6 its float64
-// stage and wave reduction, 7 the exact tournament and the result)
+// tile's staging store, 3 the next tile's prefetch, 4 the tile dispatch, 5 the change point's float32 prefilter, 8 its one-lane
+// finish, 6 its float64 stage of every lane and the wave reduction, 7 the exact tournament and the result)
 // ... inside the per-pattern tiles (first tile of a read only): 6 = phase 1 done, 7 = windows done, 11 = rows out, 12 = candidates done
 #if defined(TPS_EMU) || !defined(TPS_STAMPS)
 #define TPS_PP_STAMP(i) ((void)0)
@@ -104,9 +104,12 @@ constexpr int NT = 64;                            // lanes that cooperate on one
 // counters the tests read (emulation only; the numbering is the tests'): 0 = per-pattern tiles, 1 = windows recounted there,
 // 2 = lanes of a per-pattern tile whose look-back could not fix their state, 3 = sums tiles with the window phase in 16-bit pairs
 // (and chain-parity repairs of the per-pattern tiles), 4 = exact change-point tournaments, 5 = sums tiles of a self-overlap
-// table with chains corrected, 6 = ... without a chain, 7 = sums tiles that store their candidates lane by lane
+// table with chains corrected, 6 = ... without a chain, 7 = sums tiles that store their candidates lane by lane, 8 = change points
+// finished by the one lane whose candidate passed the prefilter, 9 = ... by the float64 stage of every lane and the wave reduction,
+// 10 = prefilters that found a lane with two candidates inside the margin (crowded), 11 = prefilters run on the float64 D route
 #ifdef TPS_EMU
-inline int& emu_counter(int i) { static int c[8] = {0, 0, 0, 0, 0, 0, 0, 0}; return c[i]; }
+constexpr int EMU_COUNTERS = 16;
+inline int& emu_counter(int i) { static int c[EMU_COUNTERS] = {0}; return c[i]; }
 #define TPS_EMU_COUNT(i) ((void)++tps::emu_counter(i))
 #define TPS_EMU_COUNT_N(i, n) ((void)(tps::emu_counter(i) += (int)(n)))
 TPS_DEV int tps_fresh_lane() { return 0; }
@@ -193,9 +196,11 @@ TPS_DEV uint32_t wave_max_u32(const Lane<uint32_t>& x) {
 // the value lane `src` holds: src wave-uniform (v_readlane) / src per lane, inside a phase (ds_bpermute)
 #ifdef TPS_EMU
 TPS_DEV uint32_t wave_read_lane(const Lane<uint32_t>& x, int src) { return x.v[src]; }
+TPS_DEV int wave_read_lane(const Lane<int>& x, int src) { return x.v[src]; }
 TPS_DEV uint32_t wave_shuffle(const Lane<uint32_t>& x, int tid, int src) { (void)tid; return x.v[src]; }
 #else
 TPS_DEV uint32_t wave_read_lane(const Lane<uint32_t>& x, int src) { return (uint32_t)__builtin_amdgcn_readlane((int)x, src); }
+TPS_DEV int wave_read_lane(const Lane<int>& x, int src) { return __builtin_amdgcn_readlane(x, src); }
 TPS_DEV uint32_t wave_shuffle(const Lane<uint32_t>& x, int tid, int src) { (void)tid; return (uint32_t)__builtin_amdgcn_ds_bpermute(src << 2, (int)x); }
 #endif
 
@@ -224,6 +229,10 @@ TPS_DEV int popc(uint32_t x) { return __builtin_popcount(x); }
 TPS_DEV int ffs0(uint32_t x) { return __builtin_ctz(x); }
 TPS_DEV uint32_t uniform(uint32_t x) { return x; }
 TPS_DEV float rcp_f32(float x) { return 1.0f / x; }
+TPS_DEV float med3_f32(float a, float b, float c) {
+    const float lo = a < b ? a : b, hi = a < b ? b : a;
+    return c < lo ? lo : (c > hi ? hi : c);
+}
 TPS_DEV void lds_add(uint32_t* p, uint32_t v) { *p += v; }
 TPS_DEV void lds_or(uint32_t* p, uint32_t v) { *p |= v; }
 TPS_DEV uint32_t lds_add_ret(uint32_t* p, uint32_t v) { uint32_t o = *p; *p += v; return o; }
@@ -249,6 +258,8 @@ TPS_DEV int ffs0(uint32_t x) { return __builtin_ctz(x); }
 // a value every lane of the wave agrees on (e.g. read from LDS): tell the compiler it is scalar
 TPS_DEV uint32_t uniform(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
 TPS_DEV float rcp_f32(float x) { return __builtin_amdgcn_rcpf(x); }      // v_rcp_f32 (1 ulp)
+// the median of three numbers (none a NaN): v_med3_f32
+TPS_DEV float med3_f32(float a, float b, float c) { return __builtin_amdgcn_fmed3f(a, b, c); }
 TPS_DEV void lds_add(uint32_t* p, uint32_t v) { atomicAdd(p, v); }
 TPS_DEV void lds_or(uint32_t* p, uint32_t v) { atomicOr(p, v); }
 TPS_DEV uint32_t lds_add_ret(uint32_t* p, uint32_t v) { return atomicAdd(p, v); }
@@ -457,6 +468,19 @@ TPS_DEV void g_store16_clamped(uint32_t* base, int n_dw, int cdw, const u32x4& t
     v4u x;
     x.x = t.x; x.y = t.y; x.z = t.z; x.w = t.w;
     __builtin_amdgcn_raw_buffer_store_b128(x, rs, cdw * 4, 0, STORE_AUX);
+}
+#endif
+// v -> base[i] (dwords), dropped where i >= n: one range-checked buffer_store_dword through a wave-uniform descriptor over the n
+// dwords -- the bound costs no compare and no exec mask, and an index the caller sets to n (or beyond) is how a lane opts out.
+// Default cache policy: the wave reads these values back soon.
+#ifdef TPS_EMU
+TPS_DEV void g32_store_clamped(uint64_t base, uint32_t n, uint32_t i, uint32_t v) {
+    if (i < n) ((uint32_t*)(uintptr_t)base)[i] = v;
+}
+#else
+TPS_DEV void g32_store_clamped(uint64_t base, uint32_t n, uint32_t i, uint32_t v) {
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(uintptr_t)base, 0, (int)(n * 4u), 0x00020000);
+    __builtin_amdgcn_raw_buffer_store_b32(v, rs, (int)(i * 4u), 0, 0);
 }
 #endif
 
