@@ -140,7 +140,8 @@ int  tps_set_patterns(tps_ctx* ctx, const char* pats, int32_t n_patterns, int32_
  * of equal-length ACGT strings in reference order is legal: duplicates, k-mers that overlap themselves, narrow tables too.  While a
  * wide table is current tps_batch_scan launches ONE kernel for every slide and flag combination (tps_scan_kernel_wide: 64-bit k-mer
  * codes, a hash of the distinct codes, counts per window by sliding) and every call downstream of the scan works unchanged; the
- * one-shot calls scan with it too.  tps_batch_kmer_followers keeps n_fwd <= 15 and refuses a wide table.  A window that can hold more
+ * one-shot calls scan with it too.  tps_batch_kmer_followers keeps n_fwd <= 15 and refuses a wide table: its counterpart for the
+ * tables set here is tps_batch_kmer_followers_wide (n_fwd <= 32, any number of following letters).  A window that can hold more
  * than 255 occurrences of a k-mer ((window - 1) / k > 255), or a window / step-1 head of more than 32768 bases, is TPS_E_CAPACITY.
  * The next tps_set_patterns makes the narrow kernels current again; either call re-plans every resident batch. */
 int  tps_set_patterns_wide(tps_ctx* ctx, const char* pats, int32_t n_patterns, int32_t k);
@@ -252,6 +253,14 @@ int64_t tps_window_count(int64_t read_len, int32_t window, int32_t slide, int32_
  * follow <= 8, hi - lo <= 4096, n_fwd <= 15. */
 int  tps_batch_kmer_followers(tps_ctx* ctx, int32_t slot, int32_t n_fwd, int32_t follow, int32_t lo, int32_t hi,
                               int32_t min_len, uint32_t* picks, int64_t picks_words, int64_t* hist, int64_t hist_len);
+/* The same on the table of tps_set_patterns_wide (which takes narrow tables too; a table set with tps_set_patterns is
+ * TPS_E_PATTERN here): k <= TPS_WIDE_MAX_K, 1 <= n_fwd <= 32 with 2 n_fwd <= n_patterns, follow >= 0, hi - lo <= 4096 -- the
+ * doubled form of every motif of up to 32 letters at every k, however many letters follow the k-mer.  picks and hist are laid
+ * out as above and, on a table both calls accept, bit-identical.  hist has 4^follow + 1 bins: it may be non-NULL for
+ * follow <= 8 only (TPS_E_CAPACITY otherwise); for more following letters the caller counts the rows it builds from picks.
+ * One launch of tps_followers_kernel_wide. */
+int  tps_batch_kmer_followers_wide(tps_ctx* ctx, int32_t slot, int32_t n_fwd, int32_t follow, int32_t lo, int32_t hi,
+                                   int32_t min_len, uint32_t* picks, int64_t picks_words, int64_t* hist, int64_t hist_len);
 
 /* ---- measurement ----------------------------------------------------------------------- */
 /* hipEvent timings of the scan kernel launches since the last reset: number of launches,

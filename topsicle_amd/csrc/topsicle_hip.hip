@@ -76,6 +76,20 @@ extern "C" __global__ void __launch_bounds__(tps::NT * tps::WPG) tps_followers_k
     tps::followers_read(a, r, smem + wave * tps::FOLLOW_LDS_DW);
 }
 
+// ... on a wide table (tps_set_patterns_wide; followers_wide_read in csrc/tps_wide.h): the workgroup's copy of the table image first,
+// as in tps_scan_kernel_wide, then one wave per read
+extern "C" __global__ void __launch_bounds__(tps::NT * tps::WPG) tps_followers_kernel_wide(tps::FollowWideArgs a) {
+    __shared__ __attribute__((aligned(16))) uint32_t smem[tps::WIDE_IMG_DW + tps::WPG * tps::FOLLOWW_LDS_DW];
+    for (int c = 4 * (int)threadIdx.x; c < tps::WIDE_IMG_DW; c += 4 * tps::NT * tps::WPG)
+        *(uint4*)(smem + c) = *(const uint4*)(a.img + c);
+    __syncthreads();
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t r = (int64_t)blockIdx.x * tps::WPG + wave;
+    if (r >= a.n_reads) return;
+    tps::followers_wide_read(a, r, smem + tps::WIDE_IMG_DW + wave * tps::FOLLOWW_LDS_DW, smem);
+}
+static_assert(tps::WIDE_IMG_DW % 4 == 0 && tps::FOLLOWW_LDS_DW % 4 == 0, "16-byte LDS accesses");
+
 // ASCII -> packed batch (tps_pack.h), one workgroup per read, one thread per word of 16 bases.  Runs once per
 // tps_batch_upload, right behind the copy of the ASCII bytes; the scan kernels only ever see the packed batch.
 // bits 1-2 of an ASCII letter: A,C,T,G (either case) -> 0,1,2,3; one v_dot4_u32_u8 packs 4 bases; a v_perm rebuilds the
@@ -1254,6 +1268,54 @@ int tps_batch_kmer_followers(tps_ctx* c, int32_t slot, int32_t n_fwd, int32_t fo
     a.pat = c->pat;
     a.n_fwd = n_fwd; a.follow = follow; a.lo = lo; a.hi = hi; a.min_len = min_len; a.pw = pw; a.nbins = nbins;
     hipLaunchKernelGGL(tps_followers_kernel, dim3((unsigned)((n + tps::WPG - 1) / tps::WPG)), dim3(tps::NT * tps::WPG), 0, c->stream, a);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(picks, c->follow_picks.p, (size_t)want * 4, hipMemcpyDeviceToHost, c->stream));
+    if (hist) HIP_TRY(hipMemcpyAsync(hist, c->follow_hist.p, (size_t)hist_len * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return TPS_OK;
+}
+
+int tps_batch_kmer_followers_wide(tps_ctx* c, int32_t slot, int32_t n_fwd, int32_t follow, int32_t lo, int32_t hi, int32_t min_len,
+                                  uint32_t* picks, int64_t picks_words, int64_t* hist, int64_t hist_len) {
+    int rc;
+    if ((rc = bind(c))) return rc;
+    Slot* sl = get_slot(c, slot);
+    if (!sl) return TPS_E_ARG;
+    if (!c->have_pat || !c->wide_cur) return fail(TPS_E_PATTERN, "tps_batch_kmer_followers_wide needs a table set with tps_set_patterns_wide");
+    if (sl->n < 0) return fail(TPS_E_STATE, "no batch uploaded in this slot");
+    const tps_ctx::WideTable& wt = *c->wide_cur;
+    if (n_fwd < 1 || n_fwd > tps::FOLLOWW_MAX_FWD || 2 * n_fwd > wt.P)
+        return fail(TPS_E_ARG, "n_fwd must be 1..%d and the table must hold the complements behind the k-mers", tps::FOLLOWW_MAX_FWD);
+    if (follow < 0) return fail(TPS_E_ARG, "follow must not be negative");
+    if (lo < 0 || hi <= lo || hi - lo > tps::FOLLOW_MAX_SPAN) return fail(TPS_E_CAPACITY, "the scanned range [lo, hi) must hold 1..%d bases", tps::FOLLOW_MAX_SPAN);
+    if (hist && follow > 8) return fail(TPS_E_CAPACITY, "the followers histogram has 4^follow bins: follow must be 0..8 bases with it (pass no hist for more)");
+    const size_t lds_max = c->prop.sharedMemPerBlock > 0 ? c->prop.sharedMemPerBlock : 64 * 1024;
+    if ((size_t)tps::followers_wide_wg_lds_dwords() * 4 > lds_max)
+        return fail(TPS_E_CAPACITY, "the wide followers kernel needs %lld bytes of LDS per workgroup", (long long)tps::followers_wide_wg_lds_dwords() * 4);
+    const int pw = (hi - lo + 31) / 32;
+    const int64_t n = sl->n;
+    const int64_t want = n * 2 * n_fwd * pw;
+    if (!picks || picks_words != want) return fail(TPS_E_ARG, "picks must hold %lld words", (long long)want);
+    const int nbins = hist ? (1 << (2 * follow)) + 1 : 0;
+    if (hist && hist_len != 2ll * n_fwd * nbins) return fail(TPS_E_ARG, "hist must hold %lld counters", 2ll * n_fwd * nbins);
+    if (n == 0) { if (hist) memset(hist, 0, (size_t)hist_len * 8); return TPS_OK; }
+    if ((rc = c->follow_picks.ensure((size_t)want * 4))) return rc;
+    HIP_TRY(hipMemsetAsync(c->follow_picks.p, 0, (size_t)want * 4, c->stream));
+    if (hist) {
+        if ((rc = c->follow_hist.ensure((size_t)hist_len * 8))) return rc;
+        HIP_TRY(hipMemsetAsync(c->follow_hist.p, 0, (size_t)hist_len * 8, c->stream));
+    }
+    tps::FollowWideArgs a{};
+    a.seq2 = (const uint32_t*)sl->seq2.p;
+    a.inv = (const uint16_t*)sl->inv.p;
+    a.desc = (const tps_read_desc*)sl->desc.p;
+    a.img = (const uint32_t*)wt.dev.p;
+    a.picks = (uint32_t*)c->follow_picks.p;
+    a.hist = hist ? (unsigned long long*)c->follow_hist.p : nullptr;
+    a.n_reads = n;
+    a.pat = wt.pat;
+    a.n_fwd = n_fwd; a.follow = follow; a.lo = lo; a.hi = hi; a.min_len = min_len; a.pw = pw; a.nbins = nbins;
+    hipLaunchKernelGGL(tps_followers_kernel_wide, dim3((unsigned)((n + tps::WPG - 1) / tps::WPG)), dim3(tps::NT * tps::WPG), 0, c->stream, a);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(picks, c->follow_picks.p, (size_t)want * 4, hipMemcpyDeviceToHost, c->stream));
     if (hist) HIP_TRY(hipMemcpyAsync(hist, c->follow_hist.p, (size_t)hist_len * 8, hipMemcpyDeviceToHost, c->stream));

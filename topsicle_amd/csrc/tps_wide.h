@@ -366,4 +366,131 @@ TPS_DEV void wide_read(const WideArgs& a, int64_t r, uint32_t* lds_base, const u
 }
 static_assert(((XS_DW + 1) / 2) * 2 + MISC_DW + NT <= WIDE_CNT_DW, "the change point's scratch must fit the counter region");
 
+// ------------------------------------------------------------------ k-mer followers on a wide table (overview heat map)
+// followers_read (tps_device.h) for the tables of tps_set_patterns_wide: up to 32 k-mers of up to 32 letters and any number of
+// following letters.  Same semantics, same outputs: in bases [lo, hi) of a read and of its reversed string, the leftmost
+// non-overlapping matches of  kmer(.{f})  for patterns 0 .. n_fwd - 1 (strand 0) / n_fwd .. 2 n_fwd - 1 (strand 1), one bit per
+// match in picks[read][strand][pattern][pw], and -- where the caller asks and f <= 8 -- the (pattern x followers) histogram.
+// One wave per read.  What differs from the narrow kernel:
+//   * the look-up is wide_lookup's: one byte per position, group + 1.  A position holds one group; list pattern j reaches its
+//     group through pg[] (the two halves of the list may share groups: the 32-letter motif at k = 4 has 58 patterns, 54 groups);
+//   * no per-pattern occurrence bitmaps in LDS (32 x 4096 bits would be 16 KB per wave).  The byte map is turned into 32-bit
+//     occurrence words a block at a time: lane (pattern j, sub s) compares the 32 bytes of word w0 + s with ITS group -- the lanes
+//     of one s read the same 16 bytes (a broadcast) -- and leaves one word in LDS; then lane j < n_fwd walks its NT / n_fwd words of the
+//     block leftmost-first with its cursor in a register (a match consumes k + f positions), stores the pick word and, if wanted,
+//     adds every pick's followers to the histogram.  The start positions looked up are only those whose f followers lie inside
+//     [lo, min(L, hi)), so nothing past them can be picked.
+struct FollowWideArgs {
+    const uint32_t* seq2;
+    const uint16_t* inv;
+    const tps_read_desc* desc;
+    const uint32_t* img;         // the table image (WIDE_IMG_DW dwords)
+    uint32_t* picks;             // [n_reads][2][n_fwd][pw]
+    unsigned long long* hist;    // [2][n_fwd][nbins] or nullptr (the host passes it for follow <= 8 only)
+    int64_t n_reads;
+    WidePat pat;
+    int32_t n_fwd, follow, lo, hi, min_len, pw, nbins;
+};
+constexpr int FOLLOWW_MAX_FWD = 32;
+constexpr int FOLLOWW_PM_DW = FOLLOW_MAX_SPAN / 4 + 8;
+constexpr int FOLLOWW_VAL_DW = (FOLLOW_SEQ_DW / 2 + 4 + 3) & ~3;       // (a multiple of 4 dwords: the byte map behind it is read and written 16 bytes at a time)
+constexpr int FOLLOWW_PM_OFF = FOLLOW_SEQ_DW + FOLLOWW_VAL_DW;
+constexpr int FOLLOWW_OCC_OFF = FOLLOWW_PM_OFF + FOLLOWW_PM_DW;
+constexpr int FOLLOWW_LDS_DW = (FOLLOWW_OCC_OFF + NT + MISC_DW + 3) & ~3;    // per wave: seq, val, byte map, a block's words, flags
+static_assert(FOLLOW_SEQ_DW % 4 == 0 && FOLLOWW_PM_OFF % 4 == 0 && FOLLOWW_PM_DW % 4 == 0 && FOLLOWW_LDS_DW % 4 == 0 && WIDE_IMG_DW % 4 == 0,
+              "seq, the byte map and every wave's slice start on 16-byte boundaries (lds_load16 / lds_store16)");
+TPS_HD int64_t followers_wide_wg_lds_dwords() { return WIDE_IMG_DW + (int64_t)WPG * FOLLOWW_LDS_DW; }       // (does not depend on n_fwd or the span: sized for 32 and 4096)
+
+// bit j = byte j of the 16 equals g1 (g1 >= 1: an empty position never matches)
+TPS_DEV uint32_t wide_occ16(const u32x4& v, uint32_t g1) {
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+    uint32_t m = 0;
+    TPS_UNROLL
+    for (int j = 0; j < 16; ++j) m |= (((w[j >> 2] >> (8 * (j & 3))) & 255u) == g1 ? 1u : 0u) << j;
+    return m;
+}
+
+TPS_DEV void followers_wide_read(const FollowWideArgs& a, int64_t r, uint32_t* lds, const uint32_t* img) {
+    WideArgs wa{};                                         // what wide_lookup reads of it: the table's description
+    wa.pat = a.pat;
+    WideLds l{};
+    l.seq = lds;
+    l.val = (uint16_t*)(lds + FOLLOW_SEQ_DW);
+    l.pm = lds + FOLLOWW_PM_OFF;
+    uint32_t* occ = lds + FOLLOWW_OCC_OFF;
+    l.misc = occ + NT;
+    l.tab = img;
+    l.pg = (const uint8_t*)(img + WIDE_TAB_DW + WIDE_GM_DW);
+    const WidePat& pat = a.pat;
+    const int64_t woff = a.desc[r].word_off;
+    const int64_t L = a.desc[r].len;
+    const bool has_inv = (a.desc[r].flags & TPS_RD_HAS_INVALID) != 0;
+    if (L <= a.min_len) return;                    // (the host zeroed the picks)
+    const int64_t m = L < a.hi ? L : a.hi;
+    const int n = (int)(m - a.lo);
+    const int need = pat.k + a.follow;
+    if (n < need) return;
+    const int npos = n - need + 1;                 // start positions whose followers are inside the range
+    const int nch = (npos + 15) >> 4;              // chunks of 16 bytes wide_lookup fills
+    const int nwords = (npos + 31) >> 5;           // pick words that can hold a bit (<= pw; the others stay zero)
+    const int pw = a.pw;
+    const int n_fwd = a.n_fwd;
+    const int subs = NT / n_fwd;                   // words of a block
+    const uint32_t fmask = a.follow >= 16 ? 0xFFFFFFFFu : ((1u << (2 * a.follow)) - 1u);
+    Lane<int> sub, pat_j;                          // the lane's place in a block (one division per read, not per block)
+    TPS_LANES { TPS_AT(sub) = tid / n_fwd; TPS_AT(pat_j) = tid - TPS_AT(sub) * n_fwd; }
+    for (int strand = 0; strand < 2; ++strand) {
+        const Stage st = stage_plan(a.seq2, a.inv, woff, L, strand == 1, a.lo, 0, n);
+        TPS_PHASE { if (tid == 0) l.misc[M_INVALID] = 0; }
+        TPS_SYNC();
+        TPS_PHASE { stage_thread(st, has_inv, l.seq, l.val, st.nq + 1, &l.misc[M_INVALID], tid); }     // (+ a quad of zeros: the last chunk reads three dwords ahead)
+        TPS_SYNC();
+        const bool any_inv = has_inv && uniform(l.misc[M_INVALID]) != 0;
+        TPS_PHASE { wide_lookup(wa, l, st.delta, npos, any_inv, tid); }
+        TPS_SYNC();
+        Lane<int> cursor(0);
+        for (int w0 = 0; w0 < nwords; w0 += subs) {
+            TPS_PHASE {
+                const int s = TPS_AT(sub), pj = TPS_AT(pat_j), w = w0 + s;
+                if (s < subs && w < nwords) {
+                    const uint32_t g1 = (uint32_t)l.pg[strand * n_fwd + pj] + 1u;
+                    uint32_t mm = wide_occ16(lds_load16(l.pm + 8 * w), g1);
+                    if (2 * w + 1 < nch) mm |= wide_occ16(lds_load16(l.pm + 8 * w + 4), g1) << 16;
+                    occ[tid] = mm;
+                }
+            }
+            TPS_SYNC();
+            TPS_PHASE {
+                if (tid < n_fwd) {
+                    const uint64_t out_g = (uint64_t)(uintptr_t)(a.picks + ((r * 2 + strand) * n_fwd + tid) * (int64_t)pw);
+                    int cur = TPS_AT(cursor);
+                    for (int s = 0; s < subs && w0 + s < nwords; ++s) {
+                        const int w = w0 + s;
+                        uint32_t mm = occ[s * n_fwd + tid], picked = 0;
+                        while (mm) {
+                            const int bit = ffs0(mm);
+                            mm &= mm - 1;
+                            const int pos = 32 * w + bit;
+                            if (pos < cur) continue;
+                            picked |= 1u << bit;
+                            cur = pos + need;
+                            if (a.hist) {
+                                const int q = st.delta + pos + pat.k;
+                                uint32_t code = v_at(l.seq, q) & fmask;
+                                if (strand) code ^= 0xAAAAAAAAu & fmask;        // complement: A <-> T, C <-> G is code ^ 2
+                                const bool bad = any_inv && a.follow > 0 && invalid_at(l.val, q, a.follow);
+                                hist_add(&a.hist[((int64_t)strand * n_fwd + tid) * a.nbins + (bad ? (uint32_t)(a.nbins - 1) : code)]);
+                            }
+                        }
+                        g32_store(out_g, (uint32_t)w, picked);
+                    }
+                    TPS_AT(cursor) = cur;
+                }
+            }
+            TPS_SYNC();
+        }
+    }
+}
+static_assert(NT / FOLLOWW_MAX_FWD >= 1, "a block holds at least one word per pattern");
+
 }  // namespace tps

@@ -1,7 +1,8 @@
 """Topsicle/descriptive_plot.py's two exploratory plots (reference file:line cited per function).
 
 The heat map's counting -- every k-mer of the doubled motif followed by the next len(motif) - k bases, bases 100..2000 of
-both strands (descriptive_plot.py:259-291) -- runs on the GPU (tps_batch_kmer_followers): the kernel
+both strands (descriptive_plot.py:259-291) -- runs on the GPU (tps_batch_kmer_followers, or tps_batch_kmer_followers_wide for
+more than 15 k-mers, k-mers of more than 15 letters or more than 8 following bases): the kernel
 returns one bit per match position, from which the reference's DataFrame rows are built, and the crosstab itself.  Drawing
 uses matplotlib only.  The scatter of whole-motif hits (descriptive_plot.py:89-165: visualisation of at most 41 reads, no part
 of the hot path) is a host-side literal search over the few reads that passed the TRC filter on the GPU.
@@ -15,6 +16,7 @@ from .allsteps import pattern_scramble_telo
 
 _COMPLEMENT = str.maketrans("ACGT", "TGCA")
 LO, HI = 100, 2000               # the stretch of either end the heat map looks at (descriptive_plot.py:264-266)
+MAX_CELLS_ANNOTATED = 4096       # beyond 8 following letters the heat map writes its counts into the cells up to this many cells
 MAX_READS_DRAWN = 41             # the scatter stops after this many reads (descriptive_plot.py:146-150)
 
 
@@ -98,25 +100,32 @@ def pattern_matches(records, telopattern, telophrase, minSeqLength, engine=None)
     """The rows behind the heatmap (descriptive_plot.py:259-291): for every read longer than `minSeqLength`, in bases
     100..2000 of the read and of its reverse complement, every non-overlapping occurrence of each k-mer of the doubled
     motif followed by `len(motif) - k` more bases -> (k-mer, those bases, [read id]).  The matching runs on the GPU
-    (tps_batch_kmer_followers); returns (k-mers, rows, counts int64[n_kmers, 4**follow + 1] summed over both strands)."""
+    (tps_batch_kmer_followers / tps_batch_kmer_followers_wide); returns (k-mers, rows, counts int64[n_kmers, 4**follow + 1] summed
+    over both strands -- None where more than 8 bases follow: the crosstab would have 4**follow columns)."""
     from . import allsteps, hiplib
+    if len(telopattern) > hiplib.WIDE_MAX_K:
+        raise hiplib.TopsicleHipError(f"the k-mer / follower heat map takes motifs of up to {hiplib.WIDE_MAX_K} letters (tps_batch_kmer_followers_wide: "
+                                      f"n_fwd <= {hiplib.FOLLOW_WIDE_MAX_FWD}); {telopattern} has {len(telopattern)}")
     pattern_all = pattern_scramble_telo(telopattern, cut_length=telophrase)
     follow = int(len(telopattern) - telophrase)
     table = allsteps.patterns_to_search(telopattern, telophrase)
-    if len(pattern_all) > 15 or hiplib.needs_wide(table):
-        raise hiplib.TopsicleHipError(f"the k-mer / follower heat map takes up to 15 k-mers of up to {hiplib.MAX_K} letters (tps_batch_kmer_followers: "
-                                      f"n_fwd <= 15); {telopattern} at k = {telophrase} has {len(pattern_all)} -- the telomere scan itself takes motifs of up to "
-                                      f"{hiplib.WIDE_MAX_K} letters")
+    wide = len(pattern_all) > hiplib.FOLLOW_MAX_FWD or hiplib.needs_wide(table) or follow > hiplib.FOLLOW_HIST_MAX
     eng = engine or allsteps.get_engine()
-    eng.set_patterns(table)
+    if wide:                                       # more than 15 k-mers, k-mers of more than 15 letters or more than 8 followers: the wide kernel
+        eng.set_patterns_wide(table)
+    else:
+        eng.set_patterns(table)
     recs = [r for r in records if len(r.seq) > minSeqLength]
     if not recs:
         return pattern_all, [], None
     bases, offsets = hiplib.pack_reads([r.seq for r in recs])
     eng.upload(0, bases, offsets)
-    picks, hist = eng.kmer_followers(0, len(pattern_all), follow, LO, HI, minSeqLength)
+    if wide:
+        picks, hist = eng.kmer_followers_wide(0, len(pattern_all), follow, LO, HI, minSeqLength, follow <= hiplib.FOLLOW_HIST_MAX)
+    else:
+        picks, hist = eng.kmer_followers(0, len(pattern_all), follow, LO, HI, minSeqLength)
     rows = follower_rows([r.seq for r in recs], [r.id for r in recs], picks, pattern_all, follow)
-    return pattern_all, rows, hist.sum(axis=0)
+    return pattern_all, rows, None if hist is None else hist.sum(axis=0)
 
 
 def follower_labels(follow):
@@ -141,7 +150,9 @@ def heatmap_from_records(records, label, telopattern, telophrase, minSeqLength, 
     if grid.size:
         im = ax.imshow(grid.values, cmap="Blues", aspect="auto")
         fig.colorbar(im, ax=ax, shrink=0.75)
-        for i in range(grid.shape[0]):
+        follow = len(telopattern) - telophrase
+        # (more than 8 following letters -- only tps_batch_kmer_followers_wide takes them -- give thousands of rows: no room for numbers)
+        for i in range(grid.shape[0] if follow <= 8 or grid.size <= MAX_CELLS_ANNOTATED else 0):
             for j in range(grid.shape[1]):
                 ax.text(j, i, str(int(grid.values[i, j])), ha="center", va="center", fontsize=6)
         ax.set_xticks(range(grid.shape[1]))

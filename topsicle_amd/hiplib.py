@@ -18,11 +18,12 @@ LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
 F_STEP1, F_WINDOWS, F_BINSEG, F_STORE_SUMS, F_STORE_RAW, F_TAILS_IN = 1, 2, 4, 8, 16, 32
 MAX_K, MAX_PATTERNS, MAX_SLOTS = 15, 31, 16
 WIDE_MAX_K, WIDE_MAX_PATTERNS = 32, 64      # tps_set_patterns_wide (TPS_WIDE_MAX_K, TPS_WIDE_MAX_PATTERNS)
+FOLLOW_MAX_FWD, FOLLOW_WIDE_MAX_FWD, FOLLOW_HIST_MAX = 15, 32, 8      # k-mers tps_batch_kmer_followers / _wide take; most following letters with a histogram
 
 EXPORTS = [
     "tps_abi_version", "tps_device_count", "tps_ctx_create", "tps_ctx_destroy", "tps_last_error",
     "tps_set_patterns", "tps_set_patterns_wide", "tps_batch_upload", "tps_batch_upload_packed", "tps_batch_upload_nib4", "tps_batch_share", "tps_host_alloc", "tps_host_free",
-    "tps_batch_download_packed", "tps_batch_kmer_followers", "tps_batch_set_tails", "tps_batch_scan", "tps_sync",
+    "tps_batch_download_packed", "tps_batch_kmer_followers", "tps_batch_kmer_followers_wide", "tps_batch_set_tails", "tps_batch_scan", "tps_sync",
     "tps_batch_results", "tps_batch_window_offsets", "tps_batch_window_sums", "tps_batch_window_raw",
     "tps_batch_raw_to_fd", "tps_batch_trc_counts", "tps_trc_counts", "tps_window_counts", "tps_binseg_l2", "tps_binseg_l2_ties", "tps_batch_read_sums", "tps_window_count",
     "tps_kernel_time_ms", "tps_kernel_time_reset", "tps_device_info", "tps_batch_kernel_info", "tps_ctx_debug_option", "tps_debug_stamps_get",
@@ -94,6 +95,7 @@ def load_library(path: str | None = None) -> C.CDLL:
         "tps_host_free": (C.c_int, [vp, vp]),
         "tps_batch_download_packed": (C.c_int, [vp, i32, vp, vp, vp, i64, i64, C.POINTER(i64)]),
         "tps_batch_kmer_followers": (C.c_int, [vp, i32, i32, i32, i32, i32, i32, vp, i64, vp, i64]),
+        "tps_batch_kmer_followers_wide": (C.c_int, [vp, i32, i32, i32, i32, i32, i32, vp, i64, vp, i64]),
         "tps_batch_set_tails": (C.c_int, [vp, i32, vp]),
         "tps_batch_scan": (C.c_int, [vp, i32, C.POINTER(Params)]),
         "tps_sync": (C.c_int, [vp]),
@@ -327,7 +329,8 @@ class HipScanner:
 
     def set_patterns_wide(self, patterns: list[str]):
         """Up to WIDE_MAX_PATTERNS patterns of up to WIDE_MAX_K letters (tps_set_patterns_wide): scans then run the wide kernel,
-        everything downstream of the scan is unchanged.  Takes narrow tables too; kmer_followers refuses a wide table."""
+        everything downstream of the scan is unchanged.  Takes narrow tables too; kmer_followers refuses a wide table, kmer_followers_wide
+        is the call for it."""
         if not patterns:
             raise TopsicleHipError("empty pattern list")
         k = len(patterns[0])
@@ -404,6 +407,20 @@ class HipScanner:
         hist = np.zeros((2, n_fwd, 4 ** follow + 1), dtype=np.int64) if want_hist else None
         self._check(self.lib.tps_batch_kmer_followers(self._h, slot, n_fwd, follow, lo, hi, min_len, _ptr(picks), picks.size,
                                                       _ptr(hist), 0 if hist is None else hist.size))
+        return picks, hist
+
+    def kmer_followers_wide(self, slot: int, n_fwd: int, follow: int, lo: int = 100, hi: int = 2000, min_len: int = 0, want_hist: bool = True):
+        """kmer_followers on the table of set_patterns_wide (tps_batch_kmer_followers_wide): up to FOLLOW_WIDE_MAX_FWD k-mers of up to
+        WIDE_MAX_K letters, any number of following letters.  (picks uint32[n, 2, n_fwd, pw], hist int64[2, n_fwd, 4**follow + 1] or
+        None); the histogram has 4**follow bins and exists for follow <= FOLLOW_HIST_MAX only: ask for picks alone beyond that."""
+        if want_hist and follow > FOLLOW_HIST_MAX:
+            raise TopsicleHipError(f"the followers histogram has 4**follow bins: follow must be 0..{FOLLOW_HIST_MAX} with it, got {follow} (want_hist=False returns the picks alone)")
+        n = self._n[slot]
+        pw = max((hi - lo + 31) // 32, 0)              # (what the library refuses it refuses itself: n_fwd, follow, the range)
+        picks = np.zeros((n, 2, max(n_fwd, 0), pw), dtype=np.uint32)
+        hist = np.zeros((2, max(n_fwd, 0), 4 ** max(follow, 0) + 1), dtype=np.int64) if want_hist else None
+        self._check(self.lib.tps_batch_kmer_followers_wide(self._h, slot, n_fwd, follow, lo, hi, min_len, _ptr(picks), picks.size,
+                                                           _ptr(hist), 0 if hist is None else hist.size))
         return picks, hist
 
     def set_tails(self, slot: int, tails: np.ndarray):

@@ -3,7 +3,8 @@ read, and which bases follow each of its k-mers -- as a thin driver over the GPU
 
 Stages (the upstream script of the same name filters at a fixed TRC cutoff of 0.7 and then plots, overview_plot.py:63):
   1. one batched pass of the TRC step (kernel step 1) over every input file picks the reads to look at;
-  2. their k-mer / follower counts come from tps_batch_kmer_followers (descriptive_plot.pattern_matches);
+  2. their k-mer / follower counts come from tps_batch_kmer_followers / tps_batch_kmer_followers_wide (descriptive_plot.pattern_matches:
+     motifs of up to 32 letters at every k);
   3. matplotlib always draws descriptive_plot_<i>.png (the scatter of whole-motif hits, upstream overview_plot.py:92; host side,
      at most 41 reads) and, with --recfindingpattern, heatmap_<i>.png; --rawcount keeps the heat map's rows as CSV.
 Nothing is written to a temporary FASTA: the selected records stay in memory.
