@@ -15,7 +15,9 @@ instantiation (S, RPT, ROTZ, PAIR) its phases; `home` marks the instantiation of
 q a multiple of 8, pair table), the one config 2 runs five times per read.  The strided candidate pass is a loop (config 2:
 two passes per tile) that a tile which stores its candidates lane by lane skips.  `region*` rows are the parts of a read's
 program outside the tile phases (TPS_ISA_REGION): tile set-up, per tile the staging store, the prefetch and the dispatch,
-and the change point's stages; REGION_LOWER holds a written floor for each."""
+the change point's stages, and step 1 of the pair-table kernels (trc_decide_pairs: the static rows `stamp2` / `stamp3` behind
+it are the older routes, which such a kernel keeps for dirty heads and heads over the bound); REGION_LOWER holds a written
+floor for each."""
 import argparse
 import csv
 import os
@@ -36,7 +38,7 @@ STAMPS = {0: "entry", 1: "step1_stage_count", 2: "step1_decide", 3: "step1_decid
 # (the strided pass: none -- the lanes' own candidates need no second pass)
 LOWER = {1: 24 + 16, 2: 8 * 2 + 4 * 2, 3: 6 + 8 + 15, 4: 2, 6: 0, 5: 0}
 REGIONS = {1: "tile_setup", 2: "stage_store", 3: "prefetch", 4: "tile_dispatch", 5: "binseg_prefilter", 6: "binseg_f64_reduce",
-           7: "binseg_exact_result", 8: "binseg_one_lane"}
+           7: "binseg_exact_result", 8: "binseg_one_lane", 9: "step1_pairs"}
 # written floors of the regions, VALU per wave and execution (static rows hold BOTH sides of every branch, so a row can lie
 # above its floor by the side a read does not take):
 # 1 tile set-up: the first prefetch (a lane id, a compare, four zeros) -- everything else is wave-uniform: 6
@@ -55,7 +57,14 @@ REGIONS = {1: "tile_setup", 2: "stage_store", 3: "prefetch", 4: "tile_dispatch",
 # 6 one float64 candidate per lane (41, the fraction comparison as written) + one division (about 12) + three wave maxima
 #   (21) + two ballots' compares: 76 -- only reads with two or more close lanes, a crowded lane or no prefilter come here
 # 7 the exact tournament never runs without a tie; the gain's two divisions are counted with the finish that ran: 0
-REGION_LOWER = {1: 6, 2: 2, 3: 5, 4: 2, 5: 56 + 72 + 20, 6: 76, 7: 0, 8: 42}
+# 9 step 1 of the pair-table kernels (trc_decide_pairs), a table of at most 12 patterns: the lane's bit offset and word index (3),
+#   three funnel shifts of its bases, 16 pair lookups (a v_alignbit except at the two register boundaries, a v_and: 30), the
+#   carry-save adders (12 full adders of two v_bitop3, 2 half adders, one OR: 29), the fix-up lookup behind its lane compare
+#   (offset, index, funnel shift, v_and + v_or of the single table's base: 6) and the full lanes' compare; planes to bytes for
+#   three words (per word 4 x field, multiply, mask, and 3 merges: 15, 45), three row sums of 5 DPP adds and 2 readlanes (21):
+#   138.  The arg-max is scalar.  The counts' store (only when the caller asks for them: the lane's pattern and side, two 4-way
+#   word selects, shift, mask, address) is another 36 in the static row, and the fourth word (P > 12) another 15 + 7
+REGION_LOWER = {1: 6, 2: 2, 3: 5, 4: 2, 5: 56 + 72 + 20, 6: 76, 7: 0, 8: 42, 9: 138}
 
 
 def compile_isa(src, group, out):

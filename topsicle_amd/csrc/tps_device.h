@@ -796,6 +796,124 @@ TPS_DEV void trc_decide_packed(const ScanArgs& a, const Lds& l, const Stage& st_
 }
 #endif
 
+// The same decision in the pair-table kernels (tables without self-overlap or duplicates, clean heads), on the pair table that the
+// tiles keep at the workgroup's LDS offset 0: two positions per lookup, counts kept as bit planes.
+//   * Lane t of a side owns the start positions [32 t, 32 t + 32).  Only a FULL lane (all 32 below npos) runs the loop: its bases
+//     go into three registers once, then 16 lookups at its even positions -- one v_alignbit with an immediate and one v_and with
+//     the (k+1)-mer mask each (no table base to add).  An entry's mask holds the patterns at p and p + 1, never one pattern twice.
+//   * The rem = npos % 32 positions behind the last full lane are one lookup in the single table by lane j < rem of each side,
+//     outside the loop: nothing compares a position against npos.
+//   * The lane's (at most 17) masks are one-bit numbers per pattern; carry-save adders (xor3 / maj3: 12 full and 3 half adders)
+//     add them into bit planes, plane b = bit b of every pattern's count in this lane.  Occurrences of a pattern are at least k
+//     apart, so with k >= 3 (trc_pairs_ok) a lane's 32 positions and its fix-up hold at most 12 of one pattern: four planes, the
+//     fifth (the last half adder's carry) is always zero and is not computed.  The count halves of 32-bit entries ride along as
+//     garbage and are never looked at.
+//   * Planes to bytes, four patterns at a time: the four mask bits times 0x00204081 puts bit i at bit 8 i (and nothing else on a
+//     byte's bit 0), so P bytes come out in ceil(P / 4) words -- pattern p is byte p & 3 of word p >> 2; the fourth word only
+//     when P > 12 (uniform).  No squares, no even / odd nibble words.
+// Then the words' sums over each side's lanes, the arg-max on the scalar unit and the counts' store as in trc_decide_packed.
+// npos <= 255 k bounds a side's count of a pattern by 255 (occurrences of one pattern are at least k apart), npos <= 1024 is
+// what 32 lanes hold, k >= 3 what four planes hold.
+TPS_DEV bool trc_pairs_ok(const ScanArgs& a, int npos) { return a.pair_n != 0 && a.pat.so_mask == 0 && a.pat.P <= 15 && a.pat.k >= 3 && npos <= 1024 && npos <= 255 * a.pat.k; }
+template <bool M16>
+TPS_DEV void trc_decide_pairs(const ScanArgs& a, const Lds& l, const Stage& st_s, const Stage& st_e, int64_t r, uint32_t& ks, uint32_t& ke) {
+    const PatInfo& pat = a.pat;
+    constexpr int LS = M16 ? 1 : 2;                 // log2(bytes per table entry)
+    constexpr int MB = M16 ? 0 : 16;                // pattern 0's bit in an entry
+    const int P = pat.P;
+    const int npos = st_s.n - pat.k + 1 > 0 ? st_s.n - pat.k + 1 : 0;
+    const int full = npos >> 5, rem = npos & 31;
+    const bool w4 = P > 12;
+    const uint32_t amask = pat.kmask << LS;
+    const uint32_t amask2 = M16 ? ((pat.kmask << 3) | 0x6u) : ((pat.kmask << 4) | 0xCu);     // the (k+1)-mer's code << LS
+    Lane<uint32_t> x[4];
+    TPS_ISA_REGION(9);
+    TPS_PHASE {
+        const int side = tid >> 5, t = tid & 31;
+        const uint32_t* seq2 = l.seq2 + side * a.head_dw;
+        // the base BEFORE position 32 t goes to bit 0 (2-byte entries: its high bit), as in the tiles
+        const int bo = 2 * ((side ? st_e.delta : st_s.delta) + 32 * t) - LS;
+        uint32_t pl[4] = {0u, 0u, 0u, 0u};
+        if (t < rem) {                              // the remainder: position 32 full + t, a single lookup
+            const int bf = bo + 64 * (full - t) + 2 * t;
+            const uint32_t v_ = alignbit(seq2[(bf >> 5) + 1], seq2[bf >> 5], (uint32_t)(bf & 31));
+            pl[0] = M16 ? lut16_at(l.lut, v_, amask) : lut_at(l.lut, v_, amask);
+        }
+        if (t < full) {
+            const int idx = bo >> 5;                 // -1 for lane 0 of an aligned head: harmless
+            const uint32_t sh = (uint32_t)(bo & 31);
+            const uint32_t d0 = seq2[idx], d1 = seq2[idx + 1], d2 = seq2[idx + 2], d3 = seq2[idx + 3];
+            const uint32_t w0 = alignbit(d1, d0, sh), w1 = alignbit(d2, d1, sh), w2 = alignbit(d3, d2, sh);
+            uint32_t h[16];
+            TPS_UNROLL
+            for (int j = 0; j < 16; ++j) {
+                const uint32_t lo = j < 8 ? w0 : w1, hi = j < 8 ? w1 : w2;
+                const uint32_t v_ = (j & 7) == 0 ? lo : alignbit(hi, lo, 4u * (uint32_t)(j & 7));
+                h[j] = M16 ? lut16_at(l.lut2, v_, amask2) : lut_at(l.lut2, v_, amask2);
+            }
+            // weight 1: 17 inputs -> plane 0 and eight carries
+            uint32_t s[5], c1[8], c2[4], c3[2];
+            TPS_UNROLL
+            for (int i = 0; i < 5; ++i) { s[i] = xor3(h[3 * i], h[3 * i + 1], h[3 * i + 2]); c1[i] = maj3(h[3 * i], h[3 * i + 1], h[3 * i + 2]); }
+            const uint32_t s5 = xor3(s[0], s[1], s[2]), s6 = xor3(s[3], s[4], h[15]);
+            c1[5] = maj3(s[0], s[1], s[2]); c1[6] = maj3(s[3], s[4], h[15]);
+            c1[7] = maj3(s5, s6, pl[0]);
+            pl[0] = xor3(s5, s6, pl[0]);
+            // weight 2: eight carries -> plane 1 and four carries
+            const uint32_t t0 = xor3(c1[0], c1[1], c1[2]), t1 = xor3(c1[3], c1[4], c1[5]);
+            c2[0] = maj3(c1[0], c1[1], c1[2]); c2[1] = maj3(c1[3], c1[4], c1[5]);
+            const uint32_t t2 = xor3(t0, t1, c1[6]);
+            c2[2] = maj3(t0, t1, c1[6]);
+            pl[1] = t2 ^ c1[7]; c2[3] = t2 & c1[7];
+            // weight 4 and 8 (the two weight-8 carries are never both set: a count stays below 16)
+            const uint32_t u0 = xor3(c2[0], c2[1], c2[2]);
+            c3[0] = maj3(c2[0], c2[1], c2[2]);
+            pl[2] = u0 ^ c2[3]; c3[1] = u0 & c2[3];
+            pl[3] = c3[0] | c3[1];
+        }
+        TPS_UNROLL
+        for (int g = 0; g < 4; ++g) {
+            uint32_t acc = 0;
+            if (g < 3 || w4) {
+                TPS_UNROLL
+                for (int b = 3; b >= 0; --b)
+                    acc = (acc << 1) + (mul24((pl[b] >> (MB + 4 * g)) & 15u, 0x00204081u) & 0x01010101u);
+            }
+            TPS_AT(x[g]) = acc;
+        }
+    }
+    uint32_t s0[4], s1[4];
+    TPS_UNROLL
+    for (int g = 0; g < 4; ++g) {
+        s0[g] = s1[g] = 0;
+        if (g < 3 || w4) wave_half_sums(x[g], s0[g], s1[g]);
+    }
+    uint32_t bs = 0, be = 0;
+    TPS_UNROLL
+    for (int p = 0; p < 15; ++p) {
+        if (p < P) {                                  // uniform
+            const uint32_t c0 = (s0[p >> 2] >> (8 * (p & 3))) & 255u, c1 = (s1[p >> 2] >> (8 * (p & 3))) & 255u;
+            const uint32_t k0 = (c0 << 5) | (uint32_t)(31 - p), k1 = (c1 << 5) | (uint32_t)(31 - p);
+            bs = k0 > bs ? k0 : bs;
+            be = k1 > be ? k1 : be;
+        }
+    }
+    ks = bs;
+    ke = be;
+    if (a.c_start) {                                  // the per-pattern counts of both heads, if the caller asked for them
+        TPS_LANES {
+            const int side = tid >> 5, p = tid & 31;
+            if (p < P) {
+                const int wi = p >> 2;
+                const uint32_t w0 = wi == 0 ? s0[0] : wi == 1 ? s0[1] : wi == 2 ? s0[2] : s0[3];
+                const uint32_t w1 = wi == 0 ? s1[0] : wi == 1 ? s1[1] : wi == 2 ? s1[2] : s1[3];
+                const uint32_t c = ((side ? w1 : w0) >> (8 * (p & 3))) & 255u;
+                (side ? a.c_end : a.c_start)[r * P + p] = (int32_t)c;
+            }
+        }
+    }
+}
+
 // Thread (side, p): sum the private histograms; if pattern p has overlapping occurrences, recount
 // it leftmost-non-overlapping (sequential, rare); publish the count and bid for the side's
 // arg-max with key = count << 5 | (31 - p), so the FIRST pattern with the largest count wins.
@@ -3081,9 +3199,17 @@ TPS_DEV void scan_read(const ScanArgs& a, int64_t r, uint32_t* lds_base, uint32_
         if constexpr (SV != 0) packed1 = clean && trc_packed_ok(a, st_s.n - pat.k + 1);
         uint32_t ks = 0, ke = 0;
         bool decided = false;
+        if constexpr (SV != 0 && !SO && !RAW && PAIR) {
+            if (clean && trc_pairs_ok(a, st_s.n - pat.k + 1)) {
+                TPS_EMU_COUNT(12);
+                trc_decide_pairs<P16K>(a, l, st_s, st_e, r, ks, ke);
+                decided = true;
+                TPS_STAMP(3);
+            }
+        }
 #ifndef TPS_EMU              /* (trc_decide_packed is device-only: DESIGN.md, "One kernel text") */
         if constexpr (SV != 0 && !SO && !RAW) {
-            if (packed1) {
+            if (packed1 && !decided) {
                 trc_decide_packed<P16K ? 2 : 0>(a, l, st_s, st_e, r, ks, ke);
                 decided = true;
                 TPS_STAMP(3);
@@ -3092,6 +3218,7 @@ TPS_DEV void scan_read(const ScanArgs& a, int64_t r, uint32_t* lds_base, uint32_
 #endif
         if (decided) {
         } else if (packed1) {
+            TPS_EMU_COUNT(13);
             bool fld = false;
             if constexpr (RAW) fld = a.lut_fields != 0;
             if (fld) {
@@ -3109,6 +3236,7 @@ TPS_DEV void scan_read(const ScanArgs& a, int64_t r, uint32_t* lds_base, uint32_
             TPS_STAMP(3);
             TPS_PHASE { trc_sum_packed(a, l, st_s, st_e, r, tid); }
         } else {
+            TPS_EMU_COUNT(14);
             TPS_PHASE { for (int i = tid; i < HIST_DW; i += NT) l.blk[i] = 0; }
             TPS_SYNC();
             if (plain) {

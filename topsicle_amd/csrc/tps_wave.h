@@ -89,7 +89,8 @@ __device__ __forceinline__ int tps_fresh_lane() {
 #endif
 // (TPS_ISA_REGION: the parts of a read's program OUTSIDE the tile phases, for the same static budget -- 1 tile set-up, 2 the
 // tile's staging store, 3 the next tile's prefetch, 4 the tile dispatch, 5 the change point's float32 prefilter, 8 its one-lane
-// finish, 6 its float64 stage of every lane and the wave reduction, 7 the exact tournament and the result)
+// finish, 6 its float64 stage of every lane and the wave reduction, 7 the exact tournament and the result, 9 step 1 of the
+// pair-table kernels (trc_decide_pairs))
 // ... inside the per-pattern tiles (first tile of a read only): 6 = phase 1 done, 7 = windows done, 11 = rows out, 12 = candidates done
 #if defined(TPS_EMU) || !defined(TPS_STAMPS)
 #define TPS_PP_STAMP(i) ((void)0)
@@ -106,7 +107,9 @@ constexpr int NT = 64;                            // lanes that cooperate on one
 // (and chain-parity repairs of the per-pattern tiles), 4 = exact change-point tournaments, 5 = sums tiles of a self-overlap
 // table with chains corrected, 6 = ... without a chain, 7 = sums tiles that store their candidates lane by lane, 8 = change points
 // finished by the one lane whose candidate passed the prefilter, 9 = ... by the float64 stage of every lane and the wave reduction,
-// 10 = prefilters that found a lane with two candidates inside the margin (crowded), 11 = prefilters run on the float64 D route
+// 10 = prefilters that found a lane with two candidates inside the margin (crowded), 11 = prefilters run on the float64 D route,
+// the route a read's step 1 took: 12 = trc_decide_pairs, 13 = the packed counts (trc_count_packed; the device's
+// trc_decide_packed among them), 14 = the histograms (trc_count_thread)
 #ifdef TPS_EMU
 constexpr int EMU_COUNTERS = 16;
 inline int& emu_counter(int i) { static int c[EMU_COUNTERS] = {0}; return c[i]; }
@@ -191,6 +194,25 @@ TPS_DEV uint32_t wave_max_u32(const Lane<uint32_t>& x) {
     v = mx(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false));   // row_bcast:15 -> rows 1, 3
     v = mx(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false));   // row_bcast:31 -> rows 2, 3
     return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
+}
+#endif
+// the sums of a per-lane value over lanes 0 .. 31 (lo) and over lanes 32 .. 63 (hi), both wave-uniform (device: DPP row sums, the
+// rows' totals broadcast into the next row, lanes 31 and 63 read)
+#ifdef TPS_EMU
+TPS_DEV void wave_half_sums(const Lane<uint32_t>& x, uint32_t& lo, uint32_t& hi) {
+    lo = hi = 0;
+    for (int t = 0; t < NT / 2; ++t) { lo += x.v[t]; hi += x.v[t + NT / 2]; }
+}
+#else
+TPS_DEV void wave_half_sums(const Lane<uint32_t>& x, uint32_t& lo, uint32_t& hi) {
+    uint32_t v = x;
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);   // row_shr:1
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);   // row_shr:2
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false);   // row_shr:4
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false);   // row_shr:8
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);   // row_bcast:15 -> rows 1, 3
+    lo = (uint32_t)__builtin_amdgcn_readlane((int)v, 31);
+    hi = (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
 }
 #endif
 // the value lane `src` holds: src wave-uniform (v_readlane) / src per lane, inside a phase (ds_bpermute)
@@ -392,6 +414,16 @@ TPS_DEV uint32_t mul24(uint32_t x, uint32_t y) { return (x & 0xFFFFFFu) * (y & 0
 TPS_DEV uint32_t add_bytes(uint32_t v, uint32_t acc) { return acc + (v & 255u) + ((v >> 8) & 255u) + ((v >> 16) & 255u) + (v >> 24); }
 #else
 TPS_DEV uint32_t add_bytes(uint32_t v, uint32_t acc) { return __builtin_amdgcn_sad_u8(v, 0u, acc); }
+#endif
+
+// a full adder over 32 independent bit positions: the sum bit a ^ b ^ c and the carry (the majority of the three), one
+// v_bitop3_b32 each (written out in C++ the compiler shares a ^ b between the two and ends with five instructions)
+#ifdef TPS_EMU
+TPS_DEV uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) { return a ^ b ^ c; }
+TPS_DEV uint32_t maj3(uint32_t a, uint32_t b, uint32_t c) { return (a & b) | (c & (a | b)); }
+#else
+TPS_DEV uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) { return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96); }
+TPS_DEV uint32_t maj3(uint32_t a, uint32_t b, uint32_t c) { return __builtin_amdgcn_bitop3_b32(a, b, c, 0xE8); }
 #endif
 
 // two 16-bit lanes in one word (lane 0 = bits 0 .. 15): lane-wise a - b; a + the low half of b in both
