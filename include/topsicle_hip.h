@@ -262,6 +262,35 @@ int  tps_batch_kmer_followers(tps_ctx* ctx, int32_t slot, int32_t n_fwd, int32_t
 int  tps_batch_kmer_followers_wide(tps_ctx* ctx, int32_t slot, int32_t n_fwd, int32_t follow, int32_t lo, int32_t hi,
                                    int32_t min_len, uint32_t* picks, int64_t picks_words, int64_t* hist, int64_t hist_len);
 
+/* ---- motif census (finding the motif from the reads) ------------------------------------- */
+/* What repeats at the ends of the reads, without a pattern table (tps_set_patterns need not have been called; the reference
+ * leaves this to other tools: its README names Tandem Repeats Finder and tidk).  For every read of the resident batch longer
+ * than min_len and each end e, let h = bases [lo, min(L, hi)) of the upper-cased read (e = 0) or of its reverse complement
+ * (e = 1) -- both "telomere first", as step 1 looks at them -- and n = len(h).  For a period u in [u_min, u_max], w = min(u, 8):
+ *   eq_u[i]  = 1 iff i + u < n and h[i], h[i + u] are both one of ACGT and equal
+ *   per_u[i] = 1 iff i + u + w <= n and eq_u[i .. i + w - 1] are all 1        (the w-mer at i recurs u bases on)
+ *   C_u      = sum over i of per_u[i]
+ * u* is the period with the largest C_u (ties: the smallest u); the run is the longest maximal run of consecutive i with
+ * per_u*[i] = 1 (ties: the leftmost).  w stops at 8 so that a long motif keeps its support at nanopore error rates.
+ *   hits   tps_motif_hit[n_reads][2]: period = u*, support = C_u*, run_start / run_len = the run, n_bases = n, unit = the u*
+ *          letters h[run_start .. run_start + u*) as 2-bit codes (A C T G = 0 1 2 3, letter j in bits [2j, 2j+1]; a letter
+ *          of the unit that is not ACGT -- possible behind its first 8 -- has the code (ASCII >> 1) & 3 of the packed batch,
+ *          complemented at e = 1).  All zeros where no C_u is positive, and for reads of min_len bases or fewer.
+ *   counts int32[n_reads][2][u_max - u_min + 1] or NULL: every C_u.
+ * 1 <= u_min <= u_max <= 32 (TPS_E_ARG), hi - lo <= 4096 (TPS_E_CAPACITY).  What a caller makes of the hits (a floor on the
+ * support, the vote over the read ends) is its own: topsicle_amd.motif.  One launch; returns when the outputs are in place. */
+typedef struct tps_motif_hit {        /* 32 bytes */
+    uint64_t unit;
+    int32_t period;
+    int32_t support;
+    int32_t run_start;
+    int32_t run_len;
+    int32_t n_bases;
+    int32_t reserved;
+} tps_motif_hit;
+int  tps_batch_motif_census(tps_ctx* ctx, int32_t slot, int32_t u_min, int32_t u_max, int32_t lo, int32_t hi, int32_t min_len,
+                            tps_motif_hit* hits, int64_t n_hits, int32_t* counts, int64_t counts_len);
+
 /* ---- measurement ----------------------------------------------------------------------- */
 /* hipEvent timings of the scan kernel launches since the last reset: number of launches,
  * total and mean milliseconds (events are recorded on the stream the kernel runs on). */

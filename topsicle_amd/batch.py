@@ -49,6 +49,41 @@ class Job:
         self.raw_sink = raw_sink if want_raw else None
 
 
+class CensusJob:
+    """A motif census of the resident batch in place of a scan (motif.find_motif; HipScanner.motif_census): no pattern table, one
+    hit per read end.  It goes through the same readers, staging buffers and worker threads as a Job; whole reads only (the prm it
+    carries asks for no step 1, so _heads_mode never takes the two-pass route)."""
+
+    def __init__(self, u_min=4, u_max=32, lo=0, hi=1000, min_len=0):
+        self.u_min, self.u_max, self.lo, self.hi, self.min_len = int(u_min), int(u_max), int(lo), int(hi), int(min_len)
+        self.patterns, self.prm = [], hiplib.make_params(no_bp=0, min_len=self.min_len, flags=0)
+        self.want_sums = self.want_raw = False
+        self.raw_sink = None
+
+
+def census_jobs(engine, recs, jobs, slot: int = 0):
+    """Upload once, then one census per job.  Returns [(hits, None, None, None), ...] in job order (the shape scan_jobs returns)."""
+    try:
+        upload_batch(engine, recs, slot)
+        out = []
+        for n, job in enumerate(jobs):
+            hits, _ = engine.motif_census(slot, job.u_min, job.u_max, job.lo, job.hi, job.min_len)      # (returns with the hits in place)
+            if n == 0 and hasattr(recs, "release"):
+                recs.release()             # the upload has completed: the staging buffers go back to the reader
+            out.append((hits, None, None, None))
+        if not jobs and hasattr(recs, "release"):
+            recs.release()
+    except BaseException:
+        try:
+            engine.sync()                  # an asynchronous upload may still be in use
+        except Exception:
+            pass
+        if hasattr(recs, "release"):
+            recs.release()
+        raise
+    return out
+
+
 class RawKept:
     """What a job with a raw_sink returns in place of the raw rows: `keep` = the reads (indices into the batch) whose rows the
     sink has written, in that order."""
@@ -226,6 +261,8 @@ def scan_jobs(engine, recs, jobs, slot: int = 0, seq=None):
     batch.SEQUENTIAL_TABLES scans them back to back on the one context instead (the A/B switch)."""
     if getattr(recs, "full_len", None) is not None:
         return scan_jobs_heads(engine, recs, jobs, slot, seq)
+    if jobs and all(isinstance(j, CensusJob) for j in jobs):
+        return census_jobs(engine, recs, jobs, slot)
     out = []
     concurrent = len(jobs) > 1 and hasattr(engine, "helper") and not SEQUENTIAL_TABLES
     engines = [engine] + ([engine.helper(j) for j in range(len(jobs) - 1)] if concurrent else [engine] * (len(jobs) - 1))

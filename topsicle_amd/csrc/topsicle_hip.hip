@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "tps_device.h"
+#include "tps_motif.h"
 #include "tps_pack.h"
 #include "tps_plan.h"
 #include "tps_wide.h"
@@ -89,6 +90,18 @@ extern "C" __global__ void __launch_bounds__(tps::NT * tps::WPG) tps_followers_k
     tps::followers_wide_read(a, r, smem + tps::WIDE_IMG_DW + wave * tps::FOLLOWW_LDS_DW, smem);
 }
 static_assert(tps::WIDE_IMG_DW % 4 == 0 && tps::FOLLOWW_LDS_DW % 4 == 0, "16-byte LDS accesses");
+
+// The motif census (tps_batch_motif_census; motif_read in csrc/tps_motif.h): no table, one wave per read.  (Inside the namespace:
+// the library exports tps_* names for the C ABI and the scan kernels' stubs only.)
+namespace tps {
+__global__ void __launch_bounds__(NT * WPG) motif_census_kernel(MotifArgs a) {
+    __shared__ __attribute__((aligned(16))) uint32_t smem[WPG * MOTIF_LDS_DW];
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t r = (int64_t)blockIdx.x * WPG + wave;
+    if (r >= a.n_reads) return;
+    motif_read(a, r, smem + wave * MOTIF_LDS_DW);
+}
+}  // namespace tps
 
 // ASCII -> packed batch (tps_pack.h), one workgroup per read, one thread per word of 16 bases.  Runs once per
 // tps_batch_upload, right behind the copy of the ASCII bytes; the scan kernels only ever see the packed batch.
@@ -315,6 +328,7 @@ struct tps_ctx {
     size_t lds_set_wide = 0;
     size_t table_rr = 0;
     DevBuf follow_picks, follow_hist; // outputs of tps_batch_kmer_followers
+    DevBuf motif_hits, motif_counts;  // outputs of tps_batch_motif_census
     DevBuf ascii, ascii_off;          // staging of tps_batch_upload: ASCII bases + offsets, packed on the device right after the copy
     DevBuf nib, nib_src;              // staging of tps_batch_upload_nib4: BAM base codes + where each read's are, expanded right after the copy
     std::set<void*> pinned;           // host buffers handed out by tps_host_alloc
@@ -989,6 +1003,8 @@ int tps_ctx_destroy(tps_ctx* c) {
     c->nib_src.release();
     c->follow_picks.release();
     c->follow_hist.release();
+    c->motif_hits.release();
+    c->motif_counts.release();
     for (void* hp : c->pinned) {
         { std::lock_guard<std::mutex> lk(g_pinned_mu); g_pinned.erase((uintptr_t)hp); }
         (void)hipHostFree(hp);
@@ -1319,6 +1335,44 @@ int tps_batch_kmer_followers_wide(tps_ctx* c, int32_t slot, int32_t n_fwd, int32
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(picks, c->follow_picks.p, (size_t)want * 4, hipMemcpyDeviceToHost, c->stream));
     if (hist) HIP_TRY(hipMemcpyAsync(hist, c->follow_hist.p, (size_t)hist_len * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return TPS_OK;
+}
+
+int tps_batch_motif_census(tps_ctx* c, int32_t slot, int32_t u_min, int32_t u_max, int32_t lo, int32_t hi, int32_t min_len,
+                           tps_motif_hit* hits, int64_t n_hits, int32_t* counts, int64_t counts_len) {
+    int rc;
+    if ((rc = bind(c))) return rc;
+    Slot* sl = get_slot(c, slot);
+    if (!sl) return TPS_E_ARG;
+    if (sl->n < 0) return fail(TPS_E_STATE, "no batch uploaded in this slot");
+    if (u_min < 1 || u_max < u_min || u_max > tps::MOTIF_MAX_PERIOD) return fail(TPS_E_ARG, "the periods must be 1 <= u_min <= u_max <= %d", tps::MOTIF_MAX_PERIOD);
+    if (lo < 0 || hi <= lo || hi - lo > tps::FOLLOW_MAX_SPAN) return fail(TPS_E_CAPACITY, "the scanned range [lo, hi) must hold 1..%d bases", tps::FOLLOW_MAX_SPAN);
+    const int64_t n = sl->n;
+    const int nu = u_max - u_min + 1;
+    if ((!hits && n > 0) || n_hits != 2 * n) return fail(TPS_E_ARG, "hits must hold %lld entries", (long long)(2 * n));
+    if (counts && counts_len != 2 * n * nu) return fail(TPS_E_ARG, "counts must hold %lld counters", (long long)(2 * n * nu));
+    if (n == 0) return TPS_OK;
+    // (the table, the slot's scan outputs and its plan are not touched: a scan before and after the census gives the same results)
+    const size_t hit_bytes = (size_t)n * 2 * sizeof(tps_motif_hit), cnt_bytes = (size_t)n * 2 * nu * 4;
+    if ((rc = c->motif_hits.ensure(hit_bytes))) return rc;
+    HIP_TRY(hipMemsetAsync(c->motif_hits.p, 0, hit_bytes, c->stream));
+    if (counts) {
+        if ((rc = c->motif_counts.ensure(cnt_bytes))) return rc;
+        HIP_TRY(hipMemsetAsync(c->motif_counts.p, 0, cnt_bytes, c->stream));
+    }
+    tps::MotifArgs a{};
+    a.seq2 = (const uint32_t*)sl->seq2.p;
+    a.inv = (const uint16_t*)sl->inv.p;
+    a.desc = (const tps_read_desc*)sl->desc.p;
+    a.hits = (tps_motif_hit*)c->motif_hits.p;
+    a.counts = counts ? (int32_t*)c->motif_counts.p : nullptr;
+    a.n_reads = n;
+    a.u_min = u_min; a.u_max = u_max; a.lo = lo; a.hi = hi; a.min_len = min_len;
+    hipLaunchKernelGGL(tps::motif_census_kernel, dim3((unsigned)((n + tps::WPG - 1) / tps::WPG)), dim3(tps::NT * tps::WPG), 0, c->stream, a);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(hits, c->motif_hits.p, hit_bytes, hipMemcpyDeviceToHost, c->stream));
+    if (counts) HIP_TRY(hipMemcpyAsync(counts, c->motif_counts.p, cnt_bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return TPS_OK;
 }

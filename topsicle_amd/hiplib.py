@@ -23,7 +23,7 @@ FOLLOW_MAX_FWD, FOLLOW_WIDE_MAX_FWD, FOLLOW_HIST_MAX = 15, 32, 8      # k-mers t
 EXPORTS = [
     "tps_abi_version", "tps_device_count", "tps_ctx_create", "tps_ctx_destroy", "tps_last_error",
     "tps_set_patterns", "tps_set_patterns_wide", "tps_batch_upload", "tps_batch_upload_packed", "tps_batch_upload_nib4", "tps_batch_share", "tps_host_alloc", "tps_host_free",
-    "tps_batch_download_packed", "tps_batch_kmer_followers", "tps_batch_kmer_followers_wide", "tps_batch_set_tails", "tps_batch_scan", "tps_sync",
+    "tps_batch_download_packed", "tps_batch_kmer_followers", "tps_batch_kmer_followers_wide", "tps_batch_motif_census", "tps_batch_set_tails", "tps_batch_scan", "tps_sync",
     "tps_batch_results", "tps_batch_window_offsets", "tps_batch_window_sums", "tps_batch_window_raw",
     "tps_batch_raw_to_fd", "tps_batch_trc_counts", "tps_trc_counts", "tps_window_counts", "tps_binseg_l2", "tps_binseg_l2_ties", "tps_batch_read_sums", "tps_window_count",
     "tps_kernel_time_ms", "tps_kernel_time_reset", "tps_device_info", "tps_batch_kernel_info", "tps_ctx_debug_option", "tps_debug_stamps_get",
@@ -54,6 +54,10 @@ RESULT_DTYPE = np.dtype([("best_start", "<i4"), ("best_start_idx", "<i4"), ("bes
                          ("best_end_idx", "<i4"), ("tail", "<i4"), ("pass", "<i4"), ("n_win", "<i4"),
                          ("bkp", "<i4"), ("gain", "<f8"), ("flags", "<u4"), ("reserved", "<u4")], align=True)
 assert RESULT_DTYPE.itemsize == 48
+MOTIF_HIT_DTYPE = np.dtype([("unit", "<u8"), ("period", "<i4"), ("support", "<i4"), ("run_start", "<i4"), ("run_len", "<i4"),
+                            ("n_bases", "<i4"), ("reserved", "<i4")], align=True)                          # struct tps_motif_hit
+assert MOTIF_HIT_DTYPE.itemsize == 32
+MOTIF_MAX_PERIOD, MOTIF_MAX_SPAN = 32, 4096      # tps_batch_motif_census: the longest period, the most bases of a read end
 RES_TIE = 1            # TPS_RES_TIE: the exact tournament decided the change-point (candidates within float64 noise of each other)
 
 
@@ -96,6 +100,7 @@ def load_library(path: str | None = None) -> C.CDLL:
         "tps_batch_download_packed": (C.c_int, [vp, i32, vp, vp, vp, i64, i64, C.POINTER(i64)]),
         "tps_batch_kmer_followers": (C.c_int, [vp, i32, i32, i32, i32, i32, i32, vp, i64, vp, i64]),
         "tps_batch_kmer_followers_wide": (C.c_int, [vp, i32, i32, i32, i32, i32, i32, vp, i64, vp, i64]),
+        "tps_batch_motif_census": (C.c_int, [vp, i32, i32, i32, i32, i32, i32, vp, i64, vp, i64]),
         "tps_batch_set_tails": (C.c_int, [vp, i32, vp]),
         "tps_batch_scan": (C.c_int, [vp, i32, C.POINTER(Params)]),
         "tps_sync": (C.c_int, [vp]),
@@ -422,6 +427,18 @@ class HipScanner:
         self._check(self.lib.tps_batch_kmer_followers_wide(self._h, slot, n_fwd, follow, lo, hi, min_len, _ptr(picks), picks.size,
                                                            _ptr(hist), 0 if hist is None else hist.size))
         return picks, hist
+
+    def motif_census(self, slot: int, u_min: int = 4, u_max: int = 32, lo: int = 0, hi: int = 1000, min_len: int = 0, want_counts: bool = False):
+        """What repeats at the read ends of the resident batch, no pattern table needed (tps_batch_motif_census; the rule is in
+        include/topsicle_hip.h): hits MOTIF_HIT_DTYPE[n, 2] -- per read and end (0 = the read's start, 1 = the start of its reverse
+        complement) the period with the most recurring 8-mers, that count, the longest run and the unit it starts with -- and, with
+        want_counts, counts int32[n, 2, u_max - u_min + 1] of every period (None otherwise)."""
+        n = self._n[slot]
+        hits = np.zeros((n, 2), dtype=MOTIF_HIT_DTYPE)
+        counts = np.zeros((n, 2, max(u_max - u_min + 1, 0)), dtype=np.int32) if want_counts else None      # (a bad period range is the library's to refuse)
+        self._check(self.lib.tps_batch_motif_census(self._h, slot, u_min, u_max, lo, hi, min_len, _ptr(hits), hits.size,
+                                                    _ptr(counts), 0 if counts is None else counts.size))
+        return hits, counts
 
     def set_tails(self, slot: int, tails: np.ndarray):
         tails = np.ascontiguousarray(tails, dtype=np.uint8)

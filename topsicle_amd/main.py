@@ -20,7 +20,7 @@ from collections import defaultdict
 
 import numpy as np
 
-from . import allsteps, batch, hiplib, rawnpz, seqio
+from . import allsteps, batch, hiplib, motif, rawnpz, seqio
 
 version_number = "1.0.0"
 Topsicle_output_prefix = "Topsicle"
@@ -324,6 +324,11 @@ def analysis_run(args, engines=None, engine_factory=None, wait_plots=True):
         tprint(f"{k}: {v}")
     print("---------------------")
     tprint("Starting Topsicle analysis")
+    if args.pattern.strip().lower() == "auto":
+        # the motif comes from the reads (motif.py); from here on the run is the one `--pattern <that motif>` would have been
+        if engines is None:
+            engines, engine_factory = _open_engines(args, engine_factory)
+        args.pattern = find_pattern(args, engines)
     if len(args.pattern) > hiplib.WIDE_MAX_K:
         # (before any file is read or written: k-mers of up to 32 letters and 64 patterns per table is what the scan kernels hold)
         tprint(f"--pattern has {len(args.pattern)} letters: motifs of up to {hiplib.WIDE_MAX_K} letters are supported")
@@ -358,14 +363,7 @@ def analysis_run(args, engines=None, engine_factory=None, wait_plots=True):
         csv.writer(fh).writerow(["file_number", "phrase", "trc", "readID", "telo_length"])
 
     if engines is None:
-        n_gpus = max(1, getattr(args, "gpus", 1) or 1)
-        first = getattr(args, "device", 0) or 0
-        if engine_factory is None:
-            def engine_factory():
-                # two contexts (launch queues) per GPU: the upload / launch ramp / download of one batch overlaps the scan of another
-                return [hiplib.HipScanner(first + i // CONTEXTS_PER_GPU) for i in range(n_gpus * CONTEXTS_PER_GPU)]
-        engines = engine_factory()
-        tprint(f"GPU engines: {[e.device_info() for e in engines]}")
+        engines, engine_factory = _open_engines(args, engine_factory)
 
     phrase_to_telo = defaultdict(list)
     phrase_to_trc = defaultdict(list)
@@ -414,6 +412,35 @@ def analysis_run(args, engines=None, engine_factory=None, wait_plots=True):
     tprint("All telomere found, have a nice day.")
     if wait_plots:
         wait_for_plots()
+
+
+def _open_engines(args, engine_factory):
+    """(contexts, the factory that made them): by default two contexts per GPU of --gpus, from --device on."""
+    n_gpus = max(1, getattr(args, "gpus", 1) or 1)
+    first = getattr(args, "device", 0) or 0
+    if engine_factory is None:
+        def engine_factory():
+            # two contexts (launch queues) per GPU: the upload / launch ramp / download of one batch overlaps the scan of another
+            return [hiplib.HipScanner(first + i // CONTEXTS_PER_GPU) for i in range(n_gpus * CONTEXTS_PER_GPU)]
+    engines = engine_factory()
+    tprint(f"GPU engines: {[e.device_info() for e in engines]}")
+    return engines, engine_factory
+
+
+def find_pattern(args, engines):
+    """`--pattern auto`: the motif census of the input's read ends (motif.find_motif, the reads --minSeqLength lets through), its
+    table in the log, and the rank-1 motif -- or the end of the run, with the candidates, when too few read ends agree on one."""
+    tprint("--pattern auto: looking for the repeat at the read ends")
+    rows, n_reads = motif.find_motif(args.inputDir, engines, min_len=args.minSeqLength, max_reads=getattr(args, "motifreads", motif.MOTIF_READS))
+    tprint(f"motif census of {n_reads} reads:")
+    for line in motif.format_table(rows):
+        tprint(line)
+    why = motif.verdict(rows)
+    if why:
+        tprint(f"--pattern auto found no motif: {why}. Candidates: {[r[0] for r in rows[:10]]}. Give the motif with --pattern.")
+        sys.exit(2)
+    tprint(f"--pattern auto: using {rows[0][0]} ({rows[0][2]} of {sum(r[2] for r in rows)} voting read ends)")
+    return rows[0][0]
 
 
 def _process_files(args, filenames, phrases, engines, engine_factory, num_cores):
@@ -499,7 +526,7 @@ def build_parser():
                                      formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     parser.add_argument("--inputDir", "-i", type=str, metavar="FILE/FOLDER", help="Required, Path to the input file or directory", required=True)
     parser.add_argument("--outputDir", "-o", type=str, metavar="FOLDER", help="Required, Path to the output directory", required=True)
-    parser.add_argument("--pattern", metavar="CHAR", type=str, help="Required, Telomere repeat sequence (in 5' to 3' orientation). For e.g., in human use CCCTAA", required=True)
+    parser.add_argument("--pattern", metavar="CHAR", type=str, help="Required, Telomere repeat sequence (in 5' to 3' orientation). For e.g., in human use CCCTAA (MI355X build: 'auto' finds it from the read ends first)", required=True)
     parser.add_argument("--minSeqLength", metavar="INT", type=int, help="Minimum length of a long read sequence that will be analyzed", default=9000)
     parser.add_argument("--rawcountpattern", action="store_true", help="Output raw count of the k-mer for each window")
     parser.add_argument("--rawcountformat", choices=["csv", "npz"], default="csv",
