@@ -143,6 +143,12 @@ int  tps_set_patterns(tps_ctx* ctx, const char* pats, int32_t n_patterns, int32_
  * one-shot calls scan with it too.  tps_batch_kmer_followers keeps n_fwd <= 15 and refuses a wide table: its counterpart for the
  * tables set here is tps_batch_kmer_followers_wide (n_fwd <= 32, any number of following letters).  A window that can hold more
  * than 255 occurrences of a k-mer ((window - 1) / k > 255), or a window / step-1 head of more than 32768 bases, is TPS_E_CAPACITY.
+ * In practice the LDS plan refuses (TPS_E_CAPACITY as well) long before 32768: a tile holds max(4096, window - 1, no_bp) positions,
+ * rounded up to 64, four waves share a workgroup, and the workgroup's budget is min(LDS per block, 160 KB).  Where that ends depends
+ * on how many distinct k-mers of the table can overlap themselves (have a period below k: a k-mer whose first and last letters agree
+ * is one): at the MI355X's 160 KB the largest step-1 head accepted is 25280 bases with none (e.g. the table A, T), 24896 with four
+ * (ACAC... at k = 16) and 24000 with fourteen (the 23-letter motif at k = 21); 64 bases more is refused.  At a 64 KB budget the
+ * same three tables stop at 7424, 7040 and 6080.  At 160 KB a window meets the counters' limit first (k <= 32: window - 1 <= 8191).
  * The next tps_set_patterns makes the narrow kernels current again; either call re-plans every resident batch. */
 int  tps_set_patterns_wide(tps_ctx* ctx, const char* pats, int32_t n_patterns, int32_t k);
 

@@ -29,6 +29,21 @@ extern "C" int emu_wide_table(const char* pats, int P, int k, uint32_t* out8) {
     return TPS_OK;
 }
 
+// the LDS plan alone, as do_scan decides it for a device whose workgroups may use budget_bytes of LDS: rc (TPS_E_CAPACITY: the plan
+// refuses, emu_wide_last_error says why), and out8 = {tp_cap, tw, seq_dw, wpg, workgroup LDS bytes, n_so, 0, 0}
+extern "C" int emu_wide_plan(const char* pats, int P, int k, const tps_params* prm, int64_t budget_bytes, int64_t* out8) {
+    std::vector<uint32_t> img;
+    tps::WideArgs a{};
+    std::string err = tps::build_wide_table(pats, P, k, img, a.pat);
+    if (!err.empty()) { g_err = err; return TPS_E_PATTERN; }
+    if (prm->window < 1 || prm->slide < 1 || prm->trimfirst < 0 || prm->maxlen < 0 || prm->no_bp < 0) { g_err = "bad window/slide/trimfirst/maxlen/no_bp"; return TPS_E_ARG; }
+    err = tps::plan_wide(a, *prm, budget_bytes / 4);
+    if (!err.empty()) { g_err = err; return TPS_E_CAPACITY; }
+    out8[0] = a.tp_cap; out8[1] = a.tw; out8[2] = a.seq_dw; out8[3] = a.wpg; out8[4] = tps::wide_wg_lds_dwords(a) * 4;
+    out8[5] = a.pat.n_so; out8[6] = out8[7] = 0;
+    return TPS_OK;
+}
+
 // One scan over a batch, like tps_set_patterns_wide + tps_batch_upload + tps_batch_scan + downloads.  base_shift moves the
 // batch inside its buffer by whole quads; words the layout does not own are garbage.
 extern "C" int emu_wide_scan(const char* pats, int P, int k, const uint8_t* bases, const int64_t* offsets, int64_t n,

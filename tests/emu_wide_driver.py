@@ -9,6 +9,7 @@ from topsicle_amd import hiplib
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "emu", "emu_wide.cpp")
+MAIN_SRC = os.path.join(HERE, "emu", "emu_wide_main.cpp")
 DEPS = [SRC] + [os.path.join(HERE, "..", "topsicle_amd", "csrc", f) for f in ("tps_wide.h", "tps_wide_plan.h", "tps_device.h", "tps_wave.h", "tps_plan.h", "tps_pack.h")] + \
        [os.path.join(HERE, "..", "include", "topsicle_hip.h")]
 
@@ -27,6 +28,18 @@ def build(asan=False):
     return out
 
 
+def build_main():
+    """tests/emu/emu_wide_main.cpp under -fsanitize=address,undefined: a program of its own, nothing loaded into Python."""
+    out = os.path.join(HERE, "emu", "_build", "emu_wide_main_asan")
+    if os.path.exists(out) and all(os.path.getmtime(out) >= os.path.getmtime(d) for d in DEPS + [MAIN_SRC]):
+        return out
+    tmp = out + ".tmp%d" % os.getpid()
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wno-unused-function", "-Wno-unused-variable", "-Wno-unknown-pragmas",
+                           "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", tmp, MAIN_SRC])
+    os.replace(tmp, out)
+    return out
+
+
 _lib = None
 
 
@@ -37,6 +50,7 @@ def lib():
         _lib.emu_wide_last_error.restype = C.c_char_p
         _lib.emu_wide_scan.restype = C.c_int
         _lib.emu_wide_table.restype = C.c_int
+        _lib.emu_wide_plan.restype = C.c_int
     return _lib
 
 
@@ -51,6 +65,21 @@ def table(patterns):
     if rc != 0:
         raise hiplib.TopsicleHipError(f"emu_wide_table rc={rc}: {lib().emu_wide_last_error().decode()}")
     return dict(zip(["n_groups", "n_so", "rot", "mul", "used", "mask_lo", "mask_hi"], [int(x) for x in out[:7]]))
+
+
+E_CAPACITY = -5                  # TPS_E_CAPACITY (include/topsicle_hip.h)
+LDS_BUDGET = 160 * 1024          # what emu_wide_scan plans with: the MI355X's LDS per workgroup
+
+
+def plan(patterns, prm, budget_bytes=LDS_BUDGET):
+    """What plan_wide (csrc/tps_wide_plan.h) decides for a device whose workgroups may use `budget_bytes` of LDS:
+    dict(tp_cap, tw, seq_dw, wpg, lds_bytes, n_so), or dict(error=TPS_E_*, message=...) where it refuses."""
+    out = np.zeros(8, np.int64)
+    L = lib()
+    rc = L.emu_wide_plan("".join(patterns).encode(), len(patterns), len(patterns[0]), C.byref(prm), C.c_int64(budget_bytes), _p(out))
+    if rc != 0:
+        return dict(error=rc, message=L.emu_wide_last_error().decode())
+    return dict(zip(["tp_cap", "tw", "seq_dw", "wpg", "lds_bytes", "n_so"], [int(x) for x in out[:6]]))
 
 
 def scan(patterns, seqs, prm, tails=None, base_shift=0):
