@@ -18,20 +18,11 @@ extern "C" int emu_scan_lc(const char* pats, int P, int k, const uint8_t* bases,
     a.val_on = 0;
     std::string err = tps::build_patterns(pats, P, k, lut, a.pat);
     if (!err.empty()) { g_err = err; return TPS_E_PATTERN; }
-    std::vector<int64_t> win_off((size_t)n + 1), win_off16((size_t)n + 1);
-    int64_t acc = 0, acc16 = 0, mx = 0;
-    for (int64_t i = 0; i < n; ++i) {
-        win_off[(size_t)i] = acc;
-        win_off16[(size_t)i] = acc16;
-        const int64_t nw = tps::window_count(offsets[i + 1] - offsets[i], prm->window, prm->slide, prm->trimfirst, prm->maxlen);
-        mx = nw > mx ? nw : mx;
-        acc += nw;
-        acc16 += tps::sums16_slots(nw);
-    }
-    win_off[(size_t)n] = acc;
-    win_off16[(size_t)n] = acc16;
+    tps::BatchLayout lay;
+    tps::plan_batch_layout(offsets, n, *prm, lay);
+    const std::vector<int64_t>& win_off = lay.win_off, &win_off16 = lay.win_off16;
     memcpy(win_off_out, win_off.data(), (size_t)(n + 1) * 8);
-    err = tps::plan_geometry(a, *prm, k, P, mx, 160 * 1024 / 4, knobs_with(0, 0));
+    err = tps::plan_geometry(a, *prm, k, P, lay.max_nwin, 160 * 1024 / 4, knobs_with(0, 0));
     if (!err.empty()) { g_err = err; return TPS_E_CAPACITY; }
     if (a.variant != 6 || a.pat.so_mask != 0 || a.pair16 || a.lut16 || a.lut_fields) { g_err = "emu_scan_lc: not a default sums kernel of slide 6"; return TPS_E_ARG; }
     // (lc_cap_force: a smaller capacity than the plan's max n_win / jump + 2 -- the kernel takes a read as long as
@@ -51,7 +42,7 @@ extern "C" int emu_scan_lc(const char* pats, int P, int k, const uint8_t* bases,
     a.results = results;
     a.win_off = win_off.data();
     a.sums = sums;
-    std::vector<uint16_t> sums16((size_t)acc16 + 8, (uint16_t)0xBEEF);
+    std::vector<uint16_t> sums16((size_t)win_off16[(size_t)n] + 8, (uint16_t)0xBEEF);
     a.sums16 = sums16.data();
     a.win_off16 = win_off16.data();
     a.n_reads = n;

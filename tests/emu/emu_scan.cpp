@@ -63,17 +63,13 @@ extern "C" int emu_scan(const char* pats, int P, int k, const uint8_t* bases, co
     a.val_on = g_val_off ? 0 : 1;  // (the emulation keeps the invalid-mask staging area; knob val_off: the layout of a clean batch, bases without invalid letters only)
     std::string err = tps::build_patterns(pats, P, k, lut, a.pat);
     if (!err.empty()) { g_err = err; return TPS_E_PATTERN; }
-    std::vector<int64_t> win_off((size_t)n + 1);
-    int64_t acc = 0, mx = 0;
-    for (int64_t i = 0; i < n; ++i) {
-        win_off[(size_t)i] = acc;
-        int64_t nw = tps::window_count(offsets[i + 1] - offsets[i], prm->window, prm->slide, prm->trimfirst, prm->maxlen);
-        mx = nw > mx ? nw : mx;
-        acc += nw;
-    }
-    win_off[(size_t)n] = acc;
+    // window layout and dispatch order as the library plans them
+    tps::BatchLayout lay;
+    tps::plan_batch_layout(offsets, n, *prm, lay);
+    const std::vector<int64_t>& win_off = lay.win_off, &win_off16 = lay.win_off16;
+    const std::vector<int32_t>& order = lay.order;       // (results do not depend on it)
     if (win_off_out) memcpy(win_off_out, win_off.data(), (size_t)(n + 1) * 8);
-    err = tps::plan_geometry(a, *prm, k, P, mx, lds_budget_bytes / 4, knobs_with(spans_pref, force_generic));
+    err = tps::plan_geometry(a, *prm, k, P, lay.max_nwin, lds_budget_bytes / 4, knobs_with(spans_pref, force_generic));
     if (!err.empty()) { g_err = err; return TPS_E_CAPACITY; }
 
     // the packed batch, exactly as the library keeps it in HBM (tps_pack.h).  Words the layout does not own are filled
@@ -97,12 +93,6 @@ extern "C" int emu_scan(const char* pats, int P, int k, const uint8_t* bases, co
     a.win_off = win_off.data();
     a.sums = sums;                                 // always present, like the library's device buffer
     // fused kernels: 16-bit sums in the padded device layout (tps_plan.h: sums16_slots), widened below like the library's download
-    std::vector<int64_t> win_off16((size_t)n + 1);
-    {
-        int64_t acc16 = 0;
-        for (int64_t i = 0; i < n; ++i) { win_off16[(size_t)i] = acc16; acc16 += tps::sums16_slots(win_off[(size_t)i + 1] - win_off[(size_t)i]); }
-        win_off16[(size_t)n] = acc16;
-    }
     std::vector<uint16_t> sums16((size_t)win_off16[(size_t)n] + 8, (uint16_t)0xBEEF);
     a.sums16 = sums16.data();
     a.win_off16 = win_off16.data();
@@ -143,17 +133,6 @@ extern "C" int emu_scan(const char* pats, int P, int k, const uint8_t* bases, co
     uint32_t* lds_al = (uint32_t*)(((uintptr_t)ldsbuf.data() + 15) & ~(uintptr_t)15);
     struct { uint32_t* p; size_t n; uint32_t* data() { return p; } uint32_t* begin() { return p; } uint32_t* end() { return p + n; } } lds{lds_al, (size_t)tps::lds_dwords(a)};
     g_variant_calls[a.variant] += (int)n;
-    // the reads in the library's dispatch order (tps::plan_dispatch_order; results do not depend on it)
-    std::vector<int32_t> order;
-    {
-        std::vector<int64_t> nwv((size_t)n);
-        std::vector<uint8_t> longer((size_t)n);
-        for (int64_t i = 0; i < n; ++i) {
-            nwv[(size_t)i] = (prm->flags & TPS_F_WINDOWS) ? win_off[(size_t)i + 1] - win_off[(size_t)i] : 0;
-            longer[(size_t)i] = !(prm->flags & TPS_F_STEP1) || offsets[i + 1] - offsets[i] > prm->min_len;
-        }
-        tps::plan_dispatch_order(nwv.data(), longer.data(), n, order);
-    }
     for (int64_t slot = 0; slot < n; ++slot) {
         const int64_t r = order.empty() ? slot : order[(size_t)slot];
         for (auto& w : lds) w = 0xDEADBEEFu;          // LDS content is undefined at workgroup start

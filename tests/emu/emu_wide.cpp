@@ -56,13 +56,10 @@ extern "C" int emu_wide_scan(const char* pats, int P, int k, const uint8_t* base
     if (prm->window < 1 || prm->slide < 1 || prm->trimfirst < 0 || prm->maxlen < 0 || prm->no_bp < 0) { g_err = "bad window/slide/trimfirst/maxlen/no_bp"; return TPS_E_ARG; }
     err = tps::plan_wide(a, *prm, 160 * 1024 / 4);
     if (!err.empty()) { g_err = err; return TPS_E_CAPACITY; }
-    std::vector<int64_t> win_off((size_t)n + 1);
-    int64_t acc = 0;
-    for (int64_t i = 0; i < n; ++i) {
-        win_off[(size_t)i] = acc;
-        acc += tps::window_count(offsets[i + 1] - offsets[i], prm->window, prm->slide, prm->trimfirst, prm->maxlen);
-    }
-    win_off[(size_t)n] = acc;
+    // window layout and dispatch order as the library plans them (the wide kernel has no 16-bit sums: win_off16 is not used)
+    tps::BatchLayout lay;
+    tps::plan_batch_layout(offsets, n, *prm, lay);
+    const std::vector<int64_t>& win_off = lay.win_off;
     if (win_off_out) memcpy(win_off_out, win_off.data(), (size_t)(n + 1) * 8);
 
     std::vector<tps_read_desc> desc((size_t)(n > 0 ? n : 1));
@@ -93,7 +90,8 @@ extern "C" int emu_wide_scan(const char* pats, int P, int k, const uint8_t* base
     const size_t dw = (size_t)tps::wide_lds_dwords(a);
     uint32_t* lds = nullptr;
     if (posix_memalign((void**)&lds, 16, dw * 4)) { g_err = "out of memory"; return TPS_E_ARG; }
-    for (int64_t r = 0; r < n; ++r) {
+    for (int64_t slot = 0; slot < n; ++slot) {
+        const int64_t r = lay.order.empty() ? slot : lay.order[(size_t)slot];       // (results do not depend on the order)
         for (size_t i = 0; i < dw; ++i) lds[i] = 0xDEADBEEFu;       // LDS content is undefined at workgroup start
         tps::wide_read(a, r, lds, img_al);
     }

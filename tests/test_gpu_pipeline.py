@@ -413,3 +413,63 @@ def test_cli_slide_10_with_raw_rows_and_two_pass_equals_the_generic_kernel(tmp_p
     for f in sorted(os.listdir(a)):
         if "_trc_over_" in f:
             assert open(a / f).read() == open(b / f).read(), f
+
+
+def test_kernel_time_counts_the_timed_launches():
+    """What tps_kernel_time_ms adds up (bench.py's kernel_ms_mean): one event pair per scan whatever kernel it launches -- a strided
+    scan's base-slide kernel is not a launch of its own --, none for an empty batch or with `no_events`, every event_stride-th launch
+    from the reset on, and a window that restarts when the pool of 16 384 pairs wraps."""
+    import time
+    motif, k = "CCCTAA", 4
+    pats = orc.kmer_table(motif, k)
+    bases, offsets, _ = synth.make_reads(24, 3000, motif, seed=7, tract_min=300, tract_max=1500)
+    prm = _params(motif, 6)
+    with hiplib.HipScanner(0) as s:
+        s.set_patterns(pats)
+        s.upload(0, bases, offsets)
+        s.upload(1, np.zeros(0, np.uint8), np.zeros(1, np.int64))
+        s.kernel_time_reset()
+        s.debug_option("event_stride", 1)
+        s.scan(0, prm)                                           # fused
+        assert s.kernel_info(0).startswith("tps_scan_kernel_s6")
+        s.debug_option("force_generic", 1)
+        s.scan(0, prm)                                           # generic
+        assert s.kernel_info(0).startswith("tps_scan_kernel ")
+        s.debug_option("force_generic", 0)
+        s.scan(0, _params(motif, 14))                            # strided: the slide-7 kernel and tps_stride_kernel are ONE timed launch
+        assert "every 2nd window" in s.kernel_info(0)
+        s.set_patterns_wide(orc.kmer_table("CTGTGGGGTCTGGGTG", 14))             # a 16-letter motif: 32 patterns
+        s.scan(0, prm)                                           # wide
+        assert s.kernel_info(0).startswith("tps_scan_kernel_wide ")
+        n, total, mean = s.kernel_time_ms()
+        assert n == 4 and total > 0 and mean == total / 4
+        s.set_patterns(pats)
+        s.scan(1, prm)                                           # an empty batch launches nothing
+        assert s.kernel_time_ms()[0] == 4
+        s.debug_option("no_events", 1)
+        for _ in range(3):
+            s.scan(0, prm)
+        assert s.kernel_time_ms()[0] == 4
+        s.debug_option("no_events", 0)
+        s.debug_option("event_stride", 3)
+        s.kernel_time_reset()
+        for _ in range(7):
+            s.scan(0, prm)
+        assert s.kernel_time_ms()[0] == 3                        # launches 0, 3 and 6
+        s.kernel_time_reset()
+        s.scan(0, _params(motif, 14))                            # launch 0; its base-slide scan is no launch of its own ...
+        s.scan(0, prm)
+        s.scan(0, prm)                                           # ... so this is launch 2, not 3
+        assert s.kernel_time_ms()[0] == 1
+    # the pool wraps at 16 384 pairs: the window restarts with the launch that finds it full
+    b8, o8, _ = synth.make_reads(8, 1200, motif, seed=8, tract_min=300, tract_max=900)
+    step1 = _params(motif, 6, flags=hiplib.F_STEP1)
+    with hiplib.HipScanner(0) as s:
+        s.set_patterns(pats)
+        s.upload(0, b8, o8)
+        s.kernel_time_reset()
+        t0 = time.perf_counter()
+        for _ in range(16384 + 5):
+            s.scan(0, step1)
+        assert s.kernel_time_ms()[0] == 5
+        print(f"pool wrap: {16384 + 5} scans in {time.perf_counter() - t0:.2f} s")

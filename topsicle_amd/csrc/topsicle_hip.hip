@@ -251,6 +251,10 @@ struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;
     bool borrowed = false;               // p belongs to another context's slot (tps_batch_share): never freed, never grown here
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;      // (owns p: whatever holds a DevBuf frees it by going away, tps_ctx_destroy names none of them)
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
     int ensure(size_t bytes) {
         if (borrowed) { p = nullptr; cap = 0; borrowed = false; }
         if (bytes <= cap) return TPS_OK;
@@ -270,10 +274,8 @@ struct Slot {
     bool inv_valid = true;               // false: the batch came packed without an inv array (no read is flagged)
     bool any_invalid = true;             // some read of the batch is flagged TPS_RD_HAS_INVALID (the kernels then stage the invalid masks)
     std::vector<int64_t> h_offsets;      // host copy of offsets (n+1)
-    std::vector<int64_t> h_win_off;      // window layout of the last plan
-    std::vector<int64_t> h_win_off16;    // ... of the fused kernels' 16-bit sums on the device (every read padded to a multiple of 8 windows)
+    tps::BatchLayout lay;                // window layout and dispatch order of the last plan (tps::plan_batch_layout)
     std::vector<uint16_t> h_sums16;      // download scratch
-    std::vector<int32_t> h_order;        // dispatch order of the last plan (tps::plan_dispatch_order; empty = file order)
     tps_read_result* h_results = nullptr;   // pinned
     size_t h_results_cap = 0;
     int64_t n = -1;
@@ -304,7 +306,35 @@ struct Slot {
     tps_params wplan_prm{};
     uint64_t wplan_table = 0;
     tps::WideArgs wargs{};
+    ~Slot() {
+        if (h_results) (void)hipHostFree(h_results);
+        delete sub;
+    }
 };
+
+// The scan kernels of tps_kernels.h by family (table kind and outputs) and slide; {} = no such instantiation.  TPS_K: the name
+// tps_batch_kernel_info reports is the symbol.
+struct ScanKernel { const void* fn; const char* name; };
+#define TPS_K(sym) {(const void*)sym, #sym}
+enum ScanFamily { KF_PLAIN, KF_PAIR, KF_PAIRQ, KF_RAW, KF_SO, KF_SOL, KF_SOR, KF_SORH, KF_COUNT };
+constexpr int KSLIDE_MIN = 3, KSLIDE_MAX = 12;
+const ScanKernel GENERIC_KERNEL = TPS_K(tps_scan_kernel);
+const ScanKernel FUSED_KERNELS[KF_COUNT][KSLIDE_MAX - KSLIDE_MIN + 1] = {
+    // plain and pair table (sums only, no self-overlap): the default kernels have every slide a window of 100 allows
+    {TPS_K(tps_scan_kernel_s3), TPS_K(tps_scan_kernel_s4), TPS_K(tps_scan_kernel_s5), TPS_K(tps_scan_kernel_s6), TPS_K(tps_scan_kernel_s7),
+     TPS_K(tps_scan_kernel_s8), TPS_K(tps_scan_kernel_s9), TPS_K(tps_scan_kernel_s10), TPS_K(tps_scan_kernel_s11), TPS_K(tps_scan_kernel_s12)},
+    {TPS_K(tps_scan_kernel_s3p), TPS_K(tps_scan_kernel_s4p), TPS_K(tps_scan_kernel_s5p), TPS_K(tps_scan_kernel_s6p), TPS_K(tps_scan_kernel_s7p),
+     TPS_K(tps_scan_kernel_s8p), TPS_K(tps_scan_kernel_s9p), TPS_K(tps_scan_kernel_s10p), TPS_K(tps_scan_kernel_s11p), TPS_K(tps_scan_kernel_s12p)},
+    // the others keep slides 5 .. 8: 16-bit pair table (k = 5), raw rows, self-overlap sums (periods 5 and 6; 2 .. 4), self-overlap raw
+    // rows (32-bit fields; 16-bit field indices)
+    {{}, {}, TPS_K(tps_scan_kernel_s5q), TPS_K(tps_scan_kernel_s6q), TPS_K(tps_scan_kernel_s7q), TPS_K(tps_scan_kernel_s8q)},
+    {{}, {}, TPS_K(tps_scan_kernel_s5r), TPS_K(tps_scan_kernel_s6r), TPS_K(tps_scan_kernel_s7r), TPS_K(tps_scan_kernel_s8r)},
+    {{}, {}, TPS_K(tps_scan_kernel_s5so), TPS_K(tps_scan_kernel_s6so), TPS_K(tps_scan_kernel_s7so), TPS_K(tps_scan_kernel_s8so)},
+    {{}, {}, TPS_K(tps_scan_kernel_s5sol), TPS_K(tps_scan_kernel_s6sol), TPS_K(tps_scan_kernel_s7sol), TPS_K(tps_scan_kernel_s8sol)},
+    {{}, {}, TPS_K(tps_scan_kernel_s5sor), TPS_K(tps_scan_kernel_s6sor), TPS_K(tps_scan_kernel_s7sor), TPS_K(tps_scan_kernel_s8sor)},
+    {{}, {}, TPS_K(tps_scan_kernel_s5sorh), TPS_K(tps_scan_kernel_s6sorh), TPS_K(tps_scan_kernel_s7sorh), TPS_K(tps_scan_kernel_s8sorh)},
+};
+#undef TPS_K
 
 struct EventPair { hipEvent_t a, b; };
 
@@ -347,7 +377,8 @@ struct tps_ctx {
     int file_order = 0;               // tps_ctx_debug_option "file_order": wave slot i takes read i whatever the reads' lengths (A/B of tps::plan_dispatch_order)
     int event_stride = 1;             // time every event_stride-th launch (tps_ctx_debug_option "event_stride"): timing costs ~3.5 us per launch
     uint64_t launch_seq = 0;
-    size_t lds_set_v[56] = {0};
+    size_t lds_set_generic = 0;      // hipFuncAttributeMaxDynamicSharedMemorySize as last raised, per scan kernel
+    size_t lds_set_fused[KF_COUNT][KSLIDE_MAX - KSLIDE_MIN + 1] = {};
     uint32_t* h_flag = nullptr;      // mapped host word the pack kernel raises when a read has a non-ACGT letter
     hipEvent_t share_ev = nullptr;   // tps_batch_share: orders this context's stream behind the lender's upload
     void* raw_stage[2] = {nullptr, nullptr};    // tps_batch_raw_to_fd: two pinned pieces, one being written while the other is filled
@@ -364,10 +395,14 @@ int bind(tps_ctx* c) {
 
 using tps::window_count;
 
+// LDS one workgroup may use, in dwords: what the device reports, at most gfx950's 160 KB; 64 KB where it reports nothing
+int64_t lds_budget_dw(const tps_ctx* c) {
+    return (int64_t)(c->prop.sharedMemPerBlock > 0 ? std::min<size_t>(c->prop.sharedMemPerBlock, 160 * 1024) : 64 * 1024) / 4;
+}
+
 int plan_lds(tps_ctx* c, Slot& sl, const tps_params& prm, int64_t max_nwin) {
-    const size_t lds_max = c->prop.sharedMemPerBlock > 0 ? std::min<size_t>(c->prop.sharedMemPerBlock, 160 * 1024) : 64 * 1024;
     sl.args.pat = c->pat;                          // the plan looks at dup_mask
-    std::string err = tps::plan_geometry(sl.args, prm, c->pat.k, c->pat.P, max_nwin, (int64_t)lds_max / 4, c->knobs);
+    std::string err = tps::plan_geometry(sl.args, prm, c->pat.k, c->pat.P, max_nwin, lds_budget_dw(c), c->knobs);
     if (!err.empty()) return fail(TPS_E_CAPACITY, "%s", err.c_str());
     sl.lds_bytes = (size_t)tps::wg_lds_dwords(sl.args) * 4;
     return TPS_OK;
@@ -380,6 +415,16 @@ int check_params(const tps_params& p) {
         return fail(TPS_E_ARG, "bad jump/min_size");
     if (p.slide > 4096 || p.window > 65536 || p.jump > 4096) return fail(TPS_E_CAPACITY, "window/slide/jump too large");
     if ((p.flags & TPS_F_WINDOWS) && p.jump < 1) return fail(TPS_E_ARG, "jump must be >= 1");
+    return TPS_OK;
+}
+
+// what every scan checks before it plans, whatever the table
+int check_scan(const Slot& sl, const tps_params& prm) {
+    int rc;
+    if (sl.n < 0) return fail(TPS_E_STATE, "no batch uploaded in this slot");
+    if ((rc = check_params(prm))) return rc;
+    if (!(prm.flags & TPS_F_STEP1) && (prm.flags & TPS_F_TAILS_IN) && !sl.has_tails)
+        return fail(TPS_E_STATE, "TPS_F_TAILS_IN without tps_batch_set_tails");
     return TPS_OK;
 }
 
@@ -407,6 +452,49 @@ int ensure_packed(Slot& sl, int64_t n, int64_t n_words) {
     if ((rc = sl.seq2.ensure((size_t)std::max<int64_t>(n_words, 4) * 4))) return rc;
     if ((rc = sl.inv.ensure((size_t)std::max<int64_t>(n_words, 4) * 2))) return rc;
     if ((rc = sl.desc.ensure((size_t)std::max<int64_t>(n, 1) * sizeof(tps_read_desc)))) return rc;
+    return TPS_OK;
+}
+
+// read i of a batch that comes packed: its descriptor lies inside the n_words words of the batch
+int check_desc(const tps_read_desc& d, int64_t i, int64_t n_words) {
+    if (d.len < 0 || d.word_off < 0 || (d.word_off & 3) || d.word_off + tps::packed_words(d.len) > n_words)
+        return fail(TPS_E_ARG, "read %lld: descriptor outside the packed batch (word_off %lld, len %d, %lld words)", (long long)i,
+                    (long long)d.word_off, d.len, (long long)n_words);
+    return TPS_OK;
+}
+
+// the mapped pinned buffer the kernels write a batch's results into
+int ensure_h_results(Slot& sl, int64_t n) {
+    if (sl.h_results_cap >= (size_t)n) return TPS_OK;
+    if (sl.h_results) (void)hipHostFree(sl.h_results);
+    sl.h_results = nullptr;
+    sl.h_results_cap = 0;
+    size_t want = (size_t)n + (size_t)n / 8 + 16;
+    HIP_TRY(hipHostMalloc((void**)&sl.h_results, want * sizeof(tps_read_result), hipHostMallocMapped));
+    sl.h_results_cap = want;
+    return TPS_OK;
+}
+
+// The events of the next scan launch: a pair from the pool if it is timed, {nullptr, nullptr} if not (an inner base-slide scan --
+// the strided scan around it is the launch that counts, so it does not advance launch_seq either --, option no_events, or all
+// but every event_stride-th launch).  tps_kernel_time_ms adds up the pairs handed out since the last reset.
+int next_events(tps_ctx* c, bool inner, EventPair& ev) {
+    if (c->ev_used == c->ev_pool.size()) {
+        if (c->ev_pool.size() >= 16384) {
+            c->ev_used = c->ev_base = 0;                  // wrap: the measurement window restarts
+        } else {
+            // events are created in batches, never one per launch (hipEventCreate costs ~60 us)
+            const size_t grow = c->ev_pool.empty() ? 512 : c->ev_pool.size();
+            for (size_t i = 0; i < grow; ++i) {
+                EventPair ep;
+                HIP_TRY(hipEventCreate(&ep.a));
+                HIP_TRY(hipEventCreate(&ep.b));
+                c->ev_pool.push_back(ep);
+            }
+        }
+    }
+    const bool timed = !inner && !c->no_events && (c->launch_seq++ % (uint64_t)c->event_stride) == 0;
+    ev = timed ? c->ev_pool[c->ev_used++] : EventPair{nullptr, nullptr};
     return TPS_OK;
 }
 
@@ -447,14 +535,13 @@ int do_upload(tps_ctx* c, Slot& sl, const uint8_t* bases, const int64_t* offsets
 // Host-packed batch: three plain copies.  Pinned sources (tps_host_alloc) are copied asynchronously.
 int do_upload_packed(tps_ctx* c, Slot& sl, const uint32_t* seq2, const uint16_t* inv, const tps_read_desc* desc, int64_t n, int64_t n_words) {
     if (n < 0 || n_words < 0 || (n > 0 && !desc) || (n_words > 0 && !seq2)) return fail(TPS_E_ARG, "bad packed batch pointers");
+    int rc;
     sl.h_offsets.resize((size_t)n + 1);
     int64_t acc = 0, need = 0;
     bool flagged = false;
     for (int64_t i = 0; i < n; ++i) {
         const tps_read_desc& d = desc[i];
-        if (d.len < 0 || d.word_off < 0 || (d.word_off & 3) || d.word_off + tps::packed_words(d.len) > n_words)
-            return fail(TPS_E_ARG, "read %lld: descriptor outside the packed batch (word_off %lld, len %d, %lld words)", (long long)i,
-                        (long long)d.word_off, d.len, (long long)n_words);
+        if ((rc = check_desc(d, i, n_words))) return rc;
         sl.h_offsets[(size_t)i] = acc;
         acc += d.len;
         need = std::max(need, d.word_off + tps::packed_words(d.len));
@@ -462,7 +549,6 @@ int do_upload_packed(tps_ctx* c, Slot& sl, const uint32_t* seq2, const uint16_t*
     }
     sl.h_offsets[(size_t)n] = acc;
     if (flagged && !inv) return fail(TPS_E_ARG, "a read is flagged TPS_RD_HAS_INVALID but inv is NULL");
-    int rc;
     if ((rc = ensure_packed(sl, n, n_words))) return rc;
     if (n_words) HIP_TRY(hipMemcpyAsync(sl.seq2.p, seq2, (size_t)n_words * 4, hipMemcpyHostToDevice, c->stream));
     if (n_words && inv) HIP_TRY(hipMemcpyAsync(sl.inv.p, inv, (size_t)n_words * 2, hipMemcpyHostToDevice, c->stream));
@@ -480,14 +566,13 @@ int do_upload_packed(tps_ctx* c, Slot& sl, const uint32_t* seq2, const uint16_t*
 int do_upload_nib4(tps_ctx* c, Slot& sl, const uint8_t* nib, int64_t nib_bytes, const tps_nib_src* src, const tps_read_desc* desc, int64_t n,
                    int64_t n_words) {
     if (n < 0 || n_words < 0 || nib_bytes < 0 || (n > 0 && (!desc || !src)) || (nib_bytes > 0 && !nib)) return fail(TPS_E_ARG, "bad nib4 batch pointers");
+    int rc;
     sl.h_offsets.resize((size_t)n + 1);
     int64_t acc = 0;
     bool flagged = false;
     for (int64_t i = 0; i < n; ++i) {
         const tps_read_desc& d = desc[i];
-        if (d.len < 0 || d.word_off < 0 || (d.word_off & 3) || d.word_off + tps::packed_words(d.len) > n_words)
-            return fail(TPS_E_ARG, "read %lld: descriptor outside the packed batch (word_off %lld, len %d, %lld words)", (long long)i,
-                        (long long)d.word_off, d.len, (long long)n_words);
+        if ((rc = check_desc(d, i, n_words))) return rc;
         const int64_t units = (((int64_t)d.len + 1) / 2 + 15) & ~(int64_t)15;            // the 16-byte units the kernel may load from
         if (src[i].off < 0 || (src[i].off & 15) || src[i].off + units > nib_bytes)
             return fail(TPS_E_ARG, "read %lld: codes outside the nibble buffer (off %lld, len %d, %lld bytes)", (long long)i,
@@ -497,7 +582,6 @@ int do_upload_nib4(tps_ctx* c, Slot& sl, const uint8_t* nib, int64_t nib_bytes, 
         flagged = flagged || (d.flags & TPS_RD_HAS_INVALID);
     }
     sl.h_offsets[(size_t)n] = acc;
-    int rc;
     if ((rc = ensure_packed(sl, n, n_words))) return rc;
     if ((rc = c->nib.ensure((size_t)std::max<int64_t>(nib_bytes, 16)))) return rc;
     if ((rc = c->nib_src.ensure((size_t)std::max<int64_t>(n, 1) * sizeof(tps_nib_src)))) return rc;
@@ -516,6 +600,17 @@ int do_upload_nib4(tps_ctx* c, Slot& sl, const uint8_t* nib, int64_t nib_bytes, 
     sl.any_invalid = flagged;
     reset_slot(sl, n, n_words);
     return TPS_OK;
+}
+
+// The kernel family of a fused plan (a.variant = its slide), by table and outputs.
+ScanFamily scan_family(const tps::ScanArgs& a, bool want_raw) {
+    const bool so = a.pat.so_mask != 0;
+    const bool pair = a.pair_n != 0;
+    // the default kernels' other slides (sums only, no self-overlap: plan_geometry took the fused path for nothing else)
+    if (tps::has_default_only_slide(a.variant)) return (pair && !a.pair16) ? KF_PAIR : KF_PLAIN;
+    // sums only, self-overlap table: periods 2 .. 4 have their own kernels (96 registers, 5 waves per SIMD)
+    if (so) return want_raw ? (a.lut16 ? KF_SORH : KF_SOR) : (a.pp_d >= 2 && a.pp_d <= 4) ? KF_SOL : KF_SO;
+    return want_raw ? KF_RAW : (pair && a.pair16) ? KF_PAIRQ : pair ? KF_PAIR : KF_PLAIN;
 }
 
 bool same_params(const tps_params& x, const tps_params& y) { return memcmp(&x, &y, sizeof x) == 0; }
@@ -565,9 +660,7 @@ int do_scan_strided(tps_ctx* c, Slot& sl, const tps_params& prm, int base, hipEv
     a.jump = prm.jump;
     a.min_size = prm.min_size;
     a.binseg = (prm.flags & TPS_F_BINSEG) ? 1 : 0;
-    int64_t mx = 0;
-    for (int64_t i = 0; i < n; ++i) mx = std::max(mx, sl.h_win_off[(size_t)i + 1] - sl.h_win_off[(size_t)i]);
-    a.s16_dw = (int32_t)((((mx + 1) / 2) + 3) & ~3ll);
+    a.s16_dw = (int32_t)((((sl.lay.max_nwin + 1) / 2) + 3) & ~3ll);
     if (a.s16_dw > 3072) a.s16_dw = 0;                 // (12 KB per wave: five workgroups per CU; longer series are read back from HBM)
     const size_t lds = (size_t)tps::WPG * (size_t)(tps::BINSEG_SMEM_DW + a.s16_dw) * 4;
     void* kargs[] = {(void*)&a};
@@ -587,40 +680,22 @@ int do_scan_strided(tps_ctx* c, Slot& sl, const tps_params& prm, int base, hipEv
 // (results in mapped host memory, c_start / c_end, int32 sums at win_off, u8 rows at win_off * P), so everything downstream is shared.
 int do_scan_wide(tps_ctx* c, Slot& sl, const tps_params& prm) {
     int rc;
-    if (sl.n < 0) return fail(TPS_E_STATE, "no batch uploaded in this slot");
-    if ((rc = check_params(prm))) return rc;
-    if (!(prm.flags & TPS_F_STEP1) && (prm.flags & TPS_F_TAILS_IN) && !sl.has_tails)
-        return fail(TPS_E_STATE, "TPS_F_TAILS_IN without tps_batch_set_tails");
     const tps_ctx::WideTable& wt = *c->wide_cur;
     const int64_t n = sl.n;
     const int P = wt.P;
     if (!sl.wplanned || !same_params(prm, sl.wplan_prm) || sl.wplan_table != wt.serial) {
         tps::WideArgs w{};
         w.pat = wt.pat;
-        const size_t lds_max = c->prop.sharedMemPerBlock > 0 ? std::min<size_t>(c->prop.sharedMemPerBlock, 160 * 1024) : 64 * 1024;
-        const std::string err = tps::plan_wide(w, prm, (int64_t)lds_max / 4);
+        const std::string err = tps::plan_wide(w, prm, lds_budget_dw(c));
         if (!err.empty()) return fail(TPS_E_CAPACITY, "%s", err.c_str());
-        sl.h_win_off.resize((size_t)n + 1);
-        std::vector<int64_t> nwv((size_t)n);
-        std::vector<uint8_t> longer((size_t)n);
-        int64_t acc = 0;
-        for (int64_t i = 0; i < n; ++i) {
-            sl.h_win_off[(size_t)i] = acc;
-            const int64_t len = sl.h_offsets[i + 1] - sl.h_offsets[i];
-            const int64_t nw = window_count(len, prm.window, prm.slide, prm.trimfirst, prm.maxlen);
-            acc += nw;
-            nwv[(size_t)i] = (prm.flags & TPS_F_WINDOWS) ? nw : 0;
-            longer[(size_t)i] = !(prm.flags & TPS_F_STEP1) || len > prm.min_len;
-        }
-        sl.h_win_off[(size_t)n] = acc;
-        sl.h_order.clear();
-        if (!c->file_order) tps::plan_dispatch_order(nwv.data(), longer.data(), n, sl.h_order);
-        if (!sl.h_order.empty()) {
+        tps::plan_batch_layout(sl.h_offsets.data(), n, prm, sl.lay);        // (its win_off16 is not used: this kernel writes int32 sums)
+        if (c->file_order) sl.lay.order.clear();
+        if (!sl.lay.order.empty()) {
             if ((rc = sl.order.ensure((size_t)n * 4))) return rc;
-            HIP_TRY(hipMemcpyAsync(sl.order.p, sl.h_order.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(hipMemcpyAsync(sl.order.p, sl.lay.order.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
         }
         if ((rc = sl.win_off.ensure((size_t)(n + 1) * 8))) return rc;
-        HIP_TRY(hipMemcpyAsync(sl.win_off.p, sl.h_win_off.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(sl.win_off.p, sl.lay.win_off.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
         sl.wargs = w;
         sl.wplan_prm = prm;
@@ -639,14 +714,8 @@ int do_scan_wide(tps_ctx* c, Slot& sl, const tps_params& prm) {
     static const char wide_name[] = "tps_scan_kernel_wide";
     sl.kernel_name = wide_name;
     sl.last_flags = prm.flags;
-    const int64_t total_win = sl.h_win_off[(size_t)n];
-    if (sl.h_results_cap < (size_t)n) {
-        if (sl.h_results) (void)hipHostFree(sl.h_results);
-        sl.h_results = nullptr;
-        size_t want = (size_t)n + (size_t)n / 8 + 16;
-        HIP_TRY(hipHostMalloc((void**)&sl.h_results, want * sizeof(tps_read_result), hipHostMallocMapped));
-        sl.h_results_cap = want;
-    }
+    const int64_t total_win = sl.lay.win_off[(size_t)n];
+    if ((rc = ensure_h_results(sl, n))) return rc;
     tps::WideArgs& a = sl.wargs;
     a.seq2 = (const uint32_t*)sl.seq2.p;
     a.inv = (const uint16_t*)sl.inv.p;
@@ -662,7 +731,7 @@ int do_scan_wide(tps_ctx* c, Slot& sl, const tps_params& prm) {
         a.c_end = (int32_t*)sl.c_end.p;
     }
     a.win_off = (const int64_t*)sl.win_off.p;
-    a.order = sl.h_order.empty() ? nullptr : (const int32_t*)sl.order.p;
+    a.order = sl.lay.order.empty() ? nullptr : (const int32_t*)sl.order.p;
     a.sums = nullptr;
     a.raw = nullptr;
     if (prm.flags & TPS_F_WINDOWS) {
@@ -680,25 +749,12 @@ int do_scan_wide(tps_ctx* c, Slot& sl, const tps_params& prm) {
         HIP_TRY(hipFuncSetAttribute((const void*)tps_scan_kernel_wide, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sl.lds_bytes));
         c->lds_set_wide = sl.lds_bytes;
     }
-    if (c->ev_used == c->ev_pool.size()) {
-        if (c->ev_pool.size() >= 16384) {
-            c->ev_used = c->ev_base = 0;
-        } else {
-            const size_t grow = c->ev_pool.empty() ? 512 : c->ev_pool.size();
-            for (size_t i = 0; i < grow; ++i) {
-                EventPair ep;
-                HIP_TRY(hipEventCreate(&ep.a));
-                HIP_TRY(hipEventCreate(&ep.b));
-                c->ev_pool.push_back(ep);
-            }
-        }
-    }
-    const bool timed = !c->no_events && (c->launch_seq++ % (uint64_t)c->event_stride) == 0;
-    EventPair& ep = c->ev_pool[timed ? c->ev_used++ : 0];
+    EventPair ev;
+    if ((rc = next_events(c, false, ev))) return rc;
     const int64_t grid = (n + a.wpg - 1) / a.wpg;
     void* kargs[] = {(void*)&a};
     HIP_TRY(hipExtLaunchKernel((const void*)tps_scan_kernel_wide, dim3((unsigned)grid), dim3(tps::NT * a.wpg), kargs, sl.lds_bytes, c->stream,
-                               timed ? ep.a : nullptr, timed ? ep.b : nullptr, 0));
+                               ev.a, ev.b, 0));
     sl.scanned = true;
     return TPS_OK;
 }
@@ -706,57 +762,33 @@ int do_scan_wide(tps_ctx* c, Slot& sl, const tps_params& prm) {
 int do_scan(tps_ctx* c, Slot& sl, const tps_params& prm, bool inner, hipEvent_t ev_start) {
     int rc;
     if (!c->have_pat) return fail(TPS_E_PATTERN, "tps_set_patterns has not been called");
+    if ((rc = check_scan(sl, prm))) return rc;
     if (c->wide_cur) return do_scan_wide(c, sl, prm);
-    if (sl.n < 0) return fail(TPS_E_STATE, "no batch uploaded in this slot");
-    if ((rc = check_params(prm))) return rc;
-    if (!(prm.flags & TPS_F_STEP1) && (prm.flags & TPS_F_TAILS_IN) && !sl.has_tails)
-        return fail(TPS_E_STATE, "TPS_F_TAILS_IN without tps_batch_set_tails");
     const int64_t n = sl.n;
     const int P = c->pat.P;
     if (!sl.planned || !same_params(prm, sl.plan_prm) || sl.plan_k != c->pat.k || sl.plan_p != P ||
         (sl.plan_dup != 0) != (c->pat.dup_mask != 0) || (sl.plan_so != 0) != (c->pat.so_mask != 0)) {
-        sl.h_win_off.resize((size_t)n + 1);
-        sl.h_win_off16.resize((size_t)n + 1);
-        int64_t acc = 0, acc16 = 0, mx = 0;
-        std::vector<int64_t> nwv((size_t)n);
-        std::vector<uint8_t> longer((size_t)n);
-        for (int64_t i = 0; i < n; ++i) {
-            sl.h_win_off[(size_t)i] = acc;
-            sl.h_win_off16[(size_t)i] = acc16;
-            const int64_t len = sl.h_offsets[i + 1] - sl.h_offsets[i];
-            int64_t nw = window_count(len, prm.window, prm.slide, prm.trimfirst, prm.maxlen);
-            mx = std::max(mx, nw);
-            acc += nw;
-            acc16 += tps::sums16_slots(nw);
-            nwv[(size_t)i] = (prm.flags & TPS_F_WINDOWS) ? nw : 0;
-            longer[(size_t)i] = !(prm.flags & TPS_F_STEP1) || len > prm.min_len;      // (scan_read: pass = L > min_len && ...)
-        }
-        sl.h_win_off[(size_t)n] = acc;
-        sl.h_win_off16[(size_t)n] = acc16;
-        sl.h_order.clear();
-        if (!c->file_order) tps::plan_dispatch_order(nwv.data(), longer.data(), n, sl.h_order);
-        if (!sl.h_order.empty()) {
+        tps::plan_batch_layout(sl.h_offsets.data(), n, prm, sl.lay);
+        if (c->file_order) sl.lay.order.clear();
+        if (!sl.lay.order.empty()) {
             if ((rc = sl.order.ensure((size_t)n * 4))) return rc;
-            HIP_TRY(hipMemcpyAsync(sl.order.p, sl.h_order.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(hipMemcpyAsync(sl.order.p, sl.lay.order.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
         }
         sl.args = tps::ScanArgs{};
         sl.args.val_on = sl.any_invalid ? 1 : 0;
-        if ((rc = plan_lds(c, sl, prm, mx))) return rc;
+        if ((rc = plan_lds(c, sl, prm, sl.lay.max_nwin))) return rc;
         sl.stride_base = 0;
         if (!inner && !c->no_stride) {
-            const size_t lds_max = c->prop.sharedMemPerBlock > 0 ? std::min<size_t>(c->prop.sharedMemPerBlock, 160 * 1024) : 64 * 1024;
-            int64_t max_len = 0;
-            for (int64_t i = 0; i < n; ++i) max_len = std::max(max_len, sl.h_offsets[i + 1] - sl.h_offsets[i]);
-            sl.stride_base = tps::stride_base(sl.args, prm, c->pat.k, P, [&](int s0) { return window_count(max_len, prm.window, s0, prm.trimfirst, prm.maxlen); },
-                                              (int64_t)lds_max / 4, c->knobs);
+            sl.stride_base = tps::stride_base(sl.args, prm, c->pat.k, P, [&](int s0) { return window_count(sl.lay.max_len, prm.window, s0, prm.trimfirst, prm.maxlen); },
+                                              lds_budget_dw(c), c->knobs);
         }
         if ((rc = sl.win_off.ensure((size_t)(n + 1) * 8))) return rc;
-        HIP_TRY(hipMemcpyAsync(sl.win_off.p, sl.h_win_off.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(sl.win_off.p, sl.lay.win_off.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, c->stream));
         if (sl.args.variant) {                          // fused kernels: the padded layout of their 16-bit sums
             if ((rc = sl.win_off16.ensure((size_t)(n + 1) * 8))) return rc;
-            HIP_TRY(hipMemcpyAsync(sl.win_off16.p, sl.h_win_off16.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(hipMemcpyAsync(sl.win_off16.p, sl.lay.win_off16.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, c->stream));
         }
-        HIP_TRY(hipStreamSynchronize(c->stream));       // h_win_off may be reused by the caller's next plan
+        HIP_TRY(hipStreamSynchronize(c->stream));       // sl.lay may be reused by the caller's next plan
         sl.plan_prm = prm;
         sl.plan_k = c->pat.k;
         sl.plan_p = P;
@@ -764,14 +796,8 @@ int do_scan(tps_ctx* c, Slot& sl, const tps_params& prm, bool inner, hipEvent_t 
         sl.plan_so = c->pat.so_mask;
         sl.planned = true;
     }
-    const int64_t total_win = sl.h_win_off[(size_t)n];
-    if (sl.h_results_cap < (size_t)n) {
-        if (sl.h_results) (void)hipHostFree(sl.h_results);
-        sl.h_results = nullptr;
-        size_t want = (size_t)n + (size_t)n / 8 + 16;
-        HIP_TRY(hipHostMalloc((void**)&sl.h_results, want * sizeof(tps_read_result), hipHostMallocMapped));
-        sl.h_results_cap = want;
-    }
+    const int64_t total_win = sl.lay.win_off[(size_t)n];
+    if ((rc = ensure_h_results(sl, n))) return rc;
     tps::ScanArgs& a = sl.args;
     a.seq2 = (const uint32_t*)sl.seq2.p;
     a.inv = (const uint16_t*)sl.inv.p;
@@ -793,7 +819,7 @@ int do_scan(tps_ctx* c, Slot& sl, const tps_params& prm, bool inner, hipEvent_t 
         a.c_end = (int32_t*)sl.c_end.p;
     }
     a.win_off = (const int64_t*)sl.win_off.p;
-    a.order = sl.h_order.empty() ? nullptr : (const int32_t*)sl.order.p;
+    a.order = sl.lay.order.empty() ? nullptr : (const int32_t*)sl.order.p;
     a.sums = nullptr;
     a.sums16 = nullptr;
     a.win_off16 = nullptr;
@@ -803,7 +829,7 @@ int do_scan(tps_ctx* c, Slot& sl, const tps_params& prm, bool inner, hipEvent_t 
         // TPS_F_STORE_SUMS just makes it downloadable.  The fused kernels write 16-bit values (2 B per window, every read
         // padded to 8 windows), the generic kernel int32; tps_batch_window_sums hands out int32 either way.
         if (a.variant) {
-            if ((rc = sl.sums.ensure((size_t)std::max<int64_t>(sl.h_win_off16[(size_t)n], 8) * 2))) return rc;
+            if ((rc = sl.sums.ensure((size_t)std::max<int64_t>(sl.lay.win_off16[(size_t)n], 8) * 2))) return rc;
             a.sums16 = (uint16_t*)sl.sums.p;
             a.win_off16 = (const int64_t*)sl.win_off16.p;
         } else {
@@ -845,80 +871,24 @@ int do_scan(tps_ctx* c, Slot& sl, const tps_params& prm, bool inner, hipEvent_t 
     sl.last_flags = prm.flags;
     if (n == 0) { sl.scanned = true; return TPS_OK; }
 
-    const void* kfn;
-    int kidx;
-    const bool so = a.pat.so_mask != 0;
-    const bool pair = a.pair_n != 0;
-    const bool want_raw = a.raw != nullptr;
-    {
-        // kernel family by table and outputs: [slide 5..8] x {plain, pair table, raw rows, self-overlap sums, self-overlap raw}
-        struct K { const void* fn; const char* name; };
-        static const K plain[4] = {{(const void*)tps_scan_kernel_s5, "tps_scan_kernel_s5"}, {(const void*)tps_scan_kernel_s6, "tps_scan_kernel_s6"},
-                                   {(const void*)tps_scan_kernel_s7, "tps_scan_kernel_s7"}, {(const void*)tps_scan_kernel_s8, "tps_scan_kernel_s8"}};
-        static const K pairk[4] = {{(const void*)tps_scan_kernel_s5p, "tps_scan_kernel_s5p"}, {(const void*)tps_scan_kernel_s6p, "tps_scan_kernel_s6p"},
-                                   {(const void*)tps_scan_kernel_s7p, "tps_scan_kernel_s7p"}, {(const void*)tps_scan_kernel_s8p, "tps_scan_kernel_s8p"}};
-        static const K rawk[4] = {{(const void*)tps_scan_kernel_s5r, "tps_scan_kernel_s5r"}, {(const void*)tps_scan_kernel_s6r, "tps_scan_kernel_s6r"},
-                                  {(const void*)tps_scan_kernel_s7r, "tps_scan_kernel_s7r"}, {(const void*)tps_scan_kernel_s8r, "tps_scan_kernel_s8r"}};
-        static const K sok[4] = {{(const void*)tps_scan_kernel_s5so, "tps_scan_kernel_s5so"}, {(const void*)tps_scan_kernel_s6so, "tps_scan_kernel_s6so"},
-                                 {(const void*)tps_scan_kernel_s7so, "tps_scan_kernel_s7so"}, {(const void*)tps_scan_kernel_s8so, "tps_scan_kernel_s8so"}};
-        static const K sork[4] = {{(const void*)tps_scan_kernel_s5sor, "tps_scan_kernel_s5sor"}, {(const void*)tps_scan_kernel_s6sor, "tps_scan_kernel_s6sor"},
-                                  {(const void*)tps_scan_kernel_s7sor, "tps_scan_kernel_s7sor"}, {(const void*)tps_scan_kernel_s8sor, "tps_scan_kernel_s8sor"}};
-        static const K sorhk[4] = {{(const void*)tps_scan_kernel_s5sorh, "tps_scan_kernel_s5sorh"}, {(const void*)tps_scan_kernel_s6sorh, "tps_scan_kernel_s6sorh"},
-                                   {(const void*)tps_scan_kernel_s7sorh, "tps_scan_kernel_s7sorh"}, {(const void*)tps_scan_kernel_s8sorh, "tps_scan_kernel_s8sorh"}};
-        static const K pairqk[4] = {{(const void*)tps_scan_kernel_s5q, "tps_scan_kernel_s5q"}, {(const void*)tps_scan_kernel_s6q, "tps_scan_kernel_s6q"},
-                                    {(const void*)tps_scan_kernel_s7q, "tps_scan_kernel_s7q"}, {(const void*)tps_scan_kernel_s8q, "tps_scan_kernel_s8q"}};
-        static const K solk[4] = {{(const void*)tps_scan_kernel_s5sol, "tps_scan_kernel_s5sol"}, {(const void*)tps_scan_kernel_s6sol, "tps_scan_kernel_s6sol"},
-                                  {(const void*)tps_scan_kernel_s7sol, "tps_scan_kernel_s7sol"}, {(const void*)tps_scan_kernel_s8sol, "tps_scan_kernel_s8sol"}};
-        static const K plainx[6] = {{(const void*)tps_scan_kernel_s3, "tps_scan_kernel_s3"}, {(const void*)tps_scan_kernel_s4, "tps_scan_kernel_s4"}, {(const void*)tps_scan_kernel_s9, "tps_scan_kernel_s9"},
-                                    {(const void*)tps_scan_kernel_s10, "tps_scan_kernel_s10"}, {(const void*)tps_scan_kernel_s11, "tps_scan_kernel_s11"},
-                                    {(const void*)tps_scan_kernel_s12, "tps_scan_kernel_s12"}};
-        static const K pairx[6] = {{(const void*)tps_scan_kernel_s3p, "tps_scan_kernel_s3p"}, {(const void*)tps_scan_kernel_s4p, "tps_scan_kernel_s4p"}, {(const void*)tps_scan_kernel_s9p, "tps_scan_kernel_s9p"},
-                                   {(const void*)tps_scan_kernel_s10p, "tps_scan_kernel_s10p"}, {(const void*)tps_scan_kernel_s11p, "tps_scan_kernel_s11p"},
-                                   {(const void*)tps_scan_kernel_s12p, "tps_scan_kernel_s12p"}};
-        if (tps::has_default_only_slide(a.variant)) {
-            // the default kernels' other slides (sums only, no self-overlap: plan_geometry took the fused path for nothing else)
-            const int xi = a.variant <= 4 ? a.variant - 3 : a.variant - 7;
-            const K& k = (pair && !a.pair16) ? pairx[xi] : plainx[xi];
-            kfn = k.fn;
-            sl.kernel_name = k.name;
-            kidx = 40 + ((pair && !a.pair16) ? 6 : 0) + xi;
-        } else if (a.variant >= 5 && a.variant <= 8) {
-            // sums only, self-overlap table: periods 2 .. 4 have their own kernels (96 registers, 5 waves per SIMD)
-            const int fam = so ? (want_raw ? (a.lut16 ? 6 : 4) : (a.pp_d >= 2 && a.pp_d <= 4) ? 5 : 3) : want_raw ? 2 : (pair && a.pair16) ? 7 : pair ? 1 : 0;
-            const K* tab[8] = {plain, pairk, rawk, sok, sork, solk, sorhk, pairqk};
-            const K& k = tab[fam][a.variant - 5];
-            kfn = k.fn;
-            sl.kernel_name = k.name;
-            kidx = 1 + fam * 4 + (a.variant - 5);
-        } else {
-            kfn = (const void*)tps_scan_kernel;
-            sl.kernel_name = "tps_scan_kernel";
-            kidx = 0;
-        }
+    // which kernel the plan launches: the generic one, or the fused kernel of its slide and family
+    const ScanKernel* k = &GENERIC_KERNEL;
+    size_t* lds_set = &c->lds_set_generic;
+    if (tps::has_specialised_slide(a.variant) || tps::has_default_only_slide(a.variant)) {
+        const ScanFamily fam = scan_family(a, a.raw != nullptr);
+        k = &FUSED_KERNELS[fam][a.variant - KSLIDE_MIN];
+        lds_set = &c->lds_set_fused[fam][a.variant - KSLIDE_MIN];
     }
-    if (sl.lds_bytes > c->lds_set_v[kidx]) {
-        HIP_TRY(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sl.lds_bytes));
-        c->lds_set_v[kidx] = sl.lds_bytes;
+    sl.kernel_name = k->name;
+    if (sl.lds_bytes > *lds_set) {
+        HIP_TRY(hipFuncSetAttribute(k->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sl.lds_bytes));
+        *lds_set = sl.lds_bytes;
     }
-    if (c->ev_used == c->ev_pool.size()) {
-        if (c->ev_pool.size() >= 16384) {
-            c->ev_used = c->ev_base = 0;                  // wrap: the measurement window restarts
-        } else {
-            // events are created in batches, never one per launch (hipEventCreate costs ~60 us)
-            const size_t grow = c->ev_pool.empty() ? 512 : c->ev_pool.size();
-            for (size_t i = 0; i < grow; ++i) {
-                EventPair ep;
-                HIP_TRY(hipEventCreate(&ep.a));
-                HIP_TRY(hipEventCreate(&ep.b));
-                c->ev_pool.push_back(ep);
-            }
-        }
-    }
-    const bool timed = !inner && !c->no_events && (c->launch_seq++ % (uint64_t)c->event_stride) == 0;
-    EventPair& ep = c->ev_pool[timed ? c->ev_used++ : 0];
+    EventPair ev;
+    if ((rc = next_events(c, inner, ev))) return rc;
     if (sl.stride_base) {
         // (timed from the base kernel's start to the end of the compaction + change-point kernel)
-        if ((rc = do_scan_strided(c, sl, prm, sl.stride_base, timed ? ep.a : nullptr, timed ? ep.b : nullptr))) return rc;
+        if ((rc = do_scan_strided(c, sl, prm, sl.stride_base, ev.a, ev.b))) return rc;
         sl.scanned = true;
         return TPS_OK;
     }
@@ -928,8 +898,8 @@ int do_scan(tps_ctx* c, Slot& sl, const tps_params& prm, bool inner, hipEvent_t 
         // kept consecutive launches from running back to back)
         const int64_t grid = (n + a.wpg - 1) / a.wpg;
         void* kargs[] = {(void*)&a};
-        HIP_TRY(hipExtLaunchKernel(kfn, dim3((unsigned)grid), dim3(tps::NT * a.wpg), kargs, sl.lds_bytes, c->stream,
-                                   inner ? ev_start : (timed ? ep.a : nullptr), timed ? ep.b : nullptr, 0));
+        HIP_TRY(hipExtLaunchKernel(k->fn, dim3((unsigned)grid), dim3(tps::NT * a.wpg), kargs, sl.lds_bytes, c->stream,
+                                   inner ? ev_start : ev.a, ev.b, 0));
     }
     sl.scanned = true;
     return TPS_OK;
@@ -982,29 +952,6 @@ int tps_ctx_destroy(tps_ctx* c) {
     if (!c) return TPS_OK;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
-    for (auto& sl : c->slots) {
-        if (sl.sub) {
-            Slot& sb = *sl.sub;
-            sb.seq2.release(); sb.inv.release(); sb.desc.release(); sb.tails.release(); sb.results.release(); sb.win_off16.release();
-            sb.c_start.release(); sb.c_end.release(); sb.win_off.release(); sb.sums.release(); sb.raw.release(); sb.stamps.release(); sb.lc.release(); sb.order.release();
-            if (sb.h_results) (void)hipHostFree(sb.h_results);
-            delete sl.sub;
-            sl.sub = nullptr;
-        }
-        sl.seq2.release(); sl.inv.release(); sl.desc.release(); sl.tails.release(); sl.results.release(); sl.win_off16.release();
-        sl.c_start.release(); sl.c_end.release(); sl.win_off.release(); sl.sums.release(); sl.raw.release(); sl.stamps.release(); sl.lc.release(); sl.order.release();
-        if (sl.h_results) (void)hipHostFree(sl.h_results);
-    }
-    for (auto& t : c->tables) t.dev.release();
-    for (auto& t : c->wtables) t.dev.release();
-    c->ascii.release();
-    c->ascii_off.release();
-    c->nib.release();
-    c->nib_src.release();
-    c->follow_picks.release();
-    c->follow_hist.release();
-    c->motif_hits.release();
-    c->motif_counts.release();
     for (void* hp : c->pinned) {
         { std::lock_guard<std::mutex> lk(g_pinned_mu); g_pinned.erase((uintptr_t)hp); }
         (void)hipHostFree(hp);
@@ -1018,7 +965,7 @@ int tps_ctx_destroy(tps_ctx* c) {
     c->pinned.clear();
     for (auto& ep : c->ev_pool) { (void)hipEventDestroy(ep.a); (void)hipEventDestroy(ep.b); }
     (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;                                      // (device buffers go with what holds them: DevBuf, Slot)
     return TPS_OK;
 }
 
@@ -1305,8 +1252,11 @@ int tps_batch_kmer_followers_wide(tps_ctx* c, int32_t slot, int32_t n_fwd, int32
     if (follow < 0) return fail(TPS_E_ARG, "follow must not be negative");
     if (lo < 0 || hi <= lo || hi - lo > tps::FOLLOW_MAX_SPAN) return fail(TPS_E_CAPACITY, "the scanned range [lo, hi) must hold 1..%d bases", tps::FOLLOW_MAX_SPAN);
     if (hist && follow > 8) return fail(TPS_E_CAPACITY, "the followers histogram has 4^follow bins: follow must be 0..8 bases with it (pass no hist for more)");
-    const size_t lds_max = c->prop.sharedMemPerBlock > 0 ? c->prop.sharedMemPerBlock : 64 * 1024;
-    if ((size_t)tps::followers_wide_wg_lds_dwords() * 4 > lds_max)
+    // (static LDS of at most 64 KB: the 160 KB cap of lds_budget_dw never decides here.  The assertion restates the sum of
+    // followers_wide_wg_lds_dwords(), which is not constexpr; should the two drift apart, the kernel's own static array, sized by
+    // the same constants, still refuses to compile beyond 64 KB)
+    static_assert((tps::WIDE_IMG_DW + tps::WPG * tps::FOLLOWW_LDS_DW) * 4 <= 64 * 1024, "tps_followers_kernel_wide: followers_wide_wg_lds_dwords() within every device's budget cap");
+    if (tps::followers_wide_wg_lds_dwords() > lds_budget_dw(c))
         return fail(TPS_E_CAPACITY, "the wide followers kernel needs %lld bytes of LDS per workgroup", (long long)tps::followers_wide_wg_lds_dwords() * 4);
     const int pw = (hi - lo + 31) / 32;
     const int64_t n = sl->n;
@@ -1432,7 +1382,7 @@ int tps_batch_window_offsets(tps_ctx* c, int32_t slot, int64_t* win_off, int64_t
     int rc;
     if ((rc = need_scanned(c, slot, &sl))) return rc;
     if (n1 != sl->n + 1 || !win_off) return fail(TPS_E_ARG, "win_off must hold n+1 entries");
-    memcpy(win_off, sl->h_win_off.data(), (size_t)n1 * 8);
+    memcpy(win_off, sl->lay.win_off.data(), (size_t)n1 * 8);
     return TPS_OK;
 }
 
@@ -1441,16 +1391,16 @@ int tps_batch_window_sums(tps_ctx* c, int32_t slot, int32_t* sums, int64_t nw) {
     int rc;
     if ((rc = need_scanned(c, slot, &sl))) return rc;
     if (!(sl->last_flags & TPS_F_STORE_SUMS)) return fail(TPS_E_STATE, "last scan did not store window sums");
-    if (nw != sl->h_win_off[(size_t)sl->n] || (nw > 0 && !sums)) return fail(TPS_E_ARG, "sums must hold %lld windows", (long long)sl->h_win_off[(size_t)sl->n]);
+    if (nw != sl->lay.win_off[(size_t)sl->n] || (nw > 0 && !sums)) return fail(TPS_E_ARG, "sums must hold %lld windows", (long long)sl->lay.win_off[(size_t)sl->n]);
     if (nw && sl->args.variant) {
         // fused kernels: 16-bit sums in the padded device layout -> the caller's contiguous int32 array
-        const int64_t n16 = sl->h_win_off16[(size_t)sl->n];
+        const int64_t n16 = sl->lay.win_off16[(size_t)sl->n];
         sl->h_sums16.resize((size_t)n16);
         HIP_TRY(hipMemcpy(sl->h_sums16.data(), sl->sums.p, (size_t)n16 * 2, hipMemcpyDeviceToHost));
         for (int64_t i = 0; i < sl->n; ++i) {
-            const uint16_t* src = sl->h_sums16.data() + sl->h_win_off16[(size_t)i];
-            int32_t* dst = sums + sl->h_win_off[(size_t)i];
-            const int64_t cnt = sl->h_win_off[(size_t)i + 1] - sl->h_win_off[(size_t)i];
+            const uint16_t* src = sl->h_sums16.data() + sl->lay.win_off16[(size_t)i];
+            int32_t* dst = sums + sl->lay.win_off[(size_t)i];
+            const int64_t cnt = sl->lay.win_off[(size_t)i + 1] - sl->lay.win_off[(size_t)i];
             for (int64_t w = 0; w < cnt; ++w) dst[w] = (int32_t)src[w];
         }
     } else if (nw) {
@@ -1465,12 +1415,12 @@ int tps_batch_read_sums(tps_ctx* c, int32_t slot, int64_t read, int32_t* sums, i
     if ((rc = need_scanned(c, slot, &sl))) return rc;
     if (!(sl->last_flags & TPS_F_WINDOWS)) return fail(TPS_E_STATE, "last scan did not run the window step");
     if (read < 0 || read >= sl->n) return fail(TPS_E_ARG, "read %lld out of range", (long long)read);
-    const int64_t lo = sl->h_win_off[(size_t)read], cnt = sl->h_win_off[(size_t)read + 1] - lo;
+    const int64_t lo = sl->lay.win_off[(size_t)read], cnt = sl->lay.win_off[(size_t)read + 1] - lo;
     if (nw != cnt || (nw > 0 && !sums)) return fail(TPS_E_ARG, "sums must hold %lld windows", (long long)cnt);
     if (!nw) return TPS_OK;
     if (sl->args.variant) {
         sl->h_sums16.resize((size_t)nw);
-        HIP_TRY(hipMemcpy(sl->h_sums16.data(), (const uint16_t*)sl->sums.p + sl->h_win_off16[(size_t)read], (size_t)nw * 2, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(sl->h_sums16.data(), (const uint16_t*)sl->sums.p + sl->lay.win_off16[(size_t)read], (size_t)nw * 2, hipMemcpyDeviceToHost));
         for (int64_t w = 0; w < nw; ++w) sums[w] = (int32_t)sl->h_sums16[(size_t)w];
     } else {
         HIP_TRY(hipMemcpy(sums, (const int32_t*)sl->sums.p + lo, (size_t)nw * 4, hipMemcpyDeviceToHost));
@@ -1483,7 +1433,7 @@ int tps_batch_window_raw(tps_ctx* c, int32_t slot, uint8_t* raw, int64_t nwp) {
     int rc;
     if ((rc = need_scanned(c, slot, &sl))) return rc;
     if (!(sl->last_flags & TPS_F_STORE_RAW)) return fail(TPS_E_STATE, "last scan did not store raw counts");
-    int64_t want = sl->h_win_off[(size_t)sl->n] * sl->plan_p;
+    int64_t want = sl->lay.win_off[(size_t)sl->n] * sl->plan_p;
     if (nwp != want || (nwp > 0 && !raw)) return fail(TPS_E_ARG, "raw must hold %lld bytes", (long long)want);
     if (nwp) HIP_TRY(hipMemcpy(raw, sl->raw.p, (size_t)nwp, hipMemcpyDeviceToHost));
     return TPS_OK;
@@ -1513,7 +1463,7 @@ int tps_batch_raw_to_fd(tps_ctx* c, int32_t slot, const int64_t* reads, int64_t 
         const int64_t i = reads[j];
         if (i <= prev || i >= sl->n) return fail(TPS_E_ARG, "reads[] must be ascending indices of the batch (entry %lld)", (long long)j);
         prev = i;
-        const int64_t lo = sl->h_win_off[(size_t)i] * P, hi = sl->h_win_off[(size_t)i + 1] * P;
+        const int64_t lo = sl->lay.win_off[(size_t)i] * P, hi = sl->lay.win_off[(size_t)i + 1] * P;
         if (hi == lo) continue;
         if (!runs.empty() && runs.back().hi == lo) runs.back().hi = hi;
         else runs.push_back({lo, hi});
@@ -1637,10 +1587,10 @@ int tps_window_counts(tps_ctx* c, const uint8_t* bases, const int64_t* offsets, 
     p.flags = TPS_F_WINDOWS | TPS_F_TAILS_IN | TPS_F_STORE_SUMS | (raw ? TPS_F_STORE_RAW : 0u);
     if ((rc = do_scan(c, sl, p))) return rc;
     for (int64_t i = 0; i <= n; ++i)
-        if (win_off[i] != sl.h_win_off[(size_t)i])
+        if (win_off[i] != sl.lay.win_off[(size_t)i])
             return fail(TPS_E_ARG, "win_off[%lld]=%lld does not match the window layout (%lld)", (long long)i,
-                        (long long)win_off[i], (long long)sl.h_win_off[(size_t)i]);
-    int64_t nw = sl.h_win_off[(size_t)n];
+                        (long long)win_off[i], (long long)sl.lay.win_off[(size_t)i]);
+    int64_t nw = sl.lay.win_off[(size_t)n];
     if ((rc = tps_batch_window_sums(c, INTERNAL_SLOT, sums, nw))) return rc;
     if (raw && (rc = tps_batch_window_raw(c, INTERNAL_SLOT, raw, nw * c->pat.P))) return rc;
     return TPS_OK;

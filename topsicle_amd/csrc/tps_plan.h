@@ -52,6 +52,40 @@ inline void plan_dispatch_order(const int64_t* n_win, const uint8_t* passes, int
 // that every read's region starts 16-byte aligned and the dword that holds an odd last window ends in padding.
 inline int64_t sums16_slots(int64_t nw) { return (nw + 7) & ~7ll; }
 
+// Window layout of a batch at one set of parameters: where each read's windows start in the output arrays and in which order the
+// wave slots take the reads.  offsets[n + 1] = the reads' lengths as running sums (the ASCII batch's offsets).  The library plans
+// every scan from this and the emulations run their reads through it, so the host arithmetic is checked without a GPU.
+struct BatchLayout {
+    std::vector<int64_t> win_off;     // [n + 1] first window of read i (window_count windows each)
+    std::vector<int64_t> win_off16;   // [n + 1] ... in the fused kernels' 16-bit sums (sums16_slots: every read padded to a multiple of 8 windows)
+    std::vector<int32_t> order;       // plan_dispatch_order; empty = file order
+    int64_t max_nwin = 0;             // windows of the read with the most
+    int64_t max_len = 0;              // bases of the longest read
+};
+inline void plan_batch_layout(const int64_t* offsets, int64_t n, const tps_params& prm, BatchLayout& lay) {
+    lay.win_off.resize((size_t)n + 1);
+    lay.win_off16.resize((size_t)n + 1);
+    lay.max_nwin = lay.max_len = 0;
+    std::vector<int64_t> nwv((size_t)n);
+    std::vector<uint8_t> longer((size_t)n);
+    int64_t acc = 0, acc16 = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        lay.win_off[(size_t)i] = acc;
+        lay.win_off16[(size_t)i] = acc16;
+        const int64_t len = offsets[i + 1] - offsets[i];
+        const int64_t nw = window_count(len, prm.window, prm.slide, prm.trimfirst, prm.maxlen);
+        lay.max_len = std::max(lay.max_len, len);
+        lay.max_nwin = std::max(lay.max_nwin, nw);
+        acc += nw;
+        acc16 += sums16_slots(nw);
+        nwv[(size_t)i] = (prm.flags & TPS_F_WINDOWS) ? nw : 0;
+        longer[(size_t)i] = !(prm.flags & TPS_F_STEP1) || len > prm.min_len;      // (scan_read: pass = L > min_len && ...)
+    }
+    lay.win_off[(size_t)n] = acc;
+    lay.win_off16[(size_t)n] = acc16;
+    plan_dispatch_order(nwv.data(), longer.data(), n, lay.order);
+}
+
 inline int gcd_i(int a, int b) { while (b) { int t = a % b; a = b; b = t; } return a; }
 
 // Pattern list (P strings of k letters, reference order) -> 4^k lookup table of list masks and
