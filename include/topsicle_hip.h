@@ -297,6 +297,31 @@ typedef struct tps_motif_hit {        /* 32 bytes */
 int  tps_batch_motif_census(tps_ctx* ctx, int32_t slot, int32_t u_min, int32_t u_max, int32_t lo, int32_t hi, int32_t min_len,
                             tps_motif_hit* hits, int64_t n_hits, int32_t* counts, int64_t counts_len);
 
+/* ---- variant census (what the called telomere tract is made of) ---------------------------- */
+/* Canonical repeats, units with one substituted letter, and the rest, for a tract [begin, end) per read of the resident batch;
+ * no pattern table (the reference has nothing comparable).  `unit` is a primitive word U of m letters, 2 <= m <= 32, as
+ * tps_motif_hit.unit spells it: 2-bit codes A C T G = 0 1 2 3, letter j in bits [2j, 2j+1], nothing behind them; not a power of
+ * a shorter word.  For read r, h = the upper-cased read (tails[r] = 0) or its reverse complement (tails[r] = 1) -- "telomere
+ * first", the orientation the motif census uses and --pattern is given in -- and end[r] is clamped to L.  A read with
+ * end - begin < m contributes nothing (its row stays zero).  Otherwise every i in [begin, end - m] is EXAMINED (n += 1), with
+ * x = h[i .. i + m) and R_j = U rotated left by j (R_j[q] = U[(j + q) mod m]):
+ *   - a letter of x that is not ACGT: the position is "other";
+ *   - else the smallest j with Hamming(x, R_j) <= 1 decides: distance 0 is CANONICAL; distance 1 with the mismatch at q is the
+ *     VARIANT (p, c), p = (j + q) mod m the place in U as given, c the code of the letter x[q]  (U = AAAC, x = AAAA: j = 0,
+ *     p = 3, c = A).  The rotations of a primitive word differ pairwise in >= 2 places: a canonical position is never a variant;
+ *   - no such j: "other".
+ * The position falls in bin min((end - 1 - i) / bin, n_bins - 1): bins are measured back from the boundary.
+ *   counts  uint32[n_reads][2 + 4m]: [0] = n, [1] = canonical, [2 + 4p + c] = variant (p, c) (c = U[p] stays 0);
+ *           other = n - everything else.
+ *   profile int64[n_bins][2 + 4m] or NULL: the same row summed over all reads of the batch, per bin.
+ * Both are exact sums: identical from run to run.  TPS_E_ARG: m outside 2..32, a unit that is a power of a shorter word (or has
+ * codes behind its m letters), a negative begin / end, begin > end, a tail other than 0 / 1, n_reads or an array length that
+ * does not match the slot.  TPS_E_CAPACITY: bin outside 64..4064, n_bins outside 1..64.  TPS_E_STATE: an empty slot.
+ * One launch; returns when the outputs are in place.  The slot's scan state (tails, results, sums, raw rows) is not touched. */
+int  tps_batch_variant_census(tps_ctx* ctx, int32_t slot, uint64_t unit, int32_t m, const uint8_t* tails, const int32_t* begin,
+                              const int32_t* end, int64_t n_reads, int32_t bin, int32_t n_bins, uint32_t* counts,
+                              int64_t counts_len, int64_t* profile, int64_t profile_len);
+
 /* ---- measurement ----------------------------------------------------------------------- */
 /* hipEvent timings of the scan kernel launches since the last reset: number of launches,
  * total and mean milliseconds (events are recorded on the stream the kernel runs on). */

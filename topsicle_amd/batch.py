@@ -42,11 +42,14 @@ class Job:
     batch = `--telophrase 4 5 6`: the batch is parsed, packed and uploaded ONCE and scanned once per k (the reference
     re-parses the input for every k, main.py:206-235)."""
 
-    def __init__(self, patterns, prm: hiplib.Params, want_sums=False, want_raw=False, raw_sink=None):
+    def __init__(self, patterns, prm: hiplib.Params, want_sums=False, want_raw=False, raw_sink=None, variants=None):
         """raw_sink (with want_raw; rawnpz.RawNpzWriter): the raw rows of the reads the sink selects are written to its file by
-        the worker that scanned the batch, device -> file, and the caller gets a `RawKept` in place of the rows."""
+        the worker that scanned the batch, device -> file, and the caller gets a `RawKept` in place of the rows.
+        variants (variants.VariantSpec: unit, bin, n_bins, sink): the worker that scanned the batch runs the variant census of the
+        called tracts on it while it is still resident and hands (recs, results, counts, profile) to the spec's sink."""
         self.patterns, self.prm, self.want_sums, self.want_raw = list(patterns), prm, bool(want_sums), bool(want_raw)
         self.raw_sink = raw_sink if want_raw else None
+        self.variants = variants
 
 
 class CensusJob:
@@ -103,6 +106,27 @@ def _sink_rows(job, seq, eng, slot, recs, res, slot_index=None):
     slot_reads = keep if slot_index is None else np.searchsorted(slot_index, keep)
     sink.write_batch(seq, eng, slot, slot_reads, int(res["n_win"][keep].astype(np.int64).sum()))
     return RawKept(keep)
+
+
+def _census_variants(job, eng, slot, recs, res, slot_index=None):
+    """The variant census of the tracts the scan has just called (Job.variants), on the engine and slot that were scanned: the tract
+    of a read is [trimfirst, boundary) of its telomere-first string, boundary = bkp * slide + trimfirst where the CLI would store it
+    (variants.tract_bounds); every other read gets begin = end = 0.  `slot_index`: the batch indices of the reads resident in
+    `slot` when that is not the whole batch (second pass of the two-pass route: the passing reads only -- their packed span is the
+    first / last min(L, maxlen) bases, so the coordinates are those of the whole read), None with nothing resident: no read passed."""
+    from . import variants
+    spec = job.variants
+    m = len(spec.unit)
+    begin, end = variants.tract_bounds(res, int(job.prm.trimfirst), int(job.prm.slide), int(job.prm.maxlen))
+    tails = np.where(end > begin, res["tail"], 0).astype(np.uint8)
+    counts = np.zeros((len(res), 2 + 4 * m), np.uint32)
+    profile = np.zeros((spec.n_bins, 2 + 4 * m), np.int64)
+    if slot_index is None:
+        if eng is not None:
+            counts, profile = eng.variant_census(slot, spec.unit, tails, begin, end, spec.bin, spec.n_bins)
+    elif len(slot_index):
+        counts[slot_index], profile = eng.variant_census(slot, spec.unit, tails[slot_index], begin[slot_index], end[slot_index], spec.bin, spec.n_bins)
+    spec.sink(recs, res, counts, profile)
 
 
 def upload_batch(engine, recs, slot: int = 0):
@@ -212,6 +236,8 @@ def scan_jobs_heads(engine, recs, jobs, slot: int = 0, seq=None):
                     hiplib.resolve_ties(eng, slot_b, rb, len(job.patterns), p.jump, p.min_size)
                 for f in ("n_win", "bkp", "gain", "flags"):
                     res[f][idx] = rb[f]
+                if getattr(job, "variants", None) is not None:
+                    _census_variants(job, eng, slot_b, recs, res, slot_index=idx)
                 np.cumsum(np.where(passing, res["n_win"], 0), out=win_off[1:])
                 if job.want_sums:
                     sums, wo_b = eng.window_sums(slot_b)
@@ -222,6 +248,8 @@ def scan_jobs_heads(engine, recs, jobs, slot: int = 0, seq=None):
                     raw, wo_b = eng.window_raw(slot_b)
                     assert int(wo_b[-1]) == int(win_off[-1])
             else:
+                if getattr(job, "variants", None) is not None:
+                    _census_variants(job, None, slot_b, recs, res)             # (no read passed: an all-zero answer)
                 if job.want_sums:
                     sums = np.zeros(0, np.int32)
                 if job.want_raw and job.raw_sink is not None and seq is not None:
@@ -291,6 +319,8 @@ def scan_jobs(engine, recs, jobs, slot: int = 0, seq=None):
             res = eng.results(slot)
             if p.flags & hiplib.F_BINSEG:              # exact ties: ruptures' float64 answer (a handful of reads at most)
                 hiplib.resolve_ties(eng, slot, res, len(job.patterns), p.jump, p.min_size)
+            if getattr(job, "variants", None) is not None:
+                _census_variants(job, eng, slot, recs, res)
             sums = raw = win_off = None
             if job.want_sums:
                 sums, win_off = eng.window_sums(slot)

@@ -22,6 +22,7 @@
 
 #include "tps_device.h"
 #include "tps_motif.h"
+#include "tps_variant.h"
 #include "tps_pack.h"
 #include "tps_plan.h"
 #include "tps_wide.h"
@@ -100,6 +101,15 @@ __global__ void __launch_bounds__(NT * WPG) motif_census_kernel(MotifArgs a) {
     const int64_t r = (int64_t)blockIdx.x * WPG + wave;
     if (r >= a.n_reads) return;
     motif_read(a, r, smem + wave * MOTIF_LDS_DW);
+}
+// The variant census (tps_batch_variant_census; variant_read in csrc/tps_variant.h): no table, one wave per read, the workgroup
+// picks the partial profile.
+__global__ void __launch_bounds__(NT * WPG) variant_census_kernel(VariantArgs a) {
+    __shared__ __attribute__((aligned(16))) uint32_t smem[WPG * VARIANT_LDS_DW];
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t r = (int64_t)blockIdx.x * WPG + wave;
+    if (r >= a.n_reads) return;
+    variant_read(a, r, smem + wave * VARIANT_LDS_DW, (int)(blockIdx.x % VARIANT_PARTS));
 }
 }  // namespace tps
 
@@ -359,6 +369,8 @@ struct tps_ctx {
     size_t table_rr = 0;
     DevBuf follow_picks, follow_hist; // outputs of tps_batch_kmer_followers
     DevBuf motif_hits, motif_counts;  // outputs of tps_batch_motif_census
+    DevBuf variant_in, variant_counts, variant_prof;      // tps_batch_variant_census: tails / begin / end, its outputs
+    std::vector<unsigned long long> h_variant_prof;        // ... the partial profiles as downloaded
     DevBuf ascii, ascii_off;          // staging of tps_batch_upload: ASCII bases + offsets, packed on the device right after the copy
     DevBuf nib, nib_src;              // staging of tps_batch_upload_nib4: BAM base codes + where each read's are, expanded right after the copy
     std::set<void*> pinned;           // host buffers handed out by tps_host_alloc
@@ -1324,6 +1336,72 @@ int tps_batch_motif_census(tps_ctx* c, int32_t slot, int32_t u_min, int32_t u_ma
     HIP_TRY(hipMemcpyAsync(hits, c->motif_hits.p, hit_bytes, hipMemcpyDeviceToHost, c->stream));
     if (counts) HIP_TRY(hipMemcpyAsync(counts, c->motif_counts.p, cnt_bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    return TPS_OK;
+}
+
+int tps_batch_variant_census(tps_ctx* c, int32_t slot, uint64_t unit, int32_t m, const uint8_t* tails, const int32_t* begin, const int32_t* end,
+                             int64_t n_reads, int32_t bin, int32_t n_bins, uint32_t* counts, int64_t counts_len, int64_t* profile, int64_t profile_len) {
+    int rc;
+    if ((rc = bind(c))) return rc;
+    Slot* sl = get_slot(c, slot);
+    if (!sl) return TPS_E_ARG;
+    if (sl->n < 0) return fail(TPS_E_STATE, "no batch uploaded in this slot");
+    if (m < 2 || m > tps::VARIANT_MAX_UNIT) return fail(TPS_E_ARG, "the unit must have 2..%d letters", tps::VARIANT_MAX_UNIT);
+    if (m < 32 && (unit >> (2 * m)) != 0) return fail(TPS_E_ARG, "the unit has codes behind its %d letters", m);
+    for (int d = 1; d < m; ++d) {
+        if (m % d) continue;
+        const uint64_t rot = (unit >> (2 * d)) | (unit << (2 * (m - d)));       // the unit rotated left by d letters
+        if (((rot ^ unit) & (~0ull >> (64 - 2 * m))) == 0) return fail(TPS_E_ARG, "the unit is a power of its first %d letters: pass the primitive root", d);
+    }
+    if (bin < tps::VARIANT_MIN_BIN || bin > tps::VARIANT_MAX_BIN) return fail(TPS_E_CAPACITY, "bin must be %d..%d positions", tps::VARIANT_MIN_BIN, tps::VARIANT_MAX_BIN);
+    if (n_bins < 1 || n_bins > tps::VARIANT_MAX_BINS) return fail(TPS_E_CAPACITY, "n_bins must be 1..%d", tps::VARIANT_MAX_BINS);
+    const int64_t n = sl->n;
+    const int cols = 2 + 4 * m;
+    if (n_reads != n) return fail(TPS_E_ARG, "tails, begin and end must hold %lld reads", (long long)n);
+    if (n > 0 && (!tails || !begin || !end)) return fail(TPS_E_ARG, "null tails / begin / end");
+    if ((!counts && n > 0) || counts_len != n * cols) return fail(TPS_E_ARG, "counts must hold %lld counters", (long long)(n * cols));
+    if (profile && profile_len != (int64_t)n_bins * cols) return fail(TPS_E_ARG, "profile must hold %lld counters", (long long)n_bins * cols);
+    for (int64_t i = 0; i < n; ++i) {
+        if (tails[i] > 1) return fail(TPS_E_ARG, "read %lld: tail must be 0 or 1", (long long)i);
+        if (begin[i] < 0 || end[i] < 0 || begin[i] > end[i]) return fail(TPS_E_ARG, "read %lld: need 0 <= begin <= end", (long long)i);
+    }
+    if (profile) memset(profile, 0, (size_t)profile_len * 8);
+    if (n == 0) return TPS_OK;
+    // (the table, the slot's tails, its scan outputs and its plan are not touched: a scan before and after the census gives the same results)
+    const size_t cnt_bytes = (size_t)n * cols * 4, part_len = (size_t)n_bins * cols, prof_bytes = tps::VARIANT_PARTS * part_len * 8;
+    const size_t off_begin = (((size_t)n + 15) & ~(size_t)15), off_end = off_begin + (size_t)n * 4;
+    if ((rc = c->variant_in.ensure(off_end + (size_t)n * 4))) return rc;
+    if ((rc = c->variant_counts.ensure(cnt_bytes))) return rc;
+    HIP_TRY(hipMemcpyAsync(c->variant_in.p, tails, (size_t)n, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync((char*)c->variant_in.p + off_begin, begin, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync((char*)c->variant_in.p + off_end, end, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(c->variant_counts.p, 0, cnt_bytes, c->stream));
+    if (profile) {
+        if ((rc = c->variant_prof.ensure(prof_bytes))) return rc;
+        HIP_TRY(hipMemsetAsync(c->variant_prof.p, 0, prof_bytes, c->stream));
+    }
+    tps::VariantArgs a{};
+    a.seq2 = (const uint32_t*)sl->seq2.p;
+    a.inv = (const uint16_t*)sl->inv.p;
+    a.desc = (const tps_read_desc*)sl->desc.p;
+    a.tails = (const uint8_t*)c->variant_in.p;
+    a.begin = (const int32_t*)((const char*)c->variant_in.p + off_begin);
+    a.end = (const int32_t*)((const char*)c->variant_in.p + off_end);
+    a.counts = (uint32_t*)c->variant_counts.p;
+    a.prof = profile ? (unsigned long long*)c->variant_prof.p : nullptr;
+    a.n_reads = n;
+    a.unit = unit; a.m = m; a.bin = bin; a.n_bins = n_bins;
+    hipLaunchKernelGGL(tps::variant_census_kernel, dim3((unsigned)((n + tps::WPG - 1) / tps::WPG)), dim3(tps::NT * tps::WPG), 0, c->stream, a);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(counts, c->variant_counts.p, cnt_bytes, hipMemcpyDeviceToHost, c->stream));
+    if (profile) {
+        c->h_variant_prof.resize(tps::VARIANT_PARTS * part_len);
+        HIP_TRY(hipMemcpyAsync(c->h_variant_prof.data(), c->variant_prof.p, prof_bytes, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (profile)
+        for (int p = 0; p < tps::VARIANT_PARTS; ++p)
+            for (size_t i = 0; i < part_len; ++i) profile[i] += (int64_t)c->h_variant_prof[p * part_len + i];
     return TPS_OK;
 }
 

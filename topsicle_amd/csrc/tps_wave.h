@@ -261,6 +261,7 @@ TPS_DEV uint32_t lds_add_ret(uint32_t* p, uint32_t v) { uint32_t o = *p; *p += v
 TPS_DEV void lds_max_u64(uint64_t* p, uint64_t v) { if (v > *p) *p = v; }
 TPS_DEV void lds_max_i32(int32_t* p, int32_t v) { if (v > *p) *p = v; }
 TPS_DEV void hist_add(unsigned long long* p) { *p += 1ull; }
+TPS_DEV void hist_add_n(unsigned long long* p, uint32_t v) { *p += v; }
 struct u32x4 { uint32_t x, y, z, w; };
 struct u32x2 { uint32_t x, y; };
 TPS_DEV u32x4 load16(const uint8_t* p) { return *(const u32x4*)p; }
@@ -288,6 +289,7 @@ TPS_DEV uint32_t lds_add_ret(uint32_t* p, uint32_t v) { return atomicAdd(p, v); 
 TPS_DEV void lds_max_u64(uint64_t* p, uint64_t v) { atomicMax((unsigned long long*)p, (unsigned long long)v); }
 TPS_DEV void lds_max_i32(int32_t* p, int32_t v) { atomicMax(p, v); }
 TPS_DEV void hist_add(unsigned long long* p) { atomicAdd(p, 1ull); }
+TPS_DEV void hist_add_n(unsigned long long* p, uint32_t v) { atomicAdd(p, (unsigned long long)v); }
 typedef uint4 u32x4;
 typedef uint2 u32x2;
 // 16-byte load that is KNOWN to hit global memory: the address was rebuilt from an integer (aligned
@@ -421,9 +423,12 @@ TPS_DEV uint32_t add_bytes(uint32_t v, uint32_t acc) { return __builtin_amdgcn_s
 #ifdef TPS_EMU
 TPS_DEV uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) { return a ^ b ^ c; }
 TPS_DEV uint32_t maj3(uint32_t a, uint32_t b, uint32_t c) { return (a & b) | (c & (a | b)); }
+TPS_DEV uint32_t or_and(uint32_t a, uint32_t b, uint32_t c) { return (a | b) & c; }
 #else
 TPS_DEV uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) { return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96); }
 TPS_DEV uint32_t maj3(uint32_t a, uint32_t b, uint32_t c) { return __builtin_amdgcn_bitop3_b32(a, b, c, 0xE8); }
+// (a | b) & c, one v_bitop3_b32 as well (the compiler leaves v_or + v_and where c is a literal)
+TPS_DEV uint32_t or_and(uint32_t a, uint32_t b, uint32_t c) { return __builtin_amdgcn_bitop3_b32(a, b, c, 0xA8); }
 #endif
 
 // two 16-bit lanes in one word (lane 0 = bits 0 .. 15): lane-wise a - b; a + the low half of b in both

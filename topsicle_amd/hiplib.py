@@ -23,7 +23,7 @@ FOLLOW_MAX_FWD, FOLLOW_WIDE_MAX_FWD, FOLLOW_HIST_MAX = 15, 32, 8      # k-mers t
 EXPORTS = [
     "tps_abi_version", "tps_device_count", "tps_ctx_create", "tps_ctx_destroy", "tps_last_error",
     "tps_set_patterns", "tps_set_patterns_wide", "tps_batch_upload", "tps_batch_upload_packed", "tps_batch_upload_nib4", "tps_batch_share", "tps_host_alloc", "tps_host_free",
-    "tps_batch_download_packed", "tps_batch_kmer_followers", "tps_batch_kmer_followers_wide", "tps_batch_motif_census", "tps_batch_set_tails", "tps_batch_scan", "tps_sync",
+    "tps_batch_download_packed", "tps_batch_kmer_followers", "tps_batch_kmer_followers_wide", "tps_batch_motif_census", "tps_batch_variant_census", "tps_batch_set_tails", "tps_batch_scan", "tps_sync",
     "tps_batch_results", "tps_batch_window_offsets", "tps_batch_window_sums", "tps_batch_window_raw",
     "tps_batch_raw_to_fd", "tps_batch_trc_counts", "tps_trc_counts", "tps_window_counts", "tps_binseg_l2", "tps_binseg_l2_ties", "tps_batch_read_sums", "tps_window_count",
     "tps_kernel_time_ms", "tps_kernel_time_reset", "tps_device_info", "tps_batch_kernel_info", "tps_ctx_debug_option", "tps_debug_stamps_get",
@@ -58,6 +58,7 @@ MOTIF_HIT_DTYPE = np.dtype([("unit", "<u8"), ("period", "<i4"), ("support", "<i4
                             ("n_bases", "<i4"), ("reserved", "<i4")], align=True)                          # struct tps_motif_hit
 assert MOTIF_HIT_DTYPE.itemsize == 32
 MOTIF_MAX_PERIOD, MOTIF_MAX_SPAN = 32, 4096      # tps_batch_motif_census: the longest period, the most bases of a read end
+VARIANT_MAX_UNIT, VARIANT_BIN_RANGE, VARIANT_MAX_BINS = 32, (64, 4064), 64      # tps_batch_variant_census: letters of the unit, bin width, bins
 RES_TIE = 1            # TPS_RES_TIE: the exact tournament decided the change-point (candidates within float64 noise of each other)
 
 
@@ -101,6 +102,7 @@ def load_library(path: str | None = None) -> C.CDLL:
         "tps_batch_kmer_followers": (C.c_int, [vp, i32, i32, i32, i32, i32, i32, vp, i64, vp, i64]),
         "tps_batch_kmer_followers_wide": (C.c_int, [vp, i32, i32, i32, i32, i32, i32, vp, i64, vp, i64]),
         "tps_batch_motif_census": (C.c_int, [vp, i32, i32, i32, i32, i32, i32, vp, i64, vp, i64]),
+        "tps_batch_variant_census": (C.c_int, [vp, i32, C.c_uint64, i32, vp, vp, vp, i64, i32, i32, vp, i64, vp, i64]),
         "tps_batch_set_tails": (C.c_int, [vp, i32, vp]),
         "tps_batch_scan": (C.c_int, [vp, i32, C.POINTER(Params)]),
         "tps_sync": (C.c_int, [vp]),
@@ -439,6 +441,27 @@ class HipScanner:
         self._check(self.lib.tps_batch_motif_census(self._h, slot, u_min, u_max, lo, hi, min_len, _ptr(hits), hits.size,
                                                     _ptr(counts), 0 if counts is None else counts.size))
         return hits, counts
+
+    def variant_census(self, slot: int, unit: str, tails, begin, end, bin: int = 500, n_bins: int = 40, want_profile: bool = True):
+        """What the tract [begin, end) of every read of the resident batch is made of, against the primitive unit `unit` (a string
+        of ACGT, 2 .. 32 letters; tps_batch_variant_census, the rule is in include/topsicle_hip.h; names and columns:
+        topsicle_amd.variants): (counts uint32[n, 2 + 4m], profile int64[n_bins, 2 + 4m] or None).  Column 0 = positions examined,
+        1 = canonical, 2 + 4p + c = letter c (ACTG = 0123) seen at place p of the unit.  No pattern table needed; the slot's scan
+        outputs stay as they are."""
+        from . import variants
+        code, m = variants.unit_code(unit)
+        n = self._n[slot]
+        tails = np.ascontiguousarray(tails, dtype=np.uint8)
+        begin = np.ascontiguousarray(begin, dtype=np.int32)
+        end = np.ascontiguousarray(end, dtype=np.int32)
+        if not (len(tails) == len(begin) == len(end)):
+            raise TopsicleHipError("variant_census: tails, begin and end must have one entry per read")
+        cols = 2 + 4 * m
+        counts = np.zeros((n, cols), dtype=np.uint32)
+        profile = np.zeros((max(n_bins, 0), cols), dtype=np.int64) if want_profile else None      # (a bad bin count is the library's to refuse)
+        self._check(self.lib.tps_batch_variant_census(self._h, slot, code, m, _ptr(tails), _ptr(begin), _ptr(end), len(tails), bin, n_bins,
+                                                      _ptr(counts), counts.size, _ptr(profile), 0 if profile is None else profile.size))
+        return counts, profile
 
     def set_tails(self, slot: int, tails: np.ndarray):
         tails = np.ascontiguousarray(tails, dtype=np.uint8)

@@ -20,7 +20,7 @@ from collections import defaultdict
 
 import numpy as np
 
-from . import allsteps, batch, hiplib, motif, rawnpz, seqio
+from . import allsteps, batch, hiplib, motif, rawnpz, seqio, variants
 
 version_number = "1.0.0"
 Topsicle_output_prefix = "Topsicle"
@@ -142,11 +142,14 @@ def process_file_multi(args, seq_loc, phrases, engines):
     npz = want_raw and getattr(args, "rawcountformat", "csv") == "npz"
     raw_npz = [rawnpz.RawNpzWriter(f"{args.outputDir}/rawcount_{telo_phrase}_{file_name}.npz", pattern, sliding_val, args.read_check or None)
                if npz else None for telo_phrase, pattern, sliding_val in phrases]
+    # --variants: one collector per k for the whole run (analysis_run made them); the census runs on the batch workers
+    vcols = getattr(args, "variant_collectors", None) or [None] * len(phrases)
+    vrows = [[] for _ in phrases]
     jobs = [batch.Job(pattern, hiplib.make_params(
         no_bp=no_bp, min_len=args.minSeqLength, min_count=allsteps.min_count_for_cutoff(min_cutoff, ratio, no_bp),
         window=args.windowSize, slide=slide, trimfirst=args.trimfirst, maxlen=args.maxlengthtelo,
-        flags=hiplib.F_STEP1 | hiplib.F_WINDOWS | hiplib.F_BINSEG), want_sums, want_raw, raw_sink=sink)
-        for (_k, pattern, slide), sink in zip(phrases, raw_npz)]
+        flags=hiplib.F_STEP1 | hiplib.F_WINDOWS | hiplib.F_BINSEG), want_sums, want_raw, raw_sink=sink, variants=None if col is None else col.spec)
+        for (_k, pattern, slide), sink, col in zip(phrases, raw_npz, vcols)]
 
     fmt = _formats(seq_loc)
     fasta_temp = os.path.join(args.outputDir, f"{file_name}_trc_over_{min_cutoff}.fasta")
@@ -229,6 +232,7 @@ def process_file_multi(args, seq_loc, phrases, engines):
         for pb, outs in pool.scan_file_jobs(seq_loc, jobs, shards=n_shards, shard_min_bytes=shard_min):
             for n, ((telo_phrase, pattern, sliding_val), (res, sums, raw, win_off)) in enumerate(zip(phrases, outs)):
                 idx = np.nonzero(res["pass"])[0]
+                vout = vcols[n].take(pb) if vcols[n] is not None else None
                 if wthread is not None and len(idx) and n == writer_k:
                     write_passing(pb, idx)                                   # every passing record (main.py:83-86)
                 ids = [pb.read_id(int(i)) for i in idx]
@@ -248,6 +252,10 @@ def process_file_multi(args, seq_loc, phrases, engines):
                 for j in np.nonzero(bkp < 0)[0]:
                     tprint(f"read {ids[j]}: {int(r['n_win'][j])} windows, no admissible change point; reporting 0")
                 telo_l, trc_l = telolen.tolist(), trc.tolist()
+                if vout is not None:                                         # one row per read with a stored boundary
+                    v_begin, v_end, v_counts = vout
+                    vrows[n] += [(file_name, ids[j], int(r["tail"][j]), int(v_begin[idx[j]]), int(v_end[idx[j]]), v_counts[idx[j]])
+                                 for j in np.nonzero(telolen != 0)[0]]
                 if n == 0:
                     with _CSV_LOCK, open(csv_path, mode="a", newline="") as fh:
                         csv.writer(fh).writerows(zip([file_name] * len(ids), [telo_phrase] * len(ids), ["%.3f" % t for t in trc_l], ids, telo_l))
@@ -292,6 +300,9 @@ def process_file_multi(args, seq_loc, phrases, engines):
             nbytes = os.path.getsize(fasta_temp)
             tprint(f"{base_name}: {wstat['records']} passing records, {nbytes} bytes written in {wstat['write_s']:.2f} thread-seconds on {len(wthreads)} writer threads "
                    f"({nbytes / wstat['write_s'] / 1e9:.2f} GB/s per thread); the scan loop waited {wstat['blocked_s']:.2f} s for them")
+    for col, vr in zip(vcols, vrows):
+        if col is not None:
+            col.add_file_rows(seq_loc, vr)
     st = pool.stats
     if st.get("shards", 0) > 1:
         tprint(f"{base_name}: read as {st['shards']} byte ranges, one reader team each")
@@ -378,6 +389,18 @@ def analysis_run(args, engines=None, engine_factory=None, wait_plots=True):
         tprint("patterns to search:", pattern)
         phrases.append((telo_phrase, pattern, sliding_val))
 
+    args.variant_collectors = None
+    if getattr(args, "variants", False):
+        unit = variants.primitive_root(args.pattern.upper())
+        if unit != args.pattern.upper():
+            tprint(f"--variants: {args.pattern} is a power of {unit}; the census counts against {unit}")
+        lo, hi = hiplib.VARIANT_BIN_RANGE
+        if not (2 <= len(unit) <= hiplib.VARIANT_MAX_UNIT) or not (lo <= args.variantbin <= hi) or not (1 <= args.variantbins <= hiplib.VARIANT_MAX_BINS):
+            tprint(f"--variants needs a motif whose root has 2..{hiplib.VARIANT_MAX_UNIT} letters, --variantbin {lo}..{hi} and --variantbins 1..{hiplib.VARIANT_MAX_BINS}")
+            sys.exit(2)
+        args.variant_collectors = [variants.Collector(unit, args.variantbin, args.variantbins, args.trimfirst, slide, args.maxlengthtelo)
+                                   for _k, _pattern, slide in phrases]
+
     filenames = []
     if os.path.isdir(args.inputDir):
         for root, _dirs, files in os.walk(args.inputDir):
@@ -405,6 +428,13 @@ def analysis_run(args, engines=None, engine_factory=None, wait_plots=True):
         if late:                                   # rows of the later k's follow the first k's, in upstream's order
             with _CSV_LOCK, open(output_csv, mode="a", newline="") as fh:
                 csv.writer(fh).writerows(late)
+
+    for (telo_phrase, _pattern, _slide), col in zip(phrases, args.variant_collectors or []):
+        variants.write_reads_csv(f"{args.outputDir}/variants_{telo_phrase}.csv", col.unit, col.rows_in_order(filenames))
+        variants.write_profile_csv(f"{args.outputDir}/variant_profile_{telo_phrase}.csv", col.unit, col.profile, col.spec.bin)
+        tprint(f"variant repeats (k = {telo_phrase}): {args.outputDir}/variants_{telo_phrase}.csv, {args.outputDir}/variant_profile_{telo_phrase}.csv")
+        for line in variants.summary(col.unit, col.total, col.n_tracts):
+            tprint(line)
 
     t_sum = time.perf_counter()
     summarize(args, phrase_to_telo, phrase_to_trc)
@@ -548,6 +578,11 @@ def build_parser():
     parser.add_argument("--shards", metavar="INT", type=int, default=0,
                         help="MI355X build: cut ONE plain input file into this many byte ranges, each decoded by a reader thread team of its own "
                              "(0 = one per GPU when the file has at least 256 MiB per GPU; compressed files keep one reader)")
+    parser.add_argument("--variants", action="store_true",
+                        help="MI355X build: census of the called telomere tracts -- canonical repeats, repeats with one substituted letter (by place and letter), "
+                             "the rest -- per read (variants_{k}.csv) and per distance from the boundary (variant_profile_{k}.csv)")
+    parser.add_argument("--variantbin", metavar="INT", type=int, default=variants.DEFAULT_BIN, help="--variants: width of a profile bin in bases (64..4064)")
+    parser.add_argument("--variantbins", metavar="INT", type=int, default=variants.DEFAULT_BINS, help="--variants: bins of the profile, the last takes everything beyond (1..64)")
     parser.add_argument("--twopass", choices=["auto", "on", "off"], default=None,
                         help="MI355X build: upload only the two 1000-base ends of every read for the TRC filter and the scanned part of the "
                              "reads that pass afterwards (auto, the default unless $TOPSICLE_TWO_PASS says otherwise: while few reads of a batch pass, "
