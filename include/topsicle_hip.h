@@ -322,6 +322,35 @@ int  tps_batch_variant_census(tps_ctx* ctx, int32_t slot, uint64_t unit, int32_t
                               const int32_t* end, int64_t n_reads, int32_t bin, int32_t n_bins, uint32_t* counts,
                               int64_t counts_len, int64_t* profile, int64_t profile_len);
 
+/* ---- tract map (telomere-repeat tracts anywhere in a read, on either strand) ---------------- */
+/* Where in the WHOLE read repeats of a unit lie; no pattern table, nothing assumed about the read's ends (the reference has
+ * nothing comparable).  `unit` is a primitive word U of m letters, 4 <= m <= 32, spelled as tps_motif_hit.unit and
+ * tps_batch_variant_census spell it.  Strand 0 is U as given (the C strand, what a read's head shows), strand 1 its reverse
+ * complement; the read is always taken forward, as stored, upper-cased.
+ *   word    w = min(m, 8).  The cyclic words of a unit V are the m words (V V ...)[j .. j + w), j = 0 .. m - 1.
+ *   hit     position i in [0, L - w] is a hit on strand s when read[i .. i + w) has only ACGT letters and differs in at most one
+ *           place from some cyclic word of U_s.
+ *   block   block j holds the positions [j block, (j + 1) block) of [0, L - w]: nb = ceil((L - w + 1) / block) blocks, none
+ *           when L < w.  count_s[j] = its hits; it is FLAGGED when count_s[j] >= min_hits (a short last block: same threshold).
+ *   tract   on strand s, a maximal run of flagged blocks j_0 < ... < j_t with j_(i+1) - j_i <= gap + 1 (at most `gap` unflagged
+ *           blocks between neighbours); b = j_0, e = j_t + 1; kept when e - b >= min_blocks.  begin = b block,
+ *           end = min(e block + w - 1, L), blocks = e - b, hits = the sum of count_s over [b, e), inner gaps included.
+ *           Unflagged blocks at either side never belong to a tract.
+ *   found   int32[n_reads][2]: the true number of kept tracts of strand s.
+ *   tracts  tps_tract[n_reads][2][max_tracts]: the first max_tracts of them in order of begin, the rest of the row zero.
+ *   totals  uint32[n_reads][4]: hits of strand 0, of strand 1, flagged blocks of strand 0, of strand 1, over the whole read.
+ * Exact integers, identical from run to run.  TPS_E_ARG: m outside 4..32, a unit that is a power of a shorter word (or has codes
+ * behind its m letters), an array length that does not match the slot.  TPS_E_CAPACITY: block no multiple of 64 in 64..1024,
+ * min_hits outside 1..block, gap outside 0..64, min_blocks outside 1..64, max_tracts outside 1..16.  TPS_E_STATE: an empty slot.
+ * One launch; returns when the outputs are in place.  The slot's scan state (tails, results, sums, raw rows) is not touched. */
+typedef struct tps_tract {            /* 16 bytes */
+    int32_t begin, end;               /* bases [begin, end) of the read as stored */
+    int32_t hits, blocks;
+} tps_tract;
+int  tps_batch_tract_map(tps_ctx* ctx, int32_t slot, uint64_t unit, int32_t m, int32_t block, int32_t min_hits, int32_t gap,
+                         int32_t min_blocks, int32_t max_tracts, tps_tract* tracts, int64_t tracts_len, int32_t* found,
+                         int64_t found_len, uint32_t* totals, int64_t totals_len);
+
 /* ---- measurement ----------------------------------------------------------------------- */
 /* hipEvent timings of the scan kernel launches since the last reset: number of launches,
  * total and mean milliseconds (events are recorded on the stream the kernel runs on). */

@@ -1,0 +1,169 @@
+"""The tract map (tps_batch_tract_map; csrc/tps_tract.h) on the host emulation of its kernel: equal to the plain restatement of the
+rule (tests/tract_oracle.py) field for field on every case of tests/tract_cases.py, the stand-alone sanitizer run of the same kernel
+text on the same cases, the hit table the host builds against the oracle's word set, the library's refusals, tracts.classify, and
+the detection rates of the defaults on synthetic reads."""
+import subprocess
+
+import numpy as np
+import pytest
+
+import emu_tract_driver as emu
+import tract_cases as tc
+import tract_oracle
+from topsicle_amd import hiplib, synth, tracts, variants
+
+
+@pytest.mark.parametrize("name", tc.CASE_IDS)
+def test_emulation_equals_oracle(name):
+    c = tc.case(name)
+    got = emu.tract_map(c.reads, c.unit, base_shift=tc.CASE_IDS.index(name) & 3, **c.kw)
+    assert got[0].dtype == hiplib.TRACT_DTYPE and got[1].dtype == np.int32 and got[2].dtype == np.uint32
+    tc.assert_equal(got, name)
+
+
+def test_cases_reach_what_they_are_for():
+    """The edge cases say what they claim to say (on the oracle's answers)."""
+    for key, unit in tc.UNITS.items():
+        w = min(len(unit), 8)
+        t, found, totals = tc.expected(f"lengths_{key}")
+        lens = [len(r) for r in tc.case(f"lengths_{key}").reads]
+        assert lens[:4] == [0, w - 1, w, w + 1]
+        assert (found[:2] == 0).all() and (totals[:2] == 0).all()                       # nb = 0
+        assert (found[2:, 0] == 1).all()
+        assert [int(x) for x in t["end"][2:, 0, 0]] == lens[2:]                        # end == L, the last block short or not
+        assert [int(x) for x in t["blocks"][2:, 0, 0]] == [1, 1, 1, 1, 2, 2, 3]
+        assert [int(x) for x in totals[2:, 0]] == [n - w + 1 for n in lens[2:]]        # every position of a pure repeat hits
+    t, found, totals = tc.expected("threshold_CCCTAA")
+    assert found[:, 0].tolist() == [1, 1] and t["hits"][:, 0, 0].tolist() == [20, 20] and totals[:, 0].tolist() == [39, 39] and totals[:, 2].tolist() == [1, 1]
+    assert t["begin"][:, 0, 0].tolist() == [3 * 64, 64] and t["blocks"][:, 0, 0].tolist() == [1, 1]
+    # gaps: "00" + core + "000"; 101 is one tract of 3 blocks at gap >= 1, two of one block at gap 0 (dropped at min_blocks 2)
+    assert tc.expected("gaps_g1_b2")[0]["blocks"][0, 0, 0] == 3 and tc.expected("gaps_g1_b2")[0]["begin"][0, 0, 0] == 128
+    assert tc.expected("gaps_g0_b1")[1][0, 0] == 2 and tc.expected("gaps_g0_b2")[1][0, 0] == 0
+    assert tc.expected("gaps_g1_b1")[1][2, 0] == 2 and tc.expected("gaps_g2_b1")[1][2, 0] == 1          # 1001
+    assert tc.expected("gaps_g1_b3")[1][1, 1] == 1 and tc.expected("gaps_g1_b3")[1][1, 0] == 0          # the strand-1 copy of 101
+    assert tc.expected("gaps_g1_b3")[1][8].tolist() == [0, 0]                                           # 11 is shorter than 3 blocks
+    for block in (64, 128, 1024):
+        piece = emu.piece(block)
+        assert piece % block == 0 and piece + block > 4032 >= piece
+        t, found, _ = tc.expected(f"seam_block{block}_gap1")
+        assert found[-1].tolist() == [0, 1] and t["begin"][-1, 1, 0] < piece and t["end"][-1, 1, 0] > 2 * piece          # open across three pieces
+        assert piece in t["begin"][:, 0, 0].tolist() and piece + 7 - 2 in t["end"][:, 0, 0].tolist()       # a tract begins, one ends at the cut
+        assert found[-2].tolist() == [0, 0] and tc.expected(f"seam_block{block}_gap2")[1][-2].tolist() == [1, 0]
+    t, found, _ = tc.expected("strands")
+    assert found.tolist() == [[1, 1], [1, 1], [1, 1]] and t["end"][0, 1, 0] >= t["begin"][0, 0, 0] - 64
+    t, found, totals = tc.expected("selfrc")
+    assert np.array_equal(t[:, 0], t[:, 1]) and found[0, 0] == found[0, 1] == 2 and totals[0, 0] == totals[0, 1]
+    t, found, totals = tc.expected("letters_CCCTAA")
+    assert totals[0, 0] == 384 and totals[1, 0] == 384 - 6 and totals[7, 0] == 384 and totals[9].tolist() == [0, 0, 0, 0]
+    for mt in (8, 1, 16):
+        t, found, _ = tc.expected(f"overflow_{mt}")
+        s = 1 if mt == 1 else 0
+        assert found[0, s] == mt + 2 and found[1, s] == mt and (t["blocks"][:, s] == 2).all()
+        assert t["begin"][0, s].tolist() == [256 * i for i in range(mt)]
+    t, found, totals = tc.expected("ragged")
+    assert (found.sum(axis=1) > 0).sum() > 200 and found.max() >= 1 and (totals[[5, 100, 171]] == 0).all()
+    t, found, _ = tc.expected("long")
+    assert found[0].tolist() == [4, 4] and t["end"][0, 1, 3] == 200000
+    assert tc.expected("empty")[0].shape == (0, 2, 8)
+
+
+@pytest.fixture(scope="module")
+def cases_file(tmp_path_factory):
+    path = tmp_path_factory.mktemp("tract_cases") / "cases.txt"
+    with open(path, "w") as fh:
+        for c in tc.cases():
+            k = c.kw
+            fh.write(f"case {c.unit} {k['block']} {k['min_hits']} {k['gap']} {k['min_blocks']} {k['max_tracts']} {len(c.reads)}\n")
+            fh.write("".join((r or "-") + "\n" for r in c.reads))
+    return str(path)
+
+
+def test_standalone_program_is_clean_under_sanitizers(cases_file):
+    """The same kernel text under -fsanitize=address,undefined, as a program of its own, on the cases of this file: poisoned LDS of
+    exactly one wave's size, a table of exactly its size, garbage around the batch; every answer checked against the program's own
+    restatement of the rule.  Then its built-in batch."""
+    exe = emu.build_main()
+    for argv in ([exe, cases_file], [exe]):
+        out = subprocess.run(argv, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0 and out.stdout.startswith("ok "), out.stdout[-2000:] + out.stderr[-4000:]
+        assert "runtime error" not in out.stderr and "AddressSanitizer" not in out.stderr, out.stderr[-4000:]
+    assert out.stdout.startswith("ok 4 cases")
+
+
+@pytest.mark.parametrize("key", list(tc.UNITS))
+def test_hit_table_equals_the_oracles_word_set(key):
+    unit = tc.UNITS[key]
+    w = min(len(unit), 8)
+    tab = emu.hit_table(unit)
+    assert tab.shape == (4 ** w // 16,)
+    entries = (tab[:, None] >> (2 * np.arange(16, dtype=np.uint32))[None, :]).reshape(-1) & 3
+    for s, u in enumerate((unit, tract_oracle.revcomp(unit))):
+        got = {"".join("ACTG"[(int(c) >> (2 * q)) & 3] for q in range(w)) for c in np.nonzero(entries & (1 << s))[0]}
+        assert got == tract_oracle.word_set(u)
+
+
+@pytest.mark.parametrize("kw, code", [
+    (dict(code=variants.unit_code("CCT")[0], m=3), "rc=-3"), (dict(code=0, m=33), "rc=-3"), (dict(code=variants.unit_code("CCACCA")[0]), "rc=-3"),
+    (dict(code=variants.unit_code("CCCTAA")[0] | 1 << 12), "rc=-3"),
+    (dict(lens=(15, 2, 4)), "rc=-3"), (dict(lens=(16, 3, 4)), "rc=-3"), (dict(lens=(16, 2, 5)), "rc=-3"),
+    (dict(block=0), "rc=-5"), (dict(block=96), "rc=-5"), (dict(block=1088), "rc=-5"),
+    (dict(min_hits=0), "rc=-5"), (dict(min_hits=65), "rc=-5"), (dict(gap=-1), "rc=-5"), (dict(gap=65), "rc=-5"),
+    (dict(min_blocks=0), "rc=-5"), (dict(min_blocks=65), "rc=-5"), (dict(max_tracts=0, lens=(0, 2, 4)), "rc=-5"), (dict(max_tracts=17, lens=(34, 2, 4)), "rc=-5"),
+])
+def test_refusals_carry_the_librarys_codes(kw, code):
+    """TPS_E_ARG (-3) and TPS_E_CAPACITY (-5) as tps_batch_tract_map returns them (test_gpu_tract.py asks the library the same)."""
+    a = dict(code=variants.unit_code("CCCTAA")[0], m=6, block=64, min_hits=20, gap=1, min_blocks=2, max_tracts=8, lens=None)
+    emu.tract_map_code(["CCCTAA" * 20], **a)
+    a.update(kw)
+    with pytest.raises(hiplib.TopsicleHipError) as e:
+        emu.tract_map_code(["CCCTAA" * 20], **a)
+    assert code in str(e.value)
+
+
+def test_classify():
+    L, edge = 10000, 256
+    cl = tracts.classify
+    assert cl(L, [], [], edge) == "none"
+    assert cl(L, [(0, 900)], [], edge) == "terminal" and cl(L, [], [(9000, L)], edge) == "terminal"
+    assert cl(L, [(256, 900)], [], edge) == "terminal" and cl(L, [(257, 900)], [], edge) == "interstitial"           # edge at its exact limit
+    assert cl(L, [], [(9000, L - 256)], edge) == "terminal" and cl(L, [], [(9000, L - 257)], edge) == "interstitial"
+    assert cl(L, [(0, 900)], [(9000, L)], edge) == "both_ends"
+    assert cl(L, [(4000, 4500)], [], edge) == "interstitial" and cl(L, [], [(4000, 4500)], edge) == "interstitial"
+    assert cl(L, [(9000, L)], [], edge) == "interstitial" and cl(L, [], [(0, 900)], edge) == "interstitial"           # the wrong strand for that end
+    assert cl(L, [(4500, 5000)], [(4000, 4500)], edge) == "fusion" and cl(L, [(4756, 5000)], [(4000, 4500)], edge) == "fusion"
+    assert cl(L, [(4757, 5000)], [(4000, 4500)], edge) == "interstitial"
+    assert cl(L, [(4499, 5000)], [(4000, 4500)], edge) == "interstitial"                  # exact coordinates: an overlap is no fusion ...
+    assert cl(L, [(4480, 5000)], [(4000, 4549)], edge, slack=69) == "fusion"              # ... the map's block edges: up to block + w - 1
+    assert cl(L, [(4480, 5000)], [(4000, 4550)], edge, slack=69) == "interstitial"
+    assert cl(L, [(4000, 4500)], [(4500, 5000)], edge) == "interstitial"                  # C runs into G: tail to tail, not this class
+    # priority: fusion before both_ends before interstitial before terminal
+    assert cl(L, [(0, 900), (4500, 5000)], [(4000, 4500), (9000, L)], edge) == "fusion"
+    assert cl(L, [(0, 900), (4000, 4500)], [(9000, L)], edge) == "both_ends"
+    assert cl(L, [(0, 900), (4000, 4500)], [], edge) == "interstitial"
+    assert cl(300, [(0, 200)], [(0, 300)], edge) == "both_ends"                           # a short read: every tract is near both ends
+    assert tracts.TractSpec("ccctaaccctaa").unit == "CCCTAA" and tracts.TractSpec("CCCTAA", block=128).slack == 133
+    assert tracts.check("CCCTAA", 64, 20, 1, 2) is None and tracts.check("CCT", 64, 20, 1, 2) is not None
+
+
+DETECTION = [("CCCTAA", synth.ONT), ("CCCTAA", synth.HIFI), ("AAACCCT", synth.ONT), ("CTGTGGGGTCTGGGTG", synth.ONT), ("ACGGATGTCTAACTTCTTGGTGT", synth.ONT)]
+
+
+@pytest.mark.parametrize("motif, errors", DETECTION, ids=[f"{m}_{'ONT' if e is synth.ONT else 'HIFI'}" for m, e in DETECTION])
+def test_defaults_find_the_planted_tract(motif, errors):
+    """120 reads of 6000 bases, one planted tract of 300 .. 3000 bases each: with the defaults at least 90 % of the reads have exactly
+    one tract, on the planted strand, touching the planted end, its length within 2 block + 0.1 T of the planted T (indels move it);
+    no tract on the other strand in the whole set.  (The oracle alone: >= 119 of 120 and zero.)"""
+    bases, off, truth = synth.make_reads(120, 6000, motif, 7, errors, 300, 3000)
+    reads = synth.split_reads(bases, off)
+    t, found, _ = emu.tract_map(reads, motif)
+    block, good = 64, 0
+    for r, read in enumerate(reads):
+        T, s = int(truth["tract"][r]), int(bool(truth["reverse"][r]))
+        assert found[r, 1 - s] == 0
+        if found[r, s] != 1:
+            continue
+        b, e = int(t["begin"][r, s, 0]), int(t["end"][r, s, 0])
+        touches = e == len(read) if s else b == 0
+        good += touches and abs((e - b) - T) <= 2 * block + 0.1 * T
+    print(f"{motif}: {good} of {len(reads)}")
+    assert good >= 0.9 * len(reads)

@@ -42,14 +42,18 @@ class Job:
     batch = `--telophrase 4 5 6`: the batch is parsed, packed and uploaded ONCE and scanned once per k (the reference
     re-parses the input for every k, main.py:206-235)."""
 
-    def __init__(self, patterns, prm: hiplib.Params, want_sums=False, want_raw=False, raw_sink=None, variants=None):
+    def __init__(self, patterns, prm: hiplib.Params, want_sums=False, want_raw=False, raw_sink=None, variants=None, tracts=None):
         """raw_sink (with want_raw; rawnpz.RawNpzWriter): the raw rows of the reads the sink selects are written to its file by
         the worker that scanned the batch, device -> file, and the caller gets a `RawKept` in place of the rows.
         variants (variants.VariantSpec: unit, bin, n_bins, sink): the worker that scanned the batch runs the variant census of the
-        called tracts on it while it is still resident and hands (recs, results, counts, profile) to the spec's sink."""
+        called tracts on it while it is still resident and hands (recs, results, counts, profile) to the spec's sink.
+        tracts (tracts.TractSpec: unit, the rule's parameters, sink): the same worker maps the telomere-repeat tracts of EVERY read of
+        the batch, passing or not, and hands (recs, tracts, found, totals) to the spec's sink.  The map needs whole reads: a batch
+        in heads mode is refused.  One job of a batch carries it (the map does not depend on the pattern table)."""
         self.patterns, self.prm, self.want_sums, self.want_raw = list(patterns), prm, bool(want_sums), bool(want_raw)
         self.raw_sink = raw_sink if want_raw else None
         self.variants = variants
+        self.tracts = tracts
 
 
 class CensusJob:
@@ -127,6 +131,12 @@ def _census_variants(job, eng, slot, recs, res, slot_index=None):
     elif len(slot_index):
         counts[slot_index], profile = eng.variant_census(slot, spec.unit, tails[slot_index], begin[slot_index], end[slot_index], spec.bin, spec.n_bins)
     spec.sink(recs, res, counts, profile)
+
+
+def _map_tracts(job, eng, slot, recs):
+    """The tract map of the resident batch (Job.tracts), on the engine and slot that were scanned: every read, whole."""
+    spec = job.tracts
+    spec.sink(recs, *eng.tract_map(slot, spec.unit, **spec.kw()))
 
 
 def upload_batch(engine, recs, slot: int = 0):
@@ -288,6 +298,8 @@ def scan_jobs(engine, recs, jobs, slot: int = 0, seq=None):
     of the k passes overlap on the GPU (measured: 603 vs 785 us per 10 000 x 25 kb batch for k = 4, 5, 6).
     batch.SEQUENTIAL_TABLES scans them back to back on the one context instead (the A/B switch)."""
     if getattr(recs, "full_len", None) is not None:
+        if any(getattr(j, "tracts", None) is not None for j in jobs):
+            raise ValueError("Job.tracts needs whole reads: read the file with two_pass=\"off\"")
         return scan_jobs_heads(engine, recs, jobs, slot, seq)
     if jobs and all(isinstance(j, CensusJob) for j in jobs):
         return census_jobs(engine, recs, jobs, slot)
@@ -321,6 +333,8 @@ def scan_jobs(engine, recs, jobs, slot: int = 0, seq=None):
                 hiplib.resolve_ties(eng, slot, res, len(job.patterns), p.jump, p.min_size)
             if getattr(job, "variants", None) is not None:
                 _census_variants(job, eng, slot, recs, res)
+            if getattr(job, "tracts", None) is not None:
+                _map_tracts(job, eng, slot, recs)
             sums = raw = win_off = None
             if job.want_sums:
                 sums, win_off = eng.window_sums(slot)

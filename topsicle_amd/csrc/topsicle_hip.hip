@@ -23,6 +23,7 @@
 #include "tps_device.h"
 #include "tps_motif.h"
 #include "tps_variant.h"
+#include "tps_tract.h"
 #include "tps_pack.h"
 #include "tps_plan.h"
 #include "tps_wide.h"
@@ -110,6 +111,18 @@ __global__ void __launch_bounds__(NT * WPG) variant_census_kernel(VariantArgs a)
     const int64_t r = (int64_t)blockIdx.x * WPG + wave;
     if (r >= a.n_reads) return;
     variant_read(a, r, smem + wave * VARIANT_LDS_DW, (int)(blockIdx.x % VARIANT_PARTS));
+}
+// The tract map (tps_batch_tract_map; tract_read in csrc/tps_tract.h): the workgroup copies the call's hit table into LDS once, then
+// one wave per read.  Every wave takes part in the copy and the barrier before the waves behind the batch leave.
+__global__ void __launch_bounds__(NT * TRACT_WPG) tract_map_kernel(TractArgs a) {
+    __shared__ __attribute__((aligned(16))) uint32_t smem[TRACT_TABLE_DW + TRACT_WPG * TRACT_LDS_DW];
+    const int tab_dw = tract_table_dw(a.w);
+    for (int i = (int)threadIdx.x; i < tab_dw; i += NT * TRACT_WPG) smem[i] = a.table[i];
+    __syncthreads();
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t r = (int64_t)blockIdx.x * TRACT_WPG + wave;
+    if (r >= a.n_reads) return;
+    tract_read(a, r, smem + TRACT_TABLE_DW + wave * TRACT_LDS_DW, smem);
 }
 }  // namespace tps
 
@@ -371,6 +384,7 @@ struct tps_ctx {
     DevBuf motif_hits, motif_counts;  // outputs of tps_batch_motif_census
     DevBuf variant_in, variant_counts, variant_prof;      // tps_batch_variant_census: tails / begin / end, its outputs
     std::vector<unsigned long long> h_variant_prof;        // ... the partial profiles as downloaded
+    DevBuf tract_table, tract_out;    // tps_batch_tract_map: the call's hit table; tracts, found and totals behind one another
     DevBuf ascii, ascii_off;          // staging of tps_batch_upload: ASCII bases + offsets, packed on the device right after the copy
     DevBuf nib, nib_src;              // staging of tps_batch_upload_nib4: BAM base codes + where each read's are, expanded right after the copy
     std::set<void*> pinned;           // host buffers handed out by tps_host_alloc
@@ -1402,6 +1416,49 @@ int tps_batch_variant_census(tps_ctx* c, int32_t slot, uint64_t unit, int32_t m,
     if (profile)
         for (int p = 0; p < tps::VARIANT_PARTS; ++p)
             for (size_t i = 0; i < part_len; ++i) profile[i] += (int64_t)c->h_variant_prof[p * part_len + i];
+    return TPS_OK;
+}
+
+int tps_batch_tract_map(tps_ctx* c, int32_t slot, uint64_t unit, int32_t m, int32_t block, int32_t min_hits, int32_t gap, int32_t min_blocks,
+                        int32_t max_tracts, tps_tract* tracts, int64_t tracts_len, int32_t* found, int64_t found_len, uint32_t* totals, int64_t totals_len) {
+    int rc;
+    if ((rc = bind(c))) return rc;
+    Slot* sl = get_slot(c, slot);
+    if (!sl) return TPS_E_ARG;
+    if (sl->n < 0) return fail(TPS_E_STATE, "no batch uploaded in this slot");
+    const char* why = "";
+    if ((rc = tps::tract_check(unit, m, block, min_hits, gap, min_blocks, max_tracts, &why))) return fail(rc, "%s", why);
+    const int64_t n = sl->n;
+    if (tracts_len != n * 2 * max_tracts) return fail(TPS_E_ARG, "tracts must hold %lld records", (long long)(n * 2 * max_tracts));
+    if (found_len != n * 2) return fail(TPS_E_ARG, "found must hold %lld counters", (long long)(n * 2));
+    if (totals_len != n * 4) return fail(TPS_E_ARG, "totals must hold %lld counters", (long long)(n * 4));
+    if (n == 0) return TPS_OK;
+    if (!tracts || !found || !totals) return fail(TPS_E_ARG, "null tracts / found / totals");
+    // (the pattern table, the slot's tails, its scan outputs and its plan are not touched: a scan before and after the map gives the same results)
+    const int w = m < tps::TRACT_MAX_WORD ? m : tps::TRACT_MAX_WORD;
+    std::vector<uint32_t> table((size_t)tps::tract_table_dw(w));
+    tps::tract_hit_table(unit, m, table.data());
+    const size_t tab_bytes = table.size() * 4, tr_bytes = (size_t)n * 2 * max_tracts * sizeof(tps_tract), fo_bytes = (size_t)n * 2 * 4, to_bytes = (size_t)n * 4 * 4;
+    if ((rc = c->tract_table.ensure(tab_bytes))) return rc;
+    if ((rc = c->tract_out.ensure(tr_bytes + fo_bytes + to_bytes))) return rc;
+    HIP_TRY(hipMemcpyAsync(c->tract_table.p, table.data(), tab_bytes, hipMemcpyHostToDevice, c->stream));      // (pageable: the copy has left `table` when the call returns)
+    HIP_TRY(hipMemsetAsync(c->tract_out.p, 0, tr_bytes + fo_bytes + to_bytes, c->stream));
+    tps::TractArgs a{};
+    a.seq2 = (const uint32_t*)sl->seq2.p;
+    a.inv = (const uint16_t*)sl->inv.p;
+    a.desc = (const tps_read_desc*)sl->desc.p;
+    a.table = (const uint32_t*)c->tract_table.p;
+    a.tracts = (tps_tract*)c->tract_out.p;
+    a.found = (int32_t*)((char*)c->tract_out.p + tr_bytes);
+    a.totals = (uint32_t*)((char*)c->tract_out.p + tr_bytes + fo_bytes);
+    a.n_reads = n;
+    a.w = w; a.block = block; a.min_hits = min_hits; a.gap = gap; a.min_blocks = min_blocks; a.max_tracts = max_tracts;
+    hipLaunchKernelGGL(tps::tract_map_kernel, dim3((unsigned)((n + tps::TRACT_WPG - 1) / tps::TRACT_WPG)), dim3(tps::NT * tps::TRACT_WPG), 0, c->stream, a);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(tracts, a.tracts, tr_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(found, a.found, fo_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(totals, a.totals, to_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return TPS_OK;
 }
 

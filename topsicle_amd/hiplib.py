@@ -23,7 +23,7 @@ FOLLOW_MAX_FWD, FOLLOW_WIDE_MAX_FWD, FOLLOW_HIST_MAX = 15, 32, 8      # k-mers t
 EXPORTS = [
     "tps_abi_version", "tps_device_count", "tps_ctx_create", "tps_ctx_destroy", "tps_last_error",
     "tps_set_patterns", "tps_set_patterns_wide", "tps_batch_upload", "tps_batch_upload_packed", "tps_batch_upload_nib4", "tps_batch_share", "tps_host_alloc", "tps_host_free",
-    "tps_batch_download_packed", "tps_batch_kmer_followers", "tps_batch_kmer_followers_wide", "tps_batch_motif_census", "tps_batch_variant_census", "tps_batch_set_tails", "tps_batch_scan", "tps_sync",
+    "tps_batch_download_packed", "tps_batch_kmer_followers", "tps_batch_kmer_followers_wide", "tps_batch_motif_census", "tps_batch_variant_census", "tps_batch_tract_map", "tps_batch_set_tails", "tps_batch_scan", "tps_sync",
     "tps_batch_results", "tps_batch_window_offsets", "tps_batch_window_sums", "tps_batch_window_raw",
     "tps_batch_raw_to_fd", "tps_batch_trc_counts", "tps_trc_counts", "tps_window_counts", "tps_binseg_l2", "tps_binseg_l2_ties", "tps_batch_read_sums", "tps_window_count",
     "tps_kernel_time_ms", "tps_kernel_time_reset", "tps_device_info", "tps_batch_kernel_info", "tps_ctx_debug_option", "tps_debug_stamps_get",
@@ -59,6 +59,10 @@ MOTIF_HIT_DTYPE = np.dtype([("unit", "<u8"), ("period", "<i4"), ("support", "<i4
 assert MOTIF_HIT_DTYPE.itemsize == 32
 MOTIF_MAX_PERIOD, MOTIF_MAX_SPAN = 32, 4096      # tps_batch_motif_census: the longest period, the most bases of a read end
 VARIANT_MAX_UNIT, VARIANT_BIN_RANGE, VARIANT_MAX_BINS = 32, (64, 4064), 64      # tps_batch_variant_census: letters of the unit, bin width, bins
+TRACT_DTYPE = np.dtype([("begin", "<i4"), ("end", "<i4"), ("hits", "<i4"), ("blocks", "<i4")])             # struct tps_tract
+assert TRACT_DTYPE.itemsize == 16
+# tps_batch_tract_map: letters of the unit, block (a multiple of 64), gap, min_blocks, max_tracts; min_hits is 1..block
+TRACT_UNIT_RANGE, TRACT_BLOCK_RANGE, TRACT_GAP_RANGE, TRACT_MIN_BLOCKS_RANGE, TRACT_MAX_TRACTS_RANGE = (4, 32), (64, 1024), (0, 64), (1, 64), (1, 16)
 RES_TIE = 1            # TPS_RES_TIE: the exact tournament decided the change-point (candidates within float64 noise of each other)
 
 
@@ -103,6 +107,7 @@ def load_library(path: str | None = None) -> C.CDLL:
         "tps_batch_kmer_followers_wide": (C.c_int, [vp, i32, i32, i32, i32, i32, i32, vp, i64, vp, i64]),
         "tps_batch_motif_census": (C.c_int, [vp, i32, i32, i32, i32, i32, i32, vp, i64, vp, i64]),
         "tps_batch_variant_census": (C.c_int, [vp, i32, C.c_uint64, i32, vp, vp, vp, i64, i32, i32, vp, i64, vp, i64]),
+        "tps_batch_tract_map": (C.c_int, [vp, i32, C.c_uint64, i32, i32, i32, i32, i32, i32, vp, i64, vp, i64, vp, i64]),
         "tps_batch_set_tails": (C.c_int, [vp, i32, vp]),
         "tps_batch_scan": (C.c_int, [vp, i32, C.POINTER(Params)]),
         "tps_sync": (C.c_int, [vp]),
@@ -462,6 +467,23 @@ class HipScanner:
         self._check(self.lib.tps_batch_variant_census(self._h, slot, code, m, _ptr(tails), _ptr(begin), _ptr(end), len(tails), bin, n_bins,
                                                       _ptr(counts), counts.size, _ptr(profile), 0 if profile is None else profile.size))
         return counts, profile
+
+    def tract_map(self, slot: int, unit: str, block: int = 64, min_hits: int = 20, gap: int = 1, min_blocks: int = 2, max_tracts: int = 8):
+        """Where in the whole reads of the resident batch repeats of the primitive unit `unit` (a string of ACGT, 4 .. 32 letters)
+        lie, on either strand (tps_batch_tract_map, the rule is in include/topsicle_hip.h; classes and files: topsicle_amd.tracts):
+        (tracts TRACT_DTYPE[n, 2, max_tracts], found int32[n, 2], totals uint32[n, 4]).  Strand 0 is the unit as given, strand 1 its
+        reverse complement; found is the true number of tracts, of which tracts holds the first max_tracts.  No pattern table
+        needed; the slot's scan outputs stay as they are."""
+        from . import variants
+        code, m = variants.unit_code(unit)
+        n = self._n[slot]
+        mt = max_tracts if TRACT_MAX_TRACTS_RANGE[0] <= max_tracts <= TRACT_MAX_TRACTS_RANGE[1] else 1      # (a bad count is the library's to refuse)
+        tracts = np.zeros((n, 2, mt), dtype=TRACT_DTYPE)
+        found = np.zeros((n, 2), dtype=np.int32)
+        totals = np.zeros((n, 4), dtype=np.uint32)
+        self._check(self.lib.tps_batch_tract_map(self._h, slot, code, m, block, min_hits, gap, min_blocks, max_tracts,
+                                                 _ptr(tracts), n * 2 * max_tracts, _ptr(found), found.size, _ptr(totals), totals.size))
+        return tracts, found, totals
 
     def set_tails(self, slot: int, tails: np.ndarray):
         tails = np.ascontiguousarray(tails, dtype=np.uint8)

@@ -20,7 +20,7 @@ from collections import defaultdict
 
 import numpy as np
 
-from . import allsteps, batch, hiplib, motif, rawnpz, seqio, variants
+from . import allsteps, batch, hiplib, motif, rawnpz, seqio, tracts, variants
 
 version_number = "1.0.0"
 Topsicle_output_prefix = "Topsicle"
@@ -150,6 +150,10 @@ def process_file_multi(args, seq_loc, phrases, engines):
         window=args.windowSize, slide=slide, trimfirst=args.trimfirst, maxlen=args.maxlengthtelo,
         flags=hiplib.F_STEP1 | hiplib.F_WINDOWS | hiplib.F_BINSEG), want_sums, want_raw, raw_sink=sink, variants=None if col is None else col.spec)
         for (_k, pattern, slide), sink, col in zip(phrases, raw_npz, vcols)]
+    # --tracts: one collector for the whole run; the map runs once per batch, with the first k's job
+    tcol = getattr(args, "tract_collector", None)
+    if tcol is not None:
+        jobs[0].tracts = tcol.spec
 
     fmt = _formats(seq_loc)
     fasta_temp = os.path.join(args.outputDir, f"{file_name}_trc_over_{min_cutoff}.fasta")
@@ -230,6 +234,9 @@ def process_file_multi(args, seq_loc, phrases, engines):
     ok = False
     try:
         for pb, outs in pool.scan_file_jobs(seq_loc, jobs, shards=n_shards, shard_min_bytes=shard_min):
+            if tcol is not None:                                             # every read of the batch, passing or not
+                t_tracts, t_found, _t_totals = tcol.take(pb)
+                tcol.add_batch(seq_loc, file_name, lambda i: pb.read_id(int(i)), pb.desc["len"], t_tracts, t_found)
             for n, ((telo_phrase, pattern, sliding_val), (res, sums, raw, win_off)) in enumerate(zip(phrases, outs)):
                 idx = np.nonzero(res["pass"])[0]
                 vout = vcols[n].take(pb) if vcols[n] is not None else None
@@ -335,6 +342,13 @@ def analysis_run(args, engines=None, engine_factory=None, wait_plots=True):
         tprint(f"{k}: {v}")
     print("---------------------")
     tprint("Starting Topsicle analysis")
+    if getattr(args, "tracts", False):
+        # (before any file is read or written; the root of a motif that --pattern auto has yet to find is checked below)
+        root = "ACGT" if args.pattern.strip().lower() == "auto" else variants.primitive_root(args.pattern.upper())
+        why = tracts.check(root, args.tractblock, args.tractminhits, args.tractgap, args.tractminblocks, tracts.DEFAULT_MAX_TRACTS, args.tractedge)
+        if why is not None:
+            tprint(f"--tracts needs {why}")
+            sys.exit(2)
     if args.pattern.strip().lower() == "auto":
         # the motif comes from the reads (motif.py); from here on the run is the one `--pattern <that motif>` would have been
         if engines is None:
@@ -401,6 +415,22 @@ def analysis_run(args, engines=None, engine_factory=None, wait_plots=True):
         args.variant_collectors = [variants.Collector(unit, args.variantbin, args.variantbins, args.trimfirst, slide, args.maxlengthtelo)
                                    for _k, _pattern, slide in phrases]
 
+    args.tract_collector = None
+    if getattr(args, "tracts", False):
+        unit = variants.primitive_root(args.pattern.upper())
+        why = tracts.check(unit, args.tractblock, args.tractminhits, args.tractgap, args.tractminblocks, tracts.DEFAULT_MAX_TRACTS, args.tractedge)
+        if why is not None:
+            tprint(f"--tracts needs {why}")
+            sys.exit(2)
+        if unit != args.pattern.upper():
+            tprint(f"--tracts: {args.pattern} is a power of {unit}; the map looks for {unit}")
+        # the map needs whole reads on the device: no heads-only batches
+        if getattr(args, "twopass", None) == "on":
+            tprint("--tracts maps whole reads: --twopass on ignored")
+        tprint("--tracts: every file is scanned as whole reads (--twopass off)")
+        args.twopass = "off"
+        args.tract_collector = tracts.Collector(unit, args.tractblock, args.tractminhits, args.tractgap, args.tractminblocks, tracts.DEFAULT_MAX_TRACTS, args.tractedge)
+
     filenames = []
     if os.path.isdir(args.inputDir):
         for root, _dirs, files in os.walk(args.inputDir):
@@ -434,6 +464,15 @@ def analysis_run(args, engines=None, engine_factory=None, wait_plots=True):
         variants.write_profile_csv(f"{args.outputDir}/variant_profile_{telo_phrase}.csv", col.unit, col.profile, col.spec.bin)
         tprint(f"variant repeats (k = {telo_phrase}): {args.outputDir}/variants_{telo_phrase}.csv, {args.outputDir}/variant_profile_{telo_phrase}.csv")
         for line in variants.summary(col.unit, col.total, col.n_tracts):
+            tprint(line)
+
+    if args.tract_collector is not None:
+        tcol = args.tract_collector
+        tract_rows, read_rows = tcol.rows_in_order(filenames)
+        tracts.write_tracts_csv(f"{args.outputDir}/tracts.csv", tract_rows)
+        tracts.write_reads_csv(f"{args.outputDir}/tract_reads.csv", read_rows)
+        tprint(f"tract map: {args.outputDir}/tracts.csv, {args.outputDir}/tract_reads.csv")
+        for line in tracts.summary(tcol.unit, tcol.classes):
             tprint(line)
 
     t_sum = time.perf_counter()
@@ -583,6 +622,15 @@ def build_parser():
                              "the rest -- per read (variants_{k}.csv) and per distance from the boundary (variant_profile_{k}.csv)")
     parser.add_argument("--variantbin", metavar="INT", type=int, default=variants.DEFAULT_BIN, help="--variants: width of a profile bin in bases (64..4064)")
     parser.add_argument("--variantbins", metavar="INT", type=int, default=variants.DEFAULT_BINS, help="--variants: bins of the profile, the last takes everything beyond (1..64)")
+    parser.add_argument("--tracts", action="store_true",
+                        help="MI355X build: map the telomere-repeat tracts of every WHOLE read, on both strands -- one row per tract (tracts.csv) and one per "
+                             "read with a tract and its class: fusion, both_ends, interstitial, terminal (tract_reads.csv).  Runs the files as --twopass off")
+    parser.add_argument("--tractblock", metavar="INT", type=int, default=tracts.DEFAULT_BLOCK, help="--tracts: positions per block (a multiple of 64 in 64..1024)")
+    parser.add_argument("--tractminhits", metavar="INT", type=int, default=tracts.DEFAULT_MIN_HITS, help="--tracts: hits that flag a block (1..tractblock)")
+    parser.add_argument("--tractgap", metavar="INT", type=int, default=tracts.DEFAULT_GAP, help="--tracts: unflagged blocks a tract may bridge (0..64)")
+    parser.add_argument("--tractminblocks", metavar="INT", type=int, default=tracts.DEFAULT_MIN_BLOCKS, help="--tracts: blocks a tract spans at least (1..64)")
+    parser.add_argument("--tractedge", metavar="INT", type=int, default=tracts.DEFAULT_EDGE,
+                        help="--tracts: a tract within this many bases of the read's end counts as terminal; the widest gap between the two tracts of a fusion")
     parser.add_argument("--twopass", choices=["auto", "on", "off"], default=None,
                         help="MI355X build: upload only the two 1000-base ends of every read for the TRC filter and the scanned part of the "
                              "reads that pass afterwards (auto, the default unless $TOPSICLE_TWO_PASS says otherwise: while few reads of a batch pass, "
