@@ -351,6 +351,42 @@ int  tps_batch_tract_map(tps_ctx* ctx, int32_t slot, uint64_t unit, int32_t m, i
                          int32_t min_blocks, int32_t max_tracts, tps_tract* tracts, int64_t tracts_len, int32_t* found,
                          int64_t found_len, uint32_t* totals, int64_t totals_len);
 
+/* ---- end groups (which chromosome end a telomeric read came from) --------------------------- */
+/* A sketch of the subtelomere behind the called boundary of every read of the resident batch, and the links between sketches
+ * that share enough of it; no pattern table (the reference has nothing comparable).  `unit`, m: a primitive word of 4 <= m <= 32
+ * letters, spelled as tps_batch_tract_map takes it.  For read r, h = the upper-cased read (tails[r] = 0) or its reverse
+ * complement (tails[r] = 1) -- "telomere first", as in tps_batch_variant_census -- and end[r] is clamped to L.
+ *   word    w = min(m, 8).  h[p .. p + w) is a REPEAT WORD when it has only ACGT letters and differs in at most one place from a
+ *           cyclic word of the unit or of its reverse complement (a hit on either strand of the tract map's rule).
+ *   kept    the k-mer at i in [begin, end - k] is KEPT when its k letters are all ACGT and none of its k - w + 1 words
+ *           h[i + d .. i + d + w), d = 0 .. k - w, is a repeat word: telomere k-mers, and their one-error variants, are the
+ *           same in every read and say nothing about the end.
+ *   hash    c = sum of code(h[i + q]) << 2q over q < k (A C T G = 0 1 2 3) as a uint32; x = fmix32(c ^ 0x9E3779B9), fmix32 =
+ *           MurmurHash3's 32-bit finaliser (x ^= x >> 16; x *= 0x85EBCA6B; x ^= x >> 13; x *= 0xC2B2AE35; x ^= x >> 16, modulo
+ *           2^32); bucket = x >> (32 - log2 buckets).
+ *   sketch  uint32[n_reads][buckets]: the smallest hash of each bucket, 0xFFFFFFFF for an empty one (a hash that equals
+ *           0xFFFFFFFF counts as empty).  A read with end - begin < k has an empty row.
+ *   kept    uint32[n_reads]: the number of kept k-mers.
+ * Exact, identical from run to run (a minimum does not depend on order).  TPS_E_ARG: m outside 4..32, a unit that is a power of
+ * a shorter word (or has codes behind its m letters), buckets not 64 / 128 / 256 / 512, a negative begin / end, begin > end, a
+ * tail other than 0 / 1, n_reads or an array length that does not match the slot.  TPS_E_CAPACITY: k outside 8..16,
+ * end - begin > 16384.  TPS_E_STATE: an empty slot.  One launch; returns when the outputs are in place.  The slot's scan state
+ * (tails, results, sums, raw rows) is not touched. */
+int  tps_batch_end_sketch(tps_ctx* ctx, int32_t slot, uint64_t unit, int32_t m, int32_t k, int32_t buckets, const uint8_t* tails,
+                          const int32_t* begin, const int32_t* end, int64_t n_reads, uint32_t* sketch, int64_t sketch_len,
+                          uint32_t* kept, int64_t kept_len);
+/* All pairs of n sketches (rows of `sketch`, uint32[n][buckets], from the host; no resident batch needed).  match(i, j) = the
+ * number of buckets b with s_i[b] == s_j[b], both not 0xFFFFFFFF.  For every row i:
+ *   degree  int32[n]: the true number of j > i with match(i, j) >= min_match.
+ *   links   int32[n][max_links]: the smallest such j in ascending order, the rest of the row -1.
+ *   matches int32[n][max_links]: match(i, j) beside each link, the rest of the row 0.
+ * Exact, identical from run to run.  TPS_E_ARG: buckets not 64 / 128 / 256 / 512, an array length that does not match n.
+ * TPS_E_CAPACITY: n over 262144, min_match outside 1..buckets, max_links outside 1..256.  One launch; returns when the outputs
+ * are in place. */
+int  tps_sketch_links(tps_ctx* ctx, const uint32_t* sketch, int64_t n, int32_t buckets, int64_t sketch_len, int32_t min_match,
+                      int32_t max_links, int32_t* degree, int64_t degree_len, int32_t* links, int64_t links_len, int32_t* matches,
+                      int64_t matches_len);
+
 /* ---- measurement ----------------------------------------------------------------------- */
 /* hipEvent timings of the scan kernel launches since the last reset: number of launches,
  * total and mean milliseconds (events are recorded on the stream the kernel runs on). */

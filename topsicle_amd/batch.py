@@ -42,18 +42,21 @@ class Job:
     batch = `--telophrase 4 5 6`: the batch is parsed, packed and uploaded ONCE and scanned once per k (the reference
     re-parses the input for every k, main.py:206-235)."""
 
-    def __init__(self, patterns, prm: hiplib.Params, want_sums=False, want_raw=False, raw_sink=None, variants=None, tracts=None):
+    def __init__(self, patterns, prm: hiplib.Params, want_sums=False, want_raw=False, raw_sink=None, variants=None, tracts=None, ends=None):
         """raw_sink (with want_raw; rawnpz.RawNpzWriter): the raw rows of the reads the sink selects are written to its file by
         the worker that scanned the batch, device -> file, and the caller gets a `RawKept` in place of the rows.
         variants (variants.VariantSpec: unit, bin, n_bins, sink): the worker that scanned the batch runs the variant census of the
         called tracts on it while it is still resident and hands (recs, results, counts, profile) to the spec's sink.
         tracts (tracts.TractSpec: unit, the rule's parameters, sink): the same worker maps the telomere-repeat tracts of EVERY read of
         the batch, passing or not, and hands (recs, tracts, found, totals) to the spec's sink.  The map needs whole reads: a batch
-        in heads mode is refused.  One job of a batch carries it (the map does not depend on the pattern table)."""
+        in heads mode is refused.  One job of a batch carries it (the map does not depend on the pattern table).
+        ends (ends.EndSpec: unit, k, buckets, span, sink): the worker that scanned the batch sketches the subtelomere window behind every
+        called boundary while the batch is still resident and hands (recs, results, sketch, kept) to the spec's sink."""
         self.patterns, self.prm, self.want_sums, self.want_raw = list(patterns), prm, bool(want_sums), bool(want_raw)
         self.raw_sink = raw_sink if want_raw else None
         self.variants = variants
         self.tracts = tracts
+        self.ends = ends
 
 
 class CensusJob:
@@ -131,6 +134,24 @@ def _census_variants(job, eng, slot, recs, res, slot_index=None):
     elif len(slot_index):
         counts[slot_index], profile = eng.variant_census(slot, spec.unit, tails[slot_index], begin[slot_index], end[slot_index], spec.bin, spec.n_bins)
     spec.sink(recs, res, counts, profile)
+
+
+def _sketch_ends(job, eng, slot, recs, res, slot_index=None):
+    """The end sketch of the windows behind the boundaries the scan has just called (Job.ends), on the engine and slot that were
+    scanned: [boundary, min(boundary + span, maxlen)) of the telomere-first string where the CLI would store the boundary
+    (ends.windows), begin = end = 0 -- an empty sketch -- for every other read.  `slot_index` as in _census_variants."""
+    from . import ends
+    spec = job.ends
+    begin, end = ends.windows(res, int(job.prm.trimfirst), int(job.prm.slide), int(job.prm.maxlen), spec.span)
+    tails = np.where(end > begin, res["tail"], 0).astype(np.uint8)
+    sketch = np.full((len(res), spec.buckets), ends.EMPTY, np.uint32)
+    kept = np.zeros(len(res), np.uint32)
+    if slot_index is None:
+        if eng is not None:
+            sketch, kept = eng.end_sketch(slot, spec.unit, tails, begin, end, spec.k, spec.buckets)
+    elif len(slot_index):
+        sketch[slot_index], kept[slot_index] = eng.end_sketch(slot, spec.unit, tails[slot_index], begin[slot_index], end[slot_index], spec.k, spec.buckets)
+    spec.sink(recs, res, sketch, kept)
 
 
 def _map_tracts(job, eng, slot, recs):
@@ -248,6 +269,8 @@ def scan_jobs_heads(engine, recs, jobs, slot: int = 0, seq=None):
                     res[f][idx] = rb[f]
                 if getattr(job, "variants", None) is not None:
                     _census_variants(job, eng, slot_b, recs, res, slot_index=idx)
+                if getattr(job, "ends", None) is not None:
+                    _sketch_ends(job, eng, slot_b, recs, res, slot_index=idx)
                 np.cumsum(np.where(passing, res["n_win"], 0), out=win_off[1:])
                 if job.want_sums:
                     sums, wo_b = eng.window_sums(slot_b)
@@ -260,6 +283,8 @@ def scan_jobs_heads(engine, recs, jobs, slot: int = 0, seq=None):
             else:
                 if getattr(job, "variants", None) is not None:
                     _census_variants(job, None, slot_b, recs, res)             # (no read passed: an all-zero answer)
+                if getattr(job, "ends", None) is not None:
+                    _sketch_ends(job, None, slot_b, recs, res)
                 if job.want_sums:
                     sums = np.zeros(0, np.int32)
                 if job.want_raw and job.raw_sink is not None and seq is not None:
@@ -333,6 +358,8 @@ def scan_jobs(engine, recs, jobs, slot: int = 0, seq=None):
                 hiplib.resolve_ties(eng, slot, res, len(job.patterns), p.jump, p.min_size)
             if getattr(job, "variants", None) is not None:
                 _census_variants(job, eng, slot, recs, res)
+            if getattr(job, "ends", None) is not None:
+                _sketch_ends(job, eng, slot, recs, res)
             if getattr(job, "tracts", None) is not None:
                 _map_tracts(job, eng, slot, recs)
             sums = raw = win_off = None

@@ -24,6 +24,7 @@
 #include "tps_motif.h"
 #include "tps_variant.h"
 #include "tps_tract.h"
+#include "tps_ends.h"
 #include "tps_pack.h"
 #include "tps_plan.h"
 #include "tps_wide.h"
@@ -123,6 +124,26 @@ __global__ void __launch_bounds__(NT * TRACT_WPG) tract_map_kernel(TractArgs a) 
     const int64_t r = (int64_t)blockIdx.x * TRACT_WPG + wave;
     if (r >= a.n_reads) return;
     tract_read(a, r, smem + TRACT_TABLE_DW + wave * TRACT_LDS_DW, smem);
+}
+// The end sketch (tps_batch_end_sketch; end_sketch_read in csrc/tps_ends.h): the tract map's hit table in LDS, shared by the
+// workgroup's waves as there, then one wave per read.
+__global__ void __launch_bounds__(NT * ENDS_WPG) end_sketch_kernel(EndSketchArgs a) {
+    __shared__ __attribute__((aligned(16))) uint32_t smem[TRACT_TABLE_DW + ENDS_WPG * ENDS_LDS_DW];
+    const int tab_dw = tract_table_dw(a.w);
+    for (int i = (int)threadIdx.x; i < tab_dw; i += NT * ENDS_WPG) smem[i] = a.table[i];
+    __syncthreads();
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t r = (int64_t)blockIdx.x * ENDS_WPG + wave;
+    if (r >= a.n_reads) return;
+    end_sketch_read(a, r, smem + TRACT_TABLE_DW + wave * ENDS_LDS_DW, smem);
+}
+// The links between sketches (tps_sketch_links; sketch_links_row in csrc/tps_ends.h): one wave per row.
+__global__ void __launch_bounds__(NT * LINKS_WPG) sketch_links_kernel(LinkArgs a) {
+    __shared__ __attribute__((aligned(16))) uint32_t smem[LINKS_WPG * LINKS_LDS_DW];
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t i = (int64_t)blockIdx.x * LINKS_WPG + wave;
+    if (i >= a.n) return;
+    sketch_links_row(a, i, smem + wave * LINKS_LDS_DW);
 }
 }  // namespace tps
 
@@ -385,6 +406,8 @@ struct tps_ctx {
     DevBuf variant_in, variant_counts, variant_prof;      // tps_batch_variant_census: tails / begin / end, its outputs
     std::vector<unsigned long long> h_variant_prof;        // ... the partial profiles as downloaded
     DevBuf tract_table, tract_out;    // tps_batch_tract_map: the call's hit table; tracts, found and totals behind one another
+    DevBuf ends_in, ends_out;         // tps_batch_end_sketch: tails / begin / end; sketch and kept behind one another (its table is tract_table)
+    DevBuf links_t, links_out;        // tps_sketch_links: the sketches bucket-major; degree, links and matches behind one another
     DevBuf ascii, ascii_off;          // staging of tps_batch_upload: ASCII bases + offsets, packed on the device right after the copy
     DevBuf nib, nib_src;              // staging of tps_batch_upload_nib4: BAM base codes + where each read's are, expanded right after the copy
     std::set<void*> pinned;           // host buffers handed out by tps_host_alloc
@@ -1458,6 +1481,88 @@ int tps_batch_tract_map(tps_ctx* c, int32_t slot, uint64_t unit, int32_t m, int3
     HIP_TRY(hipMemcpyAsync(tracts, a.tracts, tr_bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(found, a.found, fo_bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(totals, a.totals, to_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return TPS_OK;
+}
+
+int tps_batch_end_sketch(tps_ctx* c, int32_t slot, uint64_t unit, int32_t m, int32_t k, int32_t buckets, const uint8_t* tails, const int32_t* begin,
+                         const int32_t* end, int64_t n_reads, uint32_t* sketch, int64_t sketch_len, uint32_t* kept, int64_t kept_len) {
+    int rc;
+    if ((rc = bind(c))) return rc;
+    Slot* sl = get_slot(c, slot);
+    if (!sl) return TPS_E_ARG;
+    if (sl->n < 0) return fail(TPS_E_STATE, "no batch uploaded in this slot");
+    const char* why = "";
+    if ((rc = tps::ends_check(unit, m, k, buckets, &why))) return fail(rc, "%s", why);
+    const int64_t n = sl->n;
+    if (n_reads != n) return fail(TPS_E_ARG, "tails, begin and end must hold %lld reads", (long long)n);
+    if (sketch_len != n * buckets) return fail(TPS_E_ARG, "sketch must hold %lld hashes", (long long)(n * buckets));
+    if (kept_len != n) return fail(TPS_E_ARG, "kept must hold %lld counters", (long long)n);
+    if (n == 0) return TPS_OK;
+    if (!tails || !begin || !end || !sketch || !kept) return fail(TPS_E_ARG, "null tails / begin / end / sketch / kept");
+    int64_t at = 0;
+    if ((rc = tps::ends_check_reads(tails, begin, end, n, &why, &at))) return fail(rc, "read %lld: %s", (long long)at, why);
+    // (the pattern table, the slot's tails, its scan outputs and its plan are not touched: a scan before and after the sketch gives the same results)
+    const int w = m < tps::TRACT_MAX_WORD ? m : tps::TRACT_MAX_WORD;
+    std::vector<uint32_t> table((size_t)tps::tract_table_dw(w));
+    tps::tract_hit_table(unit, m, table.data());
+    const size_t tab_bytes = table.size() * 4, sk_bytes = (size_t)n * buckets * 4, kp_bytes = (size_t)n * 4;
+    const size_t off_begin = (((size_t)n + 15) & ~(size_t)15), off_end = off_begin + (size_t)n * 4;
+    if ((rc = c->tract_table.ensure(tab_bytes))) return rc;
+    if ((rc = c->ends_in.ensure(off_end + (size_t)n * 4))) return rc;
+    if ((rc = c->ends_out.ensure(sk_bytes + kp_bytes))) return rc;
+    HIP_TRY(hipMemcpyAsync(c->tract_table.p, table.data(), tab_bytes, hipMemcpyHostToDevice, c->stream));      // (pageable: the copy has left `table` when the call returns)
+    HIP_TRY(hipMemcpyAsync(c->ends_in.p, tails, (size_t)n, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync((char*)c->ends_in.p + off_begin, begin, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync((char*)c->ends_in.p + off_end, end, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    tps::EndSketchArgs a{};
+    a.seq2 = (const uint32_t*)sl->seq2.p;
+    a.inv = (const uint16_t*)sl->inv.p;
+    a.desc = (const tps_read_desc*)sl->desc.p;
+    a.table = (const uint32_t*)c->tract_table.p;
+    a.tails = (const uint8_t*)c->ends_in.p;
+    a.begin = (const int32_t*)((const char*)c->ends_in.p + off_begin);
+    a.end = (const int32_t*)((const char*)c->ends_in.p + off_end);
+    a.sketch = (uint32_t*)c->ends_out.p;
+    a.kept = (uint32_t*)((char*)c->ends_out.p + sk_bytes);
+    a.n_reads = n;
+    a.w = w; a.k = k; a.buckets = buckets; a.shift = 32 - tps::ends_log2(buckets);
+    hipLaunchKernelGGL(tps::end_sketch_kernel, dim3((unsigned)((n + tps::ENDS_WPG - 1) / tps::ENDS_WPG)), dim3(tps::NT * tps::ENDS_WPG), 0, c->stream, a);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(sketch, a.sketch, sk_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(kept, a.kept, kp_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return TPS_OK;
+}
+
+int tps_sketch_links(tps_ctx* c, const uint32_t* sketch, int64_t n, int32_t buckets, int64_t sketch_len, int32_t min_match, int32_t max_links,
+                     int32_t* degree, int64_t degree_len, int32_t* links, int64_t links_len, int32_t* matches, int64_t matches_len) {
+    int rc;
+    if ((rc = bind(c))) return rc;
+    const char* why = "";
+    if ((rc = tps::links_check(n, buckets, sketch_len, min_match, max_links, degree_len, links_len, matches_len, &why))) return fail(rc, "%s", why);
+    if (n == 0) return TPS_OK;
+    if (!sketch || !degree || !links || !matches) return fail(TPS_E_ARG, "null sketch / degree / links / matches");
+    std::vector<uint32_t> t((size_t)n * buckets);
+    tps::links_transpose(sketch, n, buckets, t.data());
+    const size_t t_bytes = t.size() * 4, dg_bytes = (size_t)n * 4, ln_bytes = (size_t)n * max_links * 4;
+    if ((rc = c->links_t.ensure(t_bytes))) return rc;
+    if ((rc = c->links_out.ensure(dg_bytes + 2 * ln_bytes))) return rc;
+    HIP_TRY(hipMemcpyAsync(c->links_t.p, t.data(), t_bytes, hipMemcpyHostToDevice, c->stream));      // (pageable: the copy has left `t` when the call returns)
+    tps::LinkArgs a{};
+    a.t = (const uint32_t*)c->links_t.p;
+    a.degree = (int32_t*)c->links_out.p;
+    a.links = (int32_t*)((char*)c->links_out.p + dg_bytes);
+    a.matches = (int32_t*)((char*)c->links_out.p + dg_bytes + ln_bytes);
+    a.n = n;
+    a.buckets = buckets; a.min_match = min_match; a.max_links = max_links;
+    HIP_TRY(hipMemsetAsync(a.links, 0xFF, ln_bytes, c->stream));               // -1: no link
+    HIP_TRY(hipMemsetAsync(a.matches, 0, ln_bytes, c->stream));
+    hipLaunchKernelGGL(tps::sketch_links_kernel, dim3((unsigned)((n + tps::LINKS_WPG - 1) / tps::LINKS_WPG)), dim3(tps::NT * tps::LINKS_WPG), 0, c->stream, a);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(degree, a.degree, dg_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(links, a.links, ln_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(matches, a.matches, ln_bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return TPS_OK;
 }

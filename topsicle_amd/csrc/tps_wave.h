@@ -260,6 +260,7 @@ TPS_DEV void lds_or(uint32_t* p, uint32_t v) { *p |= v; }
 TPS_DEV uint32_t lds_add_ret(uint32_t* p, uint32_t v) { uint32_t o = *p; *p += v; return o; }
 TPS_DEV void lds_max_u64(uint64_t* p, uint64_t v) { if (v > *p) *p = v; }
 TPS_DEV void lds_max_i32(int32_t* p, int32_t v) { if (v > *p) *p = v; }
+TPS_DEV void lds_min_u32(uint32_t* p, uint32_t v) { if (v < *p) *p = v; }
 TPS_DEV void hist_add(unsigned long long* p) { *p += 1ull; }
 TPS_DEV void hist_add_n(unsigned long long* p, uint32_t v) { *p += v; }
 struct u32x4 { uint32_t x, y, z, w; };
@@ -288,6 +289,7 @@ TPS_DEV void lds_or(uint32_t* p, uint32_t v) { atomicOr(p, v); }
 TPS_DEV uint32_t lds_add_ret(uint32_t* p, uint32_t v) { return atomicAdd(p, v); }
 TPS_DEV void lds_max_u64(uint64_t* p, uint64_t v) { atomicMax((unsigned long long*)p, (unsigned long long)v); }
 TPS_DEV void lds_max_i32(int32_t* p, int32_t v) { atomicMax(p, v); }
+TPS_DEV void lds_min_u32(uint32_t* p, uint32_t v) { atomicMin(p, v); }
 TPS_DEV void hist_add(unsigned long long* p) { atomicAdd(p, 1ull); }
 TPS_DEV void hist_add_n(unsigned long long* p, uint32_t v) { atomicAdd(p, (unsigned long long)v); }
 typedef uint4 u32x4;

@@ -1,0 +1,200 @@
+"""Telomeric reads grouped by chromosome end (`--ends`; HipScanner.end_sketch, HipScanner.sketch_links).
+
+The subtelomere just behind a read's called boundary is the only part of a telomeric read that says which end it came from: reads
+of one end share it, reads of different ends mostly do not.  Per read with a stored boundary the batch worker sketches the window
+[boundary, min(boundary + span, maxlengthtelo)) of the telomere-first string while the batch is resident -- the smallest hash per
+bucket over the k-mers that hold no word of the telomere repeat (tps_batch_end_sketch) -- and after the last file ONE call compares
+all sketches with each other (tps_sketch_links).  This module holds what the host adds: the windows, the collector, the groups
+(connected components of the links, by union-find), the two CSV files and the summary for the log.
+
+What comes out are GROUPS OF READS, numbered by size -- not chromosome names: no reference is read.  The defaults rest on synthetic,
+independent subtelomeres (README, "End groups").
+"""
+from __future__ import annotations
+
+import csv
+import threading
+
+import numpy as np
+
+from . import variants
+
+DEFAULT_SPAN, DEFAULT_K, DEFAULT_BUCKETS, DEFAULT_MIN_MATCH, DEFAULT_MIN_KMERS, DEFAULT_MIN_READS = 2000, 12, 256, 6, 200, 3
+DEFAULT_MAX_LINKS = 64            # links kept per sketch (the smallest partners); rows with more are counted in the log
+UNIT_RANGE, K_RANGE, BUCKETS, MAX_WINDOW, MAX_SKETCHES, MAX_LINKS = (4, 32), (8, 16), (64, 128, 256, 512), 16384, 262144, 256
+EMPTY = 0xFFFFFFFF
+
+
+def check(unit: str, span: int = DEFAULT_SPAN, k: int = DEFAULT_K, buckets: int = DEFAULT_BUCKETS, min_match: int = DEFAULT_MIN_MATCH,
+          min_kmers: int = DEFAULT_MIN_KMERS, min_reads: int = DEFAULT_MIN_READS):
+    """None, or what is wrong with the unit (a primitive root) or a value, in words for the command line."""
+    if not (UNIT_RANGE[0] <= len(unit) <= UNIT_RANGE[1]) or any(c not in "ACGT" for c in unit.upper()):
+        return f"a motif of ACGT whose primitive root has {UNIT_RANGE[0]}..{UNIT_RANGE[1]} letters, not {unit!r}"
+    if not (K_RANGE[0] <= k <= K_RANGE[1]):
+        return f"--endk {K_RANGE[0]}..{K_RANGE[1]}"
+    if buckets not in BUCKETS:
+        return "--endbuckets 64, 128, 256 or 512"
+    if not (k <= span <= MAX_WINDOW):
+        return f"--endspan --endk..{MAX_WINDOW}"
+    if not (1 <= min_match <= buckets):
+        return "--endminmatch 1..--endbuckets"
+    if min_kmers < 1 or min_reads < 1:
+        return "--endminkmers and --endminreads of at least 1"
+    return None
+
+
+class EndSpec:
+    """What batch.Job(ends=...) carries: the primitive unit, k, the buckets, the window's span, and `sink(recs, res, sketch, kept)`,
+    called by the worker that scanned a batch while that batch is still resident."""
+
+    def __init__(self, unit: str, k: int = DEFAULT_K, buckets: int = DEFAULT_BUCKETS, span: int = DEFAULT_SPAN, sink=None):
+        self.unit, self.k, self.buckets, self.span, self.sink = variants.primitive_root(unit.upper()), int(k), int(buckets), int(span), sink
+
+
+def windows(res, trimfirst: int, slide: int, maxlen: int, span: int):
+    """(begin, end) int32 arrays for a batch's results: the window [boundary, min(boundary + span, maxlen)) of every read whose
+    boundary the CLI would store (variants.tract_bounds), begin = end = 0 for every other read.  The clamp to maxlen is what makes
+    one pass and two passes agree: the second pass holds only the first / last min(L, maxlen) bases of a read."""
+    _, boundary = variants.tract_bounds(res, trimfirst, slide, maxlen)
+    ok = boundary > 0
+    b64 = boundary.astype(np.int64)
+    begin = np.where(ok, b64, 0).astype(np.int32)
+    end = np.where(ok, np.minimum(b64 + span, maxlen), 0).astype(np.int32)
+    return begin, end
+
+
+class UnionFind:
+    def __init__(self, n: int):
+        self.parent = list(range(n))
+
+    def find(self, x: int) -> int:
+        p = self.parent
+        while p[x] != x:
+            p[x] = p[p[x]]
+            x = p[x]
+        return x
+
+    def union(self, a: int, b: int):
+        ra, rb = self.find(a), self.find(b)
+        if ra != rb:
+            self.parent[max(ra, rb)] = min(ra, rb)         # the root is the component's first member
+
+
+def group(n: int, links, min_reads: int = DEFAULT_MIN_READS):
+    """end int32[n] from the links of sketch_links (row i: its partners j > i, -1 behind them): connected components, numbered
+    1, 2, ... by size, largest first, ties to the component whose first member comes first; 0 = in a component of fewer than
+    min_reads members."""
+    uf = UnionFind(n)
+    ii, pp = np.nonzero(np.asarray(links) >= 0)
+    for i, j in zip(ii.tolist(), np.asarray(links)[ii, pp].tolist()):
+        uf.union(i, j)
+    roots = np.array([uf.find(i) for i in range(n)], np.int64)
+    end = np.zeros(n, np.int32)
+    if n == 0:
+        return end
+    first, size = np.unique(roots, return_counts=True)     # (a root is its component's first member)
+    order = sorted((int(-s), int(f)) for f, s in zip(first, size) if s >= min_reads)
+    for g, (_s, f) in enumerate(order):
+        end[roots == f] = g + 1
+    return end
+
+
+def edge_stats(n: int, links, matches):
+    """(edges at each row, both directions; its best match) from the links as stored."""
+    links, matches = np.asarray(links), np.asarray(matches)
+    n_edges = np.zeros(n, np.int64)
+    best = np.zeros(n, np.int64)
+    ii, pp = np.nonzero(links >= 0)
+    jj, mm = links[ii, pp], matches[ii, pp]
+    np.add.at(n_edges, ii, 1)
+    np.add.at(n_edges, jj, 1)
+    np.maximum.at(best, ii, mm)
+    np.maximum.at(best, jj, mm)
+    return n_edges, best
+
+
+class Collector:
+    """The sink of one k of a run, modelled on variants.Collector.  The workers hand it every batch's sketches (in whatever order
+    they finish); the rows wait until the run's consumer, which sees the batches in file order, asks for them with take(recs) and
+    hands back the rows of the reads with a stored boundary.  finish() links and groups the whole run."""
+
+    def __init__(self, unit: str, k: int = DEFAULT_K, buckets: int = DEFAULT_BUCKETS, span: int = DEFAULT_SPAN, min_match: int = DEFAULT_MIN_MATCH,
+                 min_kmers: int = DEFAULT_MIN_KMERS, min_reads: int = DEFAULT_MIN_READS, trimfirst: int = 100, slide: int = 6, maxlen: int = 20000,
+                 max_links: int = DEFAULT_MAX_LINKS):
+        self.spec = EndSpec(unit, k, buckets, span, self)
+        self.unit = self.spec.unit
+        self.min_match, self.min_kmers, self.min_reads, self.max_links = int(min_match), int(min_kmers), int(min_reads), int(max_links)
+        self.trimfirst, self.slide, self.maxlen = int(trimfirst), int(slide), int(maxlen)
+        self._pending = {}
+        self._file_rows = {}
+        self._lock = threading.Lock()
+
+    def __call__(self, recs, res, sketch, kept):
+        begin, end = windows(res, self.trimfirst, self.slide, self.maxlen, self.spec.span)
+        with self._lock:
+            self._pending[id(recs)] = (begin, end, sketch, kept)
+
+    def take(self, recs):
+        """(begin, end, sketch, kept) of a batch the consumer has in hand."""
+        with self._lock:
+            return self._pending.pop(id(recs))
+
+    def add_file_rows(self, path, rows):
+        """The rows of one input file, in read order: (file, readID, tail, telo_length, begin, end, kept, sketch row) each."""
+        with self._lock:
+            self._file_rows.setdefault(path, []).extend(rows)
+
+    def rows_in_order(self, paths):
+        return [r for p in paths for r in self._file_rows.get(p, [])]
+
+    def finish(self, paths, engine):
+        """Link and group the run's reads on `engine` (anything with sketch_links): (read rows for end_reads_{k}.csv, group rows for
+        ends_{k}.csv, stats for the log)."""
+        rows = self.rows_in_order(paths)
+        part = [i for i, r in enumerate(rows) if r[6] >= self.min_kmers]
+        n = len(part)
+        if n > MAX_SKETCHES:
+            raise ValueError(f"--ends: {n} reads to compare, {MAX_SKETCHES} at most")
+        end = np.zeros(n, np.int32)
+        n_edges, best = np.zeros(n, np.int64), np.zeros(n, np.int64)
+        cut = 0
+        if n:
+            sketch = np.stack([rows[i][7] for i in part]).astype(np.uint32)
+            degree, links, matches = engine.sketch_links(sketch, self.min_match, self.max_links)
+            cut = int((degree > self.max_links).sum())
+            end = group(n, links, self.min_reads)
+            n_edges, best = edge_stats(n, links, matches)
+        where = {i: p for p, i in enumerate(part)}
+        read_rows = []
+        for i, (file, rid, tail, telo, b, e, kept, _row) in enumerate(rows):
+            p = where.get(i)
+            read_rows.append([file, rid, "forward" if tail == 0 else "reverse", telo, b, e, kept] +
+                             ([0, 0, 0] if p is None else [int(end[p]), int(n_edges[p]), int(best[p])]))
+        group_rows = []
+        for g in range(1, int(end.max()) + 1 if n else 1):
+            mem = [rows[part[p]] for p in np.nonzero(end == g)[0]]
+            telo = np.array([r[3] for r in mem], np.float64)
+            fwd = sum(1 for r in mem if r[2] == 0)
+            group_rows.append([g, len(mem), fwd, len(mem) - fwd, int(telo.min()), "%.1f" % np.median(telo), "%.1f" % telo.mean(), int(telo.max())])
+        stats = dict(reads=len(rows), compared=n, groups=len(group_rows), assigned=int((end > 0).sum()), cut=cut)
+        return read_rows, group_rows, stats
+
+
+READ_HEADER = ["file", "readID", "tail", "telo_length", "window_begin", "window_end", "kmers", "end", "links", "best_match"]
+GROUP_HEADER = ["end", "reads", "forward", "reverse", "telo_min", "telo_median", "telo_mean", "telo_max"]
+
+
+def write_csv(path, header, rows):
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(header)
+        w.writerows(rows)
+
+
+def summary(col: Collector, stats) -> list[str]:
+    """The log lines of one k."""
+    s = stats
+    return [f"end groups against {col.unit}: {s['reads']} reads with a boundary, {s['compared']} of them with at least {col.min_kmers} "
+            f"subtelomere {col.spec.k}-mers compared",
+            f"  {s['groups']} groups of at least {col.min_reads} reads: {s['assigned']} reads assigned, {s['reads'] - s['assigned']} unassigned (end 0)",
+            f"  {s['cut']} reads had more than {col.max_links} partners behind them: their links were cut at {col.max_links}"]

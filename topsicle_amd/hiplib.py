@@ -23,7 +23,7 @@ FOLLOW_MAX_FWD, FOLLOW_WIDE_MAX_FWD, FOLLOW_HIST_MAX = 15, 32, 8      # k-mers t
 EXPORTS = [
     "tps_abi_version", "tps_device_count", "tps_ctx_create", "tps_ctx_destroy", "tps_last_error",
     "tps_set_patterns", "tps_set_patterns_wide", "tps_batch_upload", "tps_batch_upload_packed", "tps_batch_upload_nib4", "tps_batch_share", "tps_host_alloc", "tps_host_free",
-    "tps_batch_download_packed", "tps_batch_kmer_followers", "tps_batch_kmer_followers_wide", "tps_batch_motif_census", "tps_batch_variant_census", "tps_batch_tract_map", "tps_batch_set_tails", "tps_batch_scan", "tps_sync",
+    "tps_batch_download_packed", "tps_batch_kmer_followers", "tps_batch_kmer_followers_wide", "tps_batch_motif_census", "tps_batch_variant_census", "tps_batch_tract_map", "tps_batch_end_sketch", "tps_sketch_links", "tps_batch_set_tails", "tps_batch_scan", "tps_sync",
     "tps_batch_results", "tps_batch_window_offsets", "tps_batch_window_sums", "tps_batch_window_raw",
     "tps_batch_raw_to_fd", "tps_batch_trc_counts", "tps_trc_counts", "tps_window_counts", "tps_binseg_l2", "tps_binseg_l2_ties", "tps_batch_read_sums", "tps_window_count",
     "tps_kernel_time_ms", "tps_kernel_time_reset", "tps_device_info", "tps_batch_kernel_info", "tps_ctx_debug_option", "tps_debug_stamps_get",
@@ -63,6 +63,9 @@ TRACT_DTYPE = np.dtype([("begin", "<i4"), ("end", "<i4"), ("hits", "<i4"), ("blo
 assert TRACT_DTYPE.itemsize == 16
 # tps_batch_tract_map: letters of the unit, block (a multiple of 64), gap, min_blocks, max_tracts; min_hits is 1..block
 TRACT_UNIT_RANGE, TRACT_BLOCK_RANGE, TRACT_GAP_RANGE, TRACT_MIN_BLOCKS_RANGE, TRACT_MAX_TRACTS_RANGE = (4, 32), (64, 1024), (0, 64), (1, 64), (1, 16)
+# tps_batch_end_sketch: k, buckets, end - begin; tps_sketch_links: sketches, links kept per row
+ENDS_K_RANGE, ENDS_BUCKETS, ENDS_MAX_WINDOW, LINKS_MAX_N, LINKS_MAX_LINKS = (8, 16), (64, 128, 256, 512), 16384, 262144, 256
+ENDS_EMPTY = 0xFFFFFFFF           # an empty bucket of a sketch
 RES_TIE = 1            # TPS_RES_TIE: the exact tournament decided the change-point (candidates within float64 noise of each other)
 
 
@@ -108,6 +111,8 @@ def load_library(path: str | None = None) -> C.CDLL:
         "tps_batch_motif_census": (C.c_int, [vp, i32, i32, i32, i32, i32, i32, vp, i64, vp, i64]),
         "tps_batch_variant_census": (C.c_int, [vp, i32, C.c_uint64, i32, vp, vp, vp, i64, i32, i32, vp, i64, vp, i64]),
         "tps_batch_tract_map": (C.c_int, [vp, i32, C.c_uint64, i32, i32, i32, i32, i32, i32, vp, i64, vp, i64, vp, i64]),
+        "tps_batch_end_sketch": (C.c_int, [vp, i32, C.c_uint64, i32, i32, i32, vp, vp, vp, i64, vp, i64, vp, i64]),
+        "tps_sketch_links": (C.c_int, [vp, vp, i64, i32, i64, i32, i32, vp, i64, vp, i64, vp, i64]),
         "tps_batch_set_tails": (C.c_int, [vp, i32, vp]),
         "tps_batch_scan": (C.c_int, [vp, i32, C.POINTER(Params)]),
         "tps_sync": (C.c_int, [vp]),
@@ -484,6 +489,44 @@ class HipScanner:
         self._check(self.lib.tps_batch_tract_map(self._h, slot, code, m, block, min_hits, gap, min_blocks, max_tracts,
                                                  _ptr(tracts), n * 2 * max_tracts, _ptr(found), found.size, _ptr(totals), totals.size))
         return tracts, found, totals
+
+    def end_sketch(self, slot: int, unit: str, tails, begin, end, k: int = 12, buckets: int = 256):
+        """A sketch of the window [begin, end) of every read of the resident batch, telomere first (tails: 0 = the read, 1 = its
+        reverse complement): the smallest hash per bucket over the k-mers that hold no word of the telomere repeat `unit` (a
+        primitive word of ACGT, 4 .. 32 letters; tps_batch_end_sketch, the rule is in include/topsicle_hip.h; groups and files:
+        topsicle_amd.ends): (sketch uint32[n, buckets], kept uint32[n]).  An empty bucket holds ENDS_EMPTY.  No pattern table
+        needed; the slot's scan outputs stay as they are."""
+        from . import variants
+        code, m = variants.unit_code(unit)
+        n = self._n[slot]
+        tails = np.ascontiguousarray(tails, dtype=np.uint8)
+        begin = np.ascontiguousarray(begin, dtype=np.int32)
+        end = np.ascontiguousarray(end, dtype=np.int32)
+        if not (len(tails) == len(begin) == len(end)):
+            raise TopsicleHipError("end_sketch: tails, begin and end must have one entry per read")
+        nb = buckets if buckets in ENDS_BUCKETS else ENDS_BUCKETS[0]          # (a bad count is the library's to refuse)
+        sketch = np.zeros((n, nb), dtype=np.uint32)
+        kept = np.zeros(n, dtype=np.uint32)
+        self._check(self.lib.tps_batch_end_sketch(self._h, slot, code, m, k, buckets, _ptr(tails), _ptr(begin), _ptr(end), len(tails),
+                                                  _ptr(sketch), n * buckets, _ptr(kept), kept.size))
+        return sketch, kept
+
+    def sketch_links(self, sketch, min_match: int = 6, max_links: int = 32):
+        """All pairs of the rows of `sketch` (uint32[n, buckets], as end_sketch returns them; tps_sketch_links): (degree int32[n],
+        links int32[n, max_links], matches int32[n, max_links]) -- per row i the true number of rows j > i that share at least
+        min_match non-empty buckets with it, the smallest such j in ascending order (-1 behind them) and their match counts.  Needs
+        no resident batch."""
+        sketch = np.ascontiguousarray(sketch, dtype=np.uint32)
+        if sketch.ndim != 2:
+            raise TopsicleHipError("sketch_links: sketch must be a 2-d array")
+        n, b = sketch.shape
+        ml = max_links if 1 <= max_links <= LINKS_MAX_LINKS else 1            # (a bad count is the library's to refuse)
+        degree = np.zeros(n, dtype=np.int32)
+        links = np.full((n, ml), -1, dtype=np.int32)
+        matches = np.zeros((n, ml), dtype=np.int32)
+        self._check(self.lib.tps_sketch_links(self._h, _ptr(sketch), n, b, sketch.size, min_match, max_links, _ptr(degree), degree.size,
+                                              _ptr(links), n * max_links, _ptr(matches), n * max_links))
+        return degree, links, matches
 
     def set_tails(self, slot: int, tails: np.ndarray):
         tails = np.ascontiguousarray(tails, dtype=np.uint8)

@@ -20,7 +20,7 @@ from collections import defaultdict
 
 import numpy as np
 
-from . import allsteps, batch, hiplib, motif, rawnpz, seqio, tracts, variants
+from . import allsteps, batch, ends, hiplib, motif, rawnpz, seqio, tracts, variants
 
 version_number = "1.0.0"
 Topsicle_output_prefix = "Topsicle"
@@ -145,11 +145,15 @@ def process_file_multi(args, seq_loc, phrases, engines):
     # --variants: one collector per k for the whole run (analysis_run made them); the census runs on the batch workers
     vcols = getattr(args, "variant_collectors", None) or [None] * len(phrases)
     vrows = [[] for _ in phrases]
+    # --ends: the same per k; the sketch runs on the batch workers, the links once per run (analysis_run)
+    ecols = getattr(args, "end_collectors", None) or [None] * len(phrases)
+    erows = [[] for _ in phrases]
     jobs = [batch.Job(pattern, hiplib.make_params(
         no_bp=no_bp, min_len=args.minSeqLength, min_count=allsteps.min_count_for_cutoff(min_cutoff, ratio, no_bp),
         window=args.windowSize, slide=slide, trimfirst=args.trimfirst, maxlen=args.maxlengthtelo,
-        flags=hiplib.F_STEP1 | hiplib.F_WINDOWS | hiplib.F_BINSEG), want_sums, want_raw, raw_sink=sink, variants=None if col is None else col.spec)
-        for (_k, pattern, slide), sink, col in zip(phrases, raw_npz, vcols)]
+        flags=hiplib.F_STEP1 | hiplib.F_WINDOWS | hiplib.F_BINSEG), want_sums, want_raw, raw_sink=sink, variants=None if col is None else col.spec,
+        ends=None if ecol is None else ecol.spec)
+        for (_k, pattern, slide), sink, col, ecol in zip(phrases, raw_npz, vcols, ecols)]
     # --tracts: one collector for the whole run; the map runs once per batch, with the first k's job
     tcol = getattr(args, "tract_collector", None)
     if tcol is not None:
@@ -240,6 +244,7 @@ def process_file_multi(args, seq_loc, phrases, engines):
             for n, ((telo_phrase, pattern, sliding_val), (res, sums, raw, win_off)) in enumerate(zip(phrases, outs)):
                 idx = np.nonzero(res["pass"])[0]
                 vout = vcols[n].take(pb) if vcols[n] is not None else None
+                eout = ecols[n].take(pb) if ecols[n] is not None else None
                 if wthread is not None and len(idx) and n == writer_k:
                     write_passing(pb, idx)                                   # every passing record (main.py:83-86)
                 ids = [pb.read_id(int(i)) for i in idx]
@@ -263,6 +268,10 @@ def process_file_multi(args, seq_loc, phrases, engines):
                     v_begin, v_end, v_counts = vout
                     vrows[n] += [(file_name, ids[j], int(r["tail"][j]), int(v_begin[idx[j]]), int(v_end[idx[j]]), v_counts[idx[j]])
                                  for j in np.nonzero(telolen != 0)[0]]
+                if eout is not None:                                         # one row per read with a stored boundary
+                    e_begin, e_end, e_sketch, e_kept = eout
+                    erows[n] += [(file_name, ids[j], int(r["tail"][j]), telo_l[j], int(e_begin[idx[j]]), int(e_end[idx[j]]), int(e_kept[idx[j]]),
+                                  e_sketch[idx[j]].copy()) for j in np.nonzero(telolen != 0)[0]]
                 if n == 0:
                     with _CSV_LOCK, open(csv_path, mode="a", newline="") as fh:
                         csv.writer(fh).writerows(zip([file_name] * len(ids), [telo_phrase] * len(ids), ["%.3f" % t for t in trc_l], ids, telo_l))
@@ -310,6 +319,9 @@ def process_file_multi(args, seq_loc, phrases, engines):
     for col, vr in zip(vcols, vrows):
         if col is not None:
             col.add_file_rows(seq_loc, vr)
+    for col, er in zip(ecols, erows):
+        if col is not None:
+            col.add_file_rows(seq_loc, er)
     st = pool.stats
     if st.get("shards", 0) > 1:
         tprint(f"{base_name}: read as {st['shards']} byte ranges, one reader team each")
@@ -348,6 +360,12 @@ def analysis_run(args, engines=None, engine_factory=None, wait_plots=True):
         why = tracts.check(root, args.tractblock, args.tractminhits, args.tractgap, args.tractminblocks, tracts.DEFAULT_MAX_TRACTS, args.tractedge)
         if why is not None:
             tprint(f"--tracts needs {why}")
+            sys.exit(2)
+    if getattr(args, "ends", False):
+        root = "ACGT" if args.pattern.strip().lower() == "auto" else variants.primitive_root(args.pattern.upper())
+        why = ends.check(root, args.endspan, args.endk, args.endbuckets, args.endminmatch, args.endminkmers, args.endminreads)
+        if why is not None:
+            tprint(f"--ends needs {why}")
             sys.exit(2)
     if args.pattern.strip().lower() == "auto":
         # the motif comes from the reads (motif.py); from here on the run is the one `--pattern <that motif>` would have been
@@ -415,6 +433,18 @@ def analysis_run(args, engines=None, engine_factory=None, wait_plots=True):
         args.variant_collectors = [variants.Collector(unit, args.variantbin, args.variantbins, args.trimfirst, slide, args.maxlengthtelo)
                                    for _k, _pattern, slide in phrases]
 
+    args.end_collectors = None
+    if getattr(args, "ends", False):
+        unit = variants.primitive_root(args.pattern.upper())
+        why = ends.check(unit, args.endspan, args.endk, args.endbuckets, args.endminmatch, args.endminkmers, args.endminreads)
+        if why is not None:
+            tprint(f"--ends needs {why}")
+            sys.exit(2)
+        if unit != args.pattern.upper():
+            tprint(f"--ends: {args.pattern} is a power of {unit}; k-mers with words of {unit} are left out of the sketches")
+        args.end_collectors = [ends.Collector(unit, args.endk, args.endbuckets, args.endspan, args.endminmatch, args.endminkmers, args.endminreads,
+                                              args.trimfirst, slide, args.maxlengthtelo) for _k, _pattern, slide in phrases]
+
     args.tract_collector = None
     if getattr(args, "tracts", False):
         unit = variants.primitive_root(args.pattern.upper())
@@ -464,6 +494,19 @@ def analysis_run(args, engines=None, engine_factory=None, wait_plots=True):
         variants.write_profile_csv(f"{args.outputDir}/variant_profile_{telo_phrase}.csv", col.unit, col.profile, col.spec.bin)
         tprint(f"variant repeats (k = {telo_phrase}): {args.outputDir}/variants_{telo_phrase}.csv, {args.outputDir}/variant_profile_{telo_phrase}.csv")
         for line in variants.summary(col.unit, col.total, col.n_tracts):
+            tprint(line)
+
+    for (telo_phrase, _pattern, _slide), col in zip(phrases, args.end_collectors or []):
+        # all pairs of the run's sketches: one call per k, on one context, after the last file
+        try:
+            read_rows, group_rows, stats = col.finish(filenames, engines[0])
+        except ValueError as e:                    # more reads than one link call takes: said, not hidden; every other output stands
+            tprint(f"{e}; no end groups written for k = {telo_phrase}")
+            continue
+        ends.write_csv(f"{args.outputDir}/end_reads_{telo_phrase}.csv", ends.READ_HEADER, read_rows)
+        ends.write_csv(f"{args.outputDir}/ends_{telo_phrase}.csv", ends.GROUP_HEADER, group_rows)
+        tprint(f"end groups (k = {telo_phrase}): {args.outputDir}/end_reads_{telo_phrase}.csv, {args.outputDir}/ends_{telo_phrase}.csv")
+        for line in ends.summary(col, stats):
             tprint(line)
 
     if args.tract_collector is not None:
@@ -622,6 +665,15 @@ def build_parser():
                              "the rest -- per read (variants_{k}.csv) and per distance from the boundary (variant_profile_{k}.csv)")
     parser.add_argument("--variantbin", metavar="INT", type=int, default=variants.DEFAULT_BIN, help="--variants: width of a profile bin in bases (64..4064)")
     parser.add_argument("--variantbins", metavar="INT", type=int, default=variants.DEFAULT_BINS, help="--variants: bins of the profile, the last takes everything beyond (1..64)")
+    parser.add_argument("--ends", action="store_true",
+                        help="MI355X build: group the telomeric reads by chromosome end from a sketch of the subtelomere behind each called boundary -- one row "
+                             "per read (end_reads_{k}.csv) and one per group (ends_{k}.csv); groups of reads, not chromosome names")
+    parser.add_argument("--endspan", metavar="INT", type=int, default=ends.DEFAULT_SPAN, help="--ends: bases behind the boundary that are sketched (endk..16384; never beyond maxlengthtelo)")
+    parser.add_argument("--endk", metavar="INT", type=int, default=ends.DEFAULT_K, help="--ends: k-mer length of the sketch (8..16)")
+    parser.add_argument("--endbuckets", metavar="INT", type=int, default=ends.DEFAULT_BUCKETS, help="--ends: buckets of a sketch (64, 128, 256 or 512)")
+    parser.add_argument("--endminmatch", metavar="INT", type=int, default=ends.DEFAULT_MIN_MATCH, help="--ends: equal buckets that link two reads (1..endbuckets)")
+    parser.add_argument("--endminkmers", metavar="INT", type=int, default=ends.DEFAULT_MIN_KMERS, help="--ends: subtelomere k-mers a read needs to take part")
+    parser.add_argument("--endminreads", metavar="INT", type=int, default=ends.DEFAULT_MIN_READS, help="--ends: reads a group needs to be reported as an end")
     parser.add_argument("--tracts", action="store_true",
                         help="MI355X build: map the telomere-repeat tracts of every WHOLE read, on both strands -- one row per tract (tracts.csv) and one per "
                              "read with a tract and its class: fusion, both_ends, interstitial, terminal (tract_reads.csv).  Runs the files as --twopass off")
