@@ -387,6 +387,39 @@ int  tps_sketch_links(tps_ctx* ctx, const uint32_t* sketch, int64_t n, int32_t b
                       int32_t max_links, int32_t* degree, int64_t degree_len, int32_t* links, int64_t links_len, int32_t* matches,
                       int64_t matches_len);
 
+/* ---- anchored lengths (one boundary per end group, in the coordinates of one of its reads) --- */
+/* The KEPT WINDOW of every read of the resident batch: what tps_batch_end_sketch hashes, handed out position by position.  The
+ * same telomere-first string h, the same window [begin, min(end, L)), the same unit, k and KEPT rule; span = the longest window,
+ * k <= span <= 4096.  Rows of (span + 15) / 16 and (span + 31) / 32 dwords, every dword written:
+ *   codes   letter q of the window (h[begin + q]) as a 2-bit code (A C T G = 0 1 2 3, already complemented for tail 1) at bits
+ *           2 (q & 15) of dword q >> 4; a letter that is not ACGT, and everything behind the window's last letter, is 0.
+ *   keep    bit q & 31 of dword q >> 5 is set exactly when the k-mer at begin + q is KEPT; popcount(keep[r]) == kept[r] of the
+ *           sketch of the same window.
+ * Exact, identical from run to run.  The checks and codes of tps_batch_end_sketch (TPS_E_ARG: the unit, a tail other than 0 / 1, a
+ * negative begin / end, begin > end; TPS_E_CAPACITY: k outside 8..16, end - begin > 16384; TPS_E_STATE: an empty slot), and
+ * TPS_E_CAPACITY: span outside k..4096, end - begin > span; TPS_E_ARG: n_reads or an array length that does not match the slot and
+ * span.  One launch; returns when the outputs are in place.  The slot's scan state is not touched. */
+int  tps_batch_end_window(tps_ctx* ctx, int32_t slot, uint64_t unit, int32_t m, int32_t k, const uint8_t* tails, const int32_t* begin,
+                          const int32_t* end, int64_t n_reads, int32_t span, uint32_t* codes, int64_t codes_len, uint32_t* keep,
+                          int64_t keep_len);
+/* The offset of window i against window ref[i], for n windows from the host (rows as tps_batch_end_window writes them, length[i]
+ * letters each; no resident batch needed).  The kept positions of a window are the p in [0, length - k] whose keep bit is set;
+ * x(p) = fmix32(c ^ 0x9E3779B9) of the k-mer's codes c, as in the sketch (fmix32 is a bijection: equal x, equal k-mer).
+ *   table   of the reference R: 4096 slots, empty = 0xFFFFFFFF; every kept q of R does
+ *           T[x >> 20] = min(T[x >> 20], ((x & 0xFFFFF) << 12) | q): the smallest low 20 bits win a slot, then the smallest q.
+ *   votes   a kept p of the query Q with t = T[x >> 20], t != empty and (t >> 12) == (x & 0xFFFFF), votes for the diagonal
+ *           d = (t & 4095) - p, -4096 < d < 4096.
+ *   coarse  H[(d + 4096) >> 6]++ over 128 bins; pair[c] = H[c] + H[c + 1], c = 0 .. 126; best = the smallest c with the largest
+ *           pair; second = the largest pair[c] with |c - best| >= 2, 0 if there is none.
+ *   fine    the 128 diagonals 64 best - 4096 <= d < 64 best - 3968: votes = their number (= pair[best]); offset = their lower
+ *           median, element (votes - 1) / 2 of the sorted votes, 0 when votes == 0.
+ * offset, votes, second: int32[n], in window coordinates (the caller adds begin_R - begin_Q).  A row with ref[i] < 0 gets 0, 0, 0;
+ * ref[i] == i is allowed.  Exact, identical from run to run (minima and counts do not depend on order).  TPS_E_CAPACITY: n over
+ * 262144, span outside k..4096, k outside 8..16.  TPS_E_ARG: ref[i] >= n, length[i] outside 0..span, out_len != n.  One launch;
+ * returns when the outputs are in place. */
+int  tps_window_offsets(tps_ctx* ctx, const uint32_t* codes, const uint32_t* keep, const int32_t* length, const int32_t* ref, int64_t n,
+                        int32_t span, int32_t k, int32_t* offset, int32_t* votes, int32_t* second, int64_t out_len);
+
 /* ---- measurement ----------------------------------------------------------------------- */
 /* hipEvent timings of the scan kernel launches since the last reset: number of launches,
  * total and mean milliseconds (events are recorded on the stream the kernel runs on). */

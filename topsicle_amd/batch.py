@@ -51,7 +51,8 @@ class Job:
         the batch, passing or not, and hands (recs, tracts, found, totals) to the spec's sink.  The map needs whole reads: a batch
         in heads mode is refused.  One job of a batch carries it (the map does not depend on the pattern table).
         ends (ends.EndSpec: unit, k, buckets, span, sink): the worker that scanned the batch sketches the subtelomere window behind every
-        called boundary while the batch is still resident and hands (recs, results, sketch, kept) to the spec's sink."""
+        called boundary while the batch is still resident and hands (recs, results, sketch, kept) to the spec's sink -- and, for a
+        spec with `anchor` set, the windows' packed letters and keep bits behind them (recs, results, sketch, kept, codes, keep)."""
         self.patterns, self.prm, self.want_sums, self.want_raw = list(patterns), prm, bool(want_sums), bool(want_raw)
         self.raw_sink = raw_sink if want_raw else None
         self.variants = variants
@@ -139,19 +140,31 @@ def _census_variants(job, eng, slot, recs, res, slot_index=None):
 def _sketch_ends(job, eng, slot, recs, res, slot_index=None):
     """The end sketch of the windows behind the boundaries the scan has just called (Job.ends), on the engine and slot that were
     scanned: [boundary, min(boundary + span, maxlen)) of the telomere-first string where the CLI would store the boundary
-    (ends.windows), begin = end = 0 -- an empty sketch -- for every other read.  `slot_index` as in _census_variants."""
+    (ends.windows), begin = end = 0 -- an empty sketch -- for every other read.  `slot_index` as in _census_variants.  A spec with
+    `anchor` set also gets the same windows position by position (end_window: packed letters and keep bits), right behind the sketch."""
     from . import ends
     spec = job.ends
+    anchor = getattr(spec, "anchor", False)
     begin, end = ends.windows(res, int(job.prm.trimfirst), int(job.prm.slide), int(job.prm.maxlen), spec.span)
     tails = np.where(end > begin, res["tail"], 0).astype(np.uint8)
     sketch = np.full((len(res), spec.buckets), ends.EMPTY, np.uint32)
     kept = np.zeros(len(res), np.uint32)
+    if anchor:
+        codes = np.zeros((len(res), (spec.span + 15) // 16), np.uint32)
+        keep = np.zeros((len(res), (spec.span + 31) // 32), np.uint32)
     if slot_index is None:
         if eng is not None:
             sketch, kept = eng.end_sketch(slot, spec.unit, tails, begin, end, spec.k, spec.buckets)
+            if anchor:
+                codes, keep = eng.end_window(slot, spec.unit, tails, begin, end, spec.k, spec.span)
     elif len(slot_index):
         sketch[slot_index], kept[slot_index] = eng.end_sketch(slot, spec.unit, tails[slot_index], begin[slot_index], end[slot_index], spec.k, spec.buckets)
-    spec.sink(recs, res, sketch, kept)
+        if anchor:
+            codes[slot_index], keep[slot_index] = eng.end_window(slot, spec.unit, tails[slot_index], begin[slot_index], end[slot_index], spec.k, spec.span)
+    if anchor:
+        spec.sink(recs, res, sketch, kept, codes, keep)
+    else:
+        spec.sink(recs, res, sketch, kept)
 
 
 def _map_tracts(job, eng, slot, recs):

@@ -25,6 +25,7 @@
 #include "tps_variant.h"
 #include "tps_tract.h"
 #include "tps_ends.h"
+#include "tps_anchor.h"
 #include "tps_pack.h"
 #include "tps_plan.h"
 #include "tps_wide.h"
@@ -144,6 +145,26 @@ __global__ void __launch_bounds__(NT * LINKS_WPG) sketch_links_kernel(LinkArgs a
     const int64_t i = (int64_t)blockIdx.x * LINKS_WPG + wave;
     if (i >= a.n) return;
     sketch_links_row(a, i, smem + wave * LINKS_LDS_DW);
+}
+// The kept windows (tps_batch_end_window; end_window_read in csrc/tps_anchor.h): the sketch's layout -- the hit table shared by the
+// workgroup's waves, one wave per read.
+__global__ void __launch_bounds__(NT * ENDS_WPG) end_window_kernel(EndWindowArgs a) {
+    __shared__ __attribute__((aligned(16))) uint32_t smem[TRACT_TABLE_DW + ENDS_WPG * ENDS_LDS_DW];
+    const int tab_dw = tract_table_dw(a.w);
+    for (int i = (int)threadIdx.x; i < tab_dw; i += NT * ENDS_WPG) smem[i] = a.table[i];
+    __syncthreads();
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t r = (int64_t)blockIdx.x * ENDS_WPG + wave;
+    if (r >= a.n_reads) return;
+    end_window_read(a, r, smem + TRACT_TABLE_DW + wave * ENDS_LDS_DW, smem);
+}
+// The offsets between windows (tps_window_offsets; window_offsets_row in csrc/tps_anchor.h): one wave per query row.
+__global__ void __launch_bounds__(NT * OFFSETS_WPG) window_offsets_kernel(OffsetArgs a) {
+    __shared__ __attribute__((aligned(16))) uint32_t smem[OFFSETS_WPG * OFFSETS_LDS_DW];
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t i = (int64_t)blockIdx.x * OFFSETS_WPG + wave;
+    if (i >= a.n) return;
+    window_offsets_row(a, i, smem + wave * OFFSETS_LDS_DW);
 }
 }  // namespace tps
 
@@ -408,6 +429,8 @@ struct tps_ctx {
     DevBuf tract_table, tract_out;    // tps_batch_tract_map: the call's hit table; tracts, found and totals behind one another
     DevBuf ends_in, ends_out;         // tps_batch_end_sketch: tails / begin / end; sketch and kept behind one another (its table is tract_table)
     DevBuf links_t, links_out;        // tps_sketch_links: the sketches bucket-major; degree, links and matches behind one another
+    DevBuf window_out;                // tps_batch_end_window: codes and keep behind one another (its inputs are ends_in, its table tract_table)
+    DevBuf offsets_in, offsets_out;   // tps_window_offsets: codes, keep, length and ref; offset, votes and second behind one another
     DevBuf ascii, ascii_off;          // staging of tps_batch_upload: ASCII bases + offsets, packed on the device right after the copy
     DevBuf nib, nib_src;              // staging of tps_batch_upload_nib4: BAM base codes + where each read's are, expanded right after the copy
     std::set<void*> pinned;           // host buffers handed out by tps_host_alloc
@@ -1563,6 +1586,97 @@ int tps_sketch_links(tps_ctx* c, const uint32_t* sketch, int64_t n, int32_t buck
     HIP_TRY(hipMemcpyAsync(degree, a.degree, dg_bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(links, a.links, ln_bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(matches, a.matches, ln_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return TPS_OK;
+}
+
+int tps_batch_end_window(tps_ctx* c, int32_t slot, uint64_t unit, int32_t m, int32_t k, const uint8_t* tails, const int32_t* begin, const int32_t* end,
+                         int64_t n_reads, int32_t span, uint32_t* codes, int64_t codes_len, uint32_t* keep, int64_t keep_len) {
+    int rc;
+    if ((rc = bind(c))) return rc;
+    Slot* sl = get_slot(c, slot);
+    if (!sl) return TPS_E_ARG;
+    if (sl->n < 0) return fail(TPS_E_STATE, "no batch uploaded in this slot");
+    const char* why = "";
+    if ((rc = tps::ends_check(unit, m, k, tps::ENDS_MIN_BUCKETS, &why))) return fail(rc, "%s", why);
+    if ((rc = tps::window_check_span(span, k, &why))) return fail(rc, "%s", why);
+    const int64_t n = sl->n;
+    const int cdw = (span + 15) / 16, kdw = (span + 31) / 32;
+    if (n_reads != n) return fail(TPS_E_ARG, "tails, begin and end must hold %lld reads", (long long)n);
+    if (codes_len != n * cdw) return fail(TPS_E_ARG, "codes must hold %lld dwords", (long long)(n * cdw));
+    if (keep_len != n * kdw) return fail(TPS_E_ARG, "keep must hold %lld dwords", (long long)(n * kdw));
+    if (n == 0) return TPS_OK;
+    if (!tails || !begin || !end || !codes || !keep) return fail(TPS_E_ARG, "null tails / begin / end / codes / keep");
+    int64_t at = 0;
+    if ((rc = tps::ends_check_reads(tails, begin, end, n, &why, &at))) return fail(rc, "read %lld: %s", (long long)at, why);
+    if ((rc = tps::window_check_reads(begin, end, n, span, &why, &at))) return fail(rc, "read %lld: %s", (long long)at, why);
+    // (like the sketch: the pattern table, the slot's tails, its scan outputs and its plan are not touched)
+    const int w = m < tps::TRACT_MAX_WORD ? m : tps::TRACT_MAX_WORD;
+    std::vector<uint32_t> table((size_t)tps::tract_table_dw(w));
+    tps::tract_hit_table(unit, m, table.data());
+    const size_t tab_bytes = table.size() * 4, co_bytes = (size_t)n * cdw * 4, kp_bytes = (size_t)n * kdw * 4;
+    const size_t off_begin = (((size_t)n + 15) & ~(size_t)15), off_end = off_begin + (size_t)n * 4;
+    if ((rc = c->tract_table.ensure(tab_bytes))) return rc;
+    if ((rc = c->ends_in.ensure(off_end + (size_t)n * 4))) return rc;
+    if ((rc = c->window_out.ensure(co_bytes + kp_bytes))) return rc;
+    HIP_TRY(hipMemcpyAsync(c->tract_table.p, table.data(), tab_bytes, hipMemcpyHostToDevice, c->stream));      // (pageable: the copy has left `table` when the call returns)
+    HIP_TRY(hipMemcpyAsync(c->ends_in.p, tails, (size_t)n, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync((char*)c->ends_in.p + off_begin, begin, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync((char*)c->ends_in.p + off_end, end, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    tps::EndWindowArgs a{};
+    a.seq2 = (const uint32_t*)sl->seq2.p;
+    a.inv = (const uint16_t*)sl->inv.p;
+    a.desc = (const tps_read_desc*)sl->desc.p;
+    a.table = (const uint32_t*)c->tract_table.p;
+    a.tails = (const uint8_t*)c->ends_in.p;
+    a.begin = (const int32_t*)((const char*)c->ends_in.p + off_begin);
+    a.end = (const int32_t*)((const char*)c->ends_in.p + off_end);
+    a.codes = (uint32_t*)c->window_out.p;
+    a.keep = (uint32_t*)((char*)c->window_out.p + co_bytes);
+    a.n_reads = n;
+    a.w = w; a.k = k; a.cdw = cdw; a.kdw = kdw;
+    hipLaunchKernelGGL(tps::end_window_kernel, dim3((unsigned)((n + tps::ENDS_WPG - 1) / tps::ENDS_WPG)), dim3(tps::NT * tps::ENDS_WPG), 0, c->stream, a);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(codes, a.codes, co_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(keep, a.keep, kp_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return TPS_OK;
+}
+
+int tps_window_offsets(tps_ctx* c, const uint32_t* codes, const uint32_t* keep, const int32_t* length, const int32_t* ref, int64_t n, int32_t span,
+                       int32_t k, int32_t* offset, int32_t* votes, int32_t* second, int64_t out_len) {
+    int rc;
+    if ((rc = bind(c))) return rc;
+    const char* why = "";
+    if ((rc = tps::offsets_check(n, span, k, out_len, &why))) return fail(rc, "%s", why);
+    if (n == 0) return TPS_OK;
+    if (!codes || !keep || !length || !ref || !offset || !votes || !second) return fail(TPS_E_ARG, "null codes / keep / length / ref / offset / votes / second");
+    int64_t at = 0;
+    if ((rc = tps::offsets_check_rows(length, ref, n, span, &why, &at))) return fail(rc, "row %lld: %s", (long long)at, why);
+    const int cdw = (span + 15) / 16, kdw = (span + 31) / 32;
+    const size_t co_bytes = (size_t)n * cdw * 4, kp_bytes = (size_t)n * kdw * 4, n_bytes = (size_t)n * 4;
+    if ((rc = c->offsets_in.ensure(co_bytes + kp_bytes + 2 * n_bytes))) return rc;
+    if ((rc = c->offsets_out.ensure(3 * n_bytes))) return rc;
+    char* in = (char*)c->offsets_in.p;
+    HIP_TRY(hipMemcpyAsync(in, codes, co_bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(in + co_bytes, keep, kp_bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(in + co_bytes + kp_bytes, length, n_bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(in + co_bytes + kp_bytes + n_bytes, ref, n_bytes, hipMemcpyHostToDevice, c->stream));
+    tps::OffsetArgs a{};
+    a.codes = (const uint32_t*)in;
+    a.keep = (const uint32_t*)(in + co_bytes);
+    a.length = (const int32_t*)(in + co_bytes + kp_bytes);
+    a.ref = (const int32_t*)(in + co_bytes + kp_bytes + n_bytes);
+    a.offset = (int32_t*)c->offsets_out.p;
+    a.votes = (int32_t*)((char*)c->offsets_out.p + n_bytes);
+    a.second = (int32_t*)((char*)c->offsets_out.p + 2 * n_bytes);
+    a.n = n;
+    a.k = k; a.cdw = cdw; a.kdw = kdw;
+    hipLaunchKernelGGL(tps::window_offsets_kernel, dim3((unsigned)((n + tps::OFFSETS_WPG - 1) / tps::OFFSETS_WPG)), dim3(tps::NT * tps::OFFSETS_WPG), 0, c->stream, a);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(offset, a.offset, n_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(votes, a.votes, n_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(second, a.second, n_bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return TPS_OK;
 }

@@ -137,6 +137,19 @@ TPS_DEV uint64_t ends_word_ballot(const uint32_t* seq, const uint32_t* tab, int 
     return wave_ballot(h);
 }
 
+// is the k-mer at position t of a staged piece (q = delta + t) kept?  cur / nxt: the repeat-word ballots of t's step and of the next
+// one.  (Shared with end_window_read, tps_anchor.h: the keep bits it writes are this predicate.)
+TPS_DEV bool ends_keep(uint64_t cur, uint64_t nxt, uint64_t wbits, int t, int np, bool any_inv, const uint16_t* val, int q, uint64_t bad_bits, int tid) {
+    const uint64_t words = ((cur >> tid) | ((nxt << 1) << (NT - 1 - tid))) & wbits;
+    bool keep = t < np && words == 0;
+    if (any_inv) {
+        const int idx = q >> 4;
+        const uint64_t v = (uint64_t)val[idx] | ((uint64_t)val[idx + 1] << 16) | ((uint64_t)val[idx + 2] << 32);
+        if (((v >> (q & 15)) & bad_bits) != 0) keep = false;
+    }
+    return keep;
+}
+
 // `tab`: the hit table (device: the workgroup's copy in LDS)
 TPS_DEV void end_sketch_read(const EndSketchArgs& a, int64_t r, uint32_t* lds, const uint32_t* tab) {
     uint32_t* seq = lds;
@@ -181,13 +194,7 @@ TPS_DEV void end_sketch_read(const EndSketchArgs& a, int64_t r, uint32_t* lds, c
             TPS_PHASE_WITH(ln) {
                 const int t = s * NT + tid;
                 const int q = st.delta + t;
-                const uint64_t words = ((cur >> tid) | ((nxt << 1) << (NT - 1 - tid))) & wbits;
-                bool keep = t < np && words == 0;
-                if (any_inv) {
-                    const int idx = q >> 4;
-                    const uint64_t v = (uint64_t)val[idx] | ((uint64_t)val[idx + 1] << 16) | ((uint64_t)val[idx + 2] << 32);
-                    if (((v >> (q & 15)) & bad_bits) != 0) keep = false;
-                }
+                const bool keep = ends_keep(cur, nxt, wbits, t, np, any_inv, val, q, bad_bits, tid);
                 if (keep) {
                     const uint32_t c = (v_at(seq, q) ^ flip) & kmask;
                     const uint32_t x = ends_fmix32(c ^ 0x9E3779B9u);

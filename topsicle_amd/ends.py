@@ -45,10 +45,12 @@ def check(unit: str, span: int = DEFAULT_SPAN, k: int = DEFAULT_K, buckets: int 
 
 class EndSpec:
     """What batch.Job(ends=...) carries: the primitive unit, k, the buckets, the window's span, and `sink(recs, res, sketch, kept)`,
-    called by the worker that scanned a batch while that batch is still resident."""
+    called by the worker that scanned a batch while that batch is still resident.  `anchor` (anchor.py): the worker also extracts the
+    windows themselves and calls `sink(recs, res, sketch, kept, codes, keep)`."""
 
-    def __init__(self, unit: str, k: int = DEFAULT_K, buckets: int = DEFAULT_BUCKETS, span: int = DEFAULT_SPAN, sink=None):
+    def __init__(self, unit: str, k: int = DEFAULT_K, buckets: int = DEFAULT_BUCKETS, span: int = DEFAULT_SPAN, sink=None, anchor: bool = False):
         self.unit, self.k, self.buckets, self.span, self.sink = variants.primitive_root(unit.upper()), int(k), int(buckets), int(span), sink
+        self.anchor = bool(anchor)
 
 
 def windows(res, trimfirst: int, slide: int, maxlen: int, span: int):
@@ -120,27 +122,36 @@ class Collector:
 
     def __init__(self, unit: str, k: int = DEFAULT_K, buckets: int = DEFAULT_BUCKETS, span: int = DEFAULT_SPAN, min_match: int = DEFAULT_MIN_MATCH,
                  min_kmers: int = DEFAULT_MIN_KMERS, min_reads: int = DEFAULT_MIN_READS, trimfirst: int = 100, slide: int = 6, maxlen: int = 20000,
-                 max_links: int = DEFAULT_MAX_LINKS):
-        self.spec = EndSpec(unit, k, buckets, span, self)
+                 max_links: int = DEFAULT_MAX_LINKS, anchor: bool = False):
+        self.spec = EndSpec(unit, k, buckets, span, self, anchor)
         self.unit = self.spec.unit
         self.min_match, self.min_kmers, self.min_reads, self.max_links = int(min_match), int(min_kmers), int(min_reads), int(max_links)
         self.trimfirst, self.slide, self.maxlen = int(trimfirst), int(slide), int(maxlen)
         self._pending = {}
+        self._pending_windows = {}    # (with anchor: the windows' packed rows of the same batches)
         self._file_rows = {}
         self._lock = threading.Lock()
 
-    def __call__(self, recs, res, sketch, kept):
+    def __call__(self, recs, res, sketch, kept, codes=None, keep=None):
         begin, end = windows(res, self.trimfirst, self.slide, self.maxlen, self.spec.span)
         with self._lock:
             self._pending[id(recs)] = (begin, end, sketch, kept)
+            if codes is not None:
+                self._pending_windows[id(recs)] = (codes, keep)
 
     def take(self, recs):
         """(begin, end, sketch, kept) of a batch the consumer has in hand."""
         with self._lock:
             return self._pending.pop(id(recs))
 
+    def take_windows(self, recs):
+        """(codes, keep) of the same batch, None without anchor."""
+        with self._lock:
+            return self._pending_windows.pop(id(recs), None)
+
     def add_file_rows(self, path, rows):
-        """The rows of one input file, in read order: (file, readID, tail, telo_length, begin, end, kept, sketch row) each."""
+        """The rows of one input file, in read order: (file, readID, tail, telo_length, begin, end, kept, sketch row) each -- with
+        anchor followed by (letters of the window, its codes row, its keep row), which anchor.run reads."""
         with self._lock:
             self._file_rows.setdefault(path, []).extend(rows)
 
@@ -166,7 +177,7 @@ class Collector:
             n_edges, best = edge_stats(n, links, matches)
         where = {i: p for p, i in enumerate(part)}
         read_rows = []
-        for i, (file, rid, tail, telo, b, e, kept, _row) in enumerate(rows):
+        for i, (file, rid, tail, telo, b, e, kept) in enumerate(r[:7] for r in rows):
             p = where.get(i)
             read_rows.append([file, rid, "forward" if tail == 0 else "reverse", telo, b, e, kept] +
                              ([0, 0, 0] if p is None else [int(end[p]), int(n_edges[p]), int(best[p])]))

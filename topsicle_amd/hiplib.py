@@ -23,7 +23,7 @@ FOLLOW_MAX_FWD, FOLLOW_WIDE_MAX_FWD, FOLLOW_HIST_MAX = 15, 32, 8      # k-mers t
 EXPORTS = [
     "tps_abi_version", "tps_device_count", "tps_ctx_create", "tps_ctx_destroy", "tps_last_error",
     "tps_set_patterns", "tps_set_patterns_wide", "tps_batch_upload", "tps_batch_upload_packed", "tps_batch_upload_nib4", "tps_batch_share", "tps_host_alloc", "tps_host_free",
-    "tps_batch_download_packed", "tps_batch_kmer_followers", "tps_batch_kmer_followers_wide", "tps_batch_motif_census", "tps_batch_variant_census", "tps_batch_tract_map", "tps_batch_end_sketch", "tps_sketch_links", "tps_batch_set_tails", "tps_batch_scan", "tps_sync",
+    "tps_batch_download_packed", "tps_batch_kmer_followers", "tps_batch_kmer_followers_wide", "tps_batch_motif_census", "tps_batch_variant_census", "tps_batch_tract_map", "tps_batch_end_sketch", "tps_sketch_links", "tps_batch_end_window", "tps_window_offsets", "tps_batch_set_tails", "tps_batch_scan", "tps_sync",
     "tps_batch_results", "tps_batch_window_offsets", "tps_batch_window_sums", "tps_batch_window_raw",
     "tps_batch_raw_to_fd", "tps_batch_trc_counts", "tps_trc_counts", "tps_window_counts", "tps_binseg_l2", "tps_binseg_l2_ties", "tps_batch_read_sums", "tps_window_count",
     "tps_kernel_time_ms", "tps_kernel_time_reset", "tps_device_info", "tps_batch_kernel_info", "tps_ctx_debug_option", "tps_debug_stamps_get",
@@ -66,6 +66,8 @@ TRACT_UNIT_RANGE, TRACT_BLOCK_RANGE, TRACT_GAP_RANGE, TRACT_MIN_BLOCKS_RANGE, TR
 # tps_batch_end_sketch: k, buckets, end - begin; tps_sketch_links: sketches, links kept per row
 ENDS_K_RANGE, ENDS_BUCKETS, ENDS_MAX_WINDOW, LINKS_MAX_N, LINKS_MAX_LINKS = (8, 16), (64, 128, 256, 512), 16384, 262144, 256
 ENDS_EMPTY = 0xFFFFFFFF           # an empty bucket of a sketch
+# tps_batch_end_window / tps_window_offsets: letters of a window, rows of one call
+ANCHOR_MAX_SPAN, ANCHOR_MAX_ROWS = 4096, 262144
 RES_TIE = 1            # TPS_RES_TIE: the exact tournament decided the change-point (candidates within float64 noise of each other)
 
 
@@ -113,6 +115,8 @@ def load_library(path: str | None = None) -> C.CDLL:
         "tps_batch_tract_map": (C.c_int, [vp, i32, C.c_uint64, i32, i32, i32, i32, i32, i32, vp, i64, vp, i64, vp, i64]),
         "tps_batch_end_sketch": (C.c_int, [vp, i32, C.c_uint64, i32, i32, i32, vp, vp, vp, i64, vp, i64, vp, i64]),
         "tps_sketch_links": (C.c_int, [vp, vp, i64, i32, i64, i32, i32, vp, i64, vp, i64, vp, i64]),
+        "tps_batch_end_window": (C.c_int, [vp, i32, C.c_uint64, i32, i32, vp, vp, vp, i64, i32, vp, i64, vp, i64]),
+        "tps_window_offsets": (C.c_int, [vp, vp, vp, vp, vp, i64, i32, i32, vp, vp, vp, i64]),
         "tps_batch_set_tails": (C.c_int, [vp, i32, vp]),
         "tps_batch_scan": (C.c_int, [vp, i32, C.POINTER(Params)]),
         "tps_sync": (C.c_int, [vp]),
@@ -527,6 +531,44 @@ class HipScanner:
         self._check(self.lib.tps_sketch_links(self._h, _ptr(sketch), n, b, sketch.size, min_match, max_links, _ptr(degree), degree.size,
                                               _ptr(links), n * max_links, _ptr(matches), n * max_links))
         return degree, links, matches
+
+    def end_window(self, slot: int, unit: str, tails, begin, end, k: int = 12, span: int = 2000):
+        """The kept window of every read of the resident batch, position by position (tps_batch_end_window; the rule is in
+        include/topsicle_hip.h): the window [begin, end) end_sketch hashes, as (codes uint32[n, (span + 15) // 16], keep
+        uint32[n, (span + 31) // 32]) -- 2-bit letters, 16 per dword, and one bit per position whose k-mer the sketch keeps.  No
+        window may be longer than span (k .. 4096).  No pattern table needed; the slot's scan outputs stay as they are."""
+        from . import variants
+        code, m = variants.unit_code(unit)
+        n = self._n[slot]
+        tails = np.ascontiguousarray(tails, dtype=np.uint8)
+        begin = np.ascontiguousarray(begin, dtype=np.int32)
+        end = np.ascontiguousarray(end, dtype=np.int32)
+        if not (len(tails) == len(begin) == len(end)):
+            raise TopsicleHipError("end_window: tails, begin and end must have one entry per read")
+        sp = span if 1 <= span <= ANCHOR_MAX_SPAN else 1                       # (a bad span is the library's to refuse)
+        codes = np.zeros((n, (sp + 15) // 16), dtype=np.uint32)
+        keep = np.zeros((n, (sp + 31) // 32), dtype=np.uint32)
+        self._check(self.lib.tps_batch_end_window(self._h, slot, code, m, k, _ptr(tails), _ptr(begin), _ptr(end), len(tails), span,
+                                                  _ptr(codes), codes.size, _ptr(keep), keep.size))
+        return codes, keep
+
+    def anchor_offsets(self, codes, keep, length, ref, span: int, k: int = 12):
+        """The offset of window i against window ref[i] by votes on their diagonals (tps_window_offsets): rows as end_window returns
+        them, length[i] letters each, ref[i] < 0 for a row without a reference: (offset int32[n], votes int32[n], second
+        int32[n]) -- the lower median of the best 128 diagonals in window coordinates, the votes there, and the best count two
+        coarse bins or more away.  Needs no resident batch."""
+        codes = np.ascontiguousarray(codes, dtype=np.uint32)
+        keep = np.ascontiguousarray(keep, dtype=np.uint32)
+        length = np.ascontiguousarray(length, dtype=np.int32)
+        ref = np.ascontiguousarray(ref, dtype=np.int32)
+        n = len(ref)
+        sp = span if 1 <= span <= ANCHOR_MAX_SPAN else 1
+        if codes.shape != (n, (sp + 15) // 16) or keep.shape != (n, (sp + 31) // 32) or len(length) != n:
+            raise TopsicleHipError("anchor_offsets: codes, keep, length and ref must hold one row of `span` letters per window")
+        offset, votes, second = (np.zeros(n, dtype=np.int32) for _ in range(3))
+        self._check(self.lib.tps_window_offsets(self._h, _ptr(codes), _ptr(keep), _ptr(length), _ptr(ref), n, span, k,
+                                                _ptr(offset), _ptr(votes), _ptr(second), n))
+        return offset, votes, second
 
     def set_tails(self, slot: int, tails: np.ndarray):
         tails = np.ascontiguousarray(tails, dtype=np.uint8)

@@ -20,7 +20,7 @@ from collections import defaultdict
 
 import numpy as np
 
-from . import allsteps, batch, ends, hiplib, motif, rawnpz, seqio, tracts, variants
+from . import allsteps, anchor, batch, ends, hiplib, motif, rawnpz, seqio, tracts, variants
 
 version_number = "1.0.0"
 Topsicle_output_prefix = "Topsicle"
@@ -245,6 +245,7 @@ def process_file_multi(args, seq_loc, phrases, engines):
                 idx = np.nonzero(res["pass"])[0]
                 vout = vcols[n].take(pb) if vcols[n] is not None else None
                 eout = ecols[n].take(pb) if ecols[n] is not None else None
+                ewin = ecols[n].take_windows(pb) if ecols[n] is not None else None          # (--anchor: the windows themselves)
                 if wthread is not None and len(idx) and n == writer_k:
                     write_passing(pb, idx)                                   # every passing record (main.py:83-86)
                 ids = [pb.read_id(int(i)) for i in idx]
@@ -270,8 +271,12 @@ def process_file_multi(args, seq_loc, phrases, engines):
                                  for j in np.nonzero(telolen != 0)[0]]
                 if eout is not None:                                         # one row per read with a stored boundary
                     e_begin, e_end, e_sketch, e_kept = eout
-                    erows[n] += [(file_name, ids[j], int(r["tail"][j]), telo_l[j], int(e_begin[idx[j]]), int(e_end[idx[j]]), int(e_kept[idx[j]]),
-                                  e_sketch[idx[j]].copy()) for j in np.nonzero(telolen != 0)[0]]
+                    stored = np.nonzero(telolen != 0)[0]
+                    new = [(file_name, ids[j], int(r["tail"][j]), telo_l[j], int(e_begin[idx[j]]), int(e_end[idx[j]]), int(e_kept[idx[j]]),
+                            e_sketch[idx[j]].copy()) for j in stored]
+                    if ewin is not None:                                     # the letters the window really has: end clamped to the read
+                        new = [row + (max(0, min(row[5], int(lens[j])) - row[4]), ewin[0][idx[j]].copy(), ewin[1][idx[j]].copy()) for row, j in zip(new, stored)]
+                    erows[n] += new
                 if n == 0:
                     with _CSV_LOCK, open(csv_path, mode="a", newline="") as fh:
                         csv.writer(fh).writerows(zip([file_name] * len(ids), [telo_phrase] * len(ids), ["%.3f" % t for t in trc_l], ids, telo_l))
@@ -367,6 +372,11 @@ def analysis_run(args, engines=None, engine_factory=None, wait_plots=True):
         if why is not None:
             tprint(f"--ends needs {why}")
             sys.exit(2)
+    if getattr(args, "anchor", False):
+        why = anchor.check(getattr(args, "ends", False), args.endspan, args.anchorminvotes, args.anchorratio)
+        if why is not None:
+            tprint(f"--anchor needs {why}")
+            sys.exit(2)
     if args.pattern.strip().lower() == "auto":
         # the motif comes from the reads (motif.py); from here on the run is the one `--pattern <that motif>` would have been
         if engines is None:
@@ -443,7 +453,8 @@ def analysis_run(args, engines=None, engine_factory=None, wait_plots=True):
         if unit != args.pattern.upper():
             tprint(f"--ends: {args.pattern} is a power of {unit}; k-mers with words of {unit} are left out of the sketches")
         args.end_collectors = [ends.Collector(unit, args.endk, args.endbuckets, args.endspan, args.endminmatch, args.endminkmers, args.endminreads,
-                                              args.trimfirst, slide, args.maxlengthtelo) for _k, _pattern, slide in phrases]
+                                              args.trimfirst, slide, args.maxlengthtelo, anchor=bool(getattr(args, "anchor", False)))
+                               for _k, _pattern, slide in phrases]
 
     args.tract_collector = None
     if getattr(args, "tracts", False):
@@ -508,6 +519,15 @@ def analysis_run(args, engines=None, engine_factory=None, wait_plots=True):
         tprint(f"end groups (k = {telo_phrase}): {args.outputDir}/end_reads_{telo_phrase}.csv, {args.outputDir}/ends_{telo_phrase}.csv")
         for line in ends.summary(col, stats):
             tprint(line)
+        if col.spec.anchor:
+            # one boundary per group: every grouped read's window against its group's reference, one call per k
+            a_reads, a_groups, a_stats = anchor.run(col.rows_in_order(filenames), read_rows, engines[0], col.spec.k, col.spec.span,
+                                                    args.anchorminvotes, args.anchorratio)
+            ends.write_csv(f"{args.outputDir}/anchored_reads_{telo_phrase}.csv", anchor.READ_HEADER, a_reads)
+            ends.write_csv(f"{args.outputDir}/anchored_ends_{telo_phrase}.csv", anchor.GROUP_HEADER, a_groups)
+            tprint(f"anchored lengths (k = {telo_phrase}): {args.outputDir}/anchored_reads_{telo_phrase}.csv, {args.outputDir}/anchored_ends_{telo_phrase}.csv")
+            for line in anchor.summary(a_stats, args.anchorminvotes, args.anchorratio):
+                tprint(line)
 
     if args.tract_collector is not None:
         tcol = args.tract_collector
@@ -674,6 +694,11 @@ def build_parser():
     parser.add_argument("--endminmatch", metavar="INT", type=int, default=ends.DEFAULT_MIN_MATCH, help="--ends: equal buckets that link two reads (1..endbuckets)")
     parser.add_argument("--endminkmers", metavar="INT", type=int, default=ends.DEFAULT_MIN_KMERS, help="--ends: subtelomere k-mers a read needs to take part")
     parser.add_argument("--endminreads", metavar="INT", type=int, default=ends.DEFAULT_MIN_READS, help="--ends: reads a group needs to be reported as an end")
+    parser.add_argument("--anchor", action="store_true",
+                        help="MI355X build, with --ends: place the reads of every end group on their group's reference read, agree on one boundary per "
+                             "group and measure every read's telomere to it (anchored_reads_{k}.csv, anchored_ends_{k}.csv); needs --endspan of at most 4096")
+    parser.add_argument("--anchorminvotes", metavar="INT", type=int, default=anchor.DEFAULT_MIN_VOTES, help="--anchor: k-mer votes a read needs on its best diagonals to be anchored")
+    parser.add_argument("--anchorratio", metavar="INT", type=int, default=anchor.DEFAULT_RATIO, help="--anchor: ... and how many times the votes of the runner-up diagonals")
     parser.add_argument("--tracts", action="store_true",
                         help="MI355X build: map the telomere-repeat tracts of every WHOLE read, on both strands -- one row per tract (tracts.csv) and one per "
                              "read with a tract and its class: fusion, both_ends, interstitial, terminal (tract_reads.csv).  Runs the files as --twopass off")
