@@ -198,12 +198,22 @@ int  tps_batch_set_tails(tps_ctx* ctx, int32_t slot, const uint8_t* tails);
 int  tps_batch_scan(tps_ctx* ctx, int32_t slot, const tps_params* prm);
 /* Wait for everything enqueued on the context's stream. */
 int  tps_sync(tps_ctx* ctx);
-/* Copy the per-read results of the last scan of `slot` (after tps_sync). */
+/* Copy the per-read results of the last scan of `slot` (after tps_sync).  Every field of every read is written by every scan,
+ * whether the read passes or not: a read that does not pass has n_win = 0, bkp = -1, gain = 0 and flags = 0. */
 int  tps_batch_results(tps_ctx* ctx, int32_t slot, tps_read_result* out, int64_t n_reads);
 /* Window layout of the last scan: win_off[n+1] (prefix of n_win over ALL reads of the batch,
  * scanned or not, computed from lengths and params only). */
 int  tps_batch_window_offsets(tps_ctx* ctx, int32_t slot, int64_t* win_off, int64_t n_plus_1);
-/* Download S_w (needs TPS_F_STORE_SUMS) / c'_p (needs TPS_F_STORE_RAW) of the last scan. */
+/* Reads that do not pass.  The window layout reserves the windows of EVERY read, and the scan kernels store S_w and c'_p only
+ * for the reads that pass: `pass` = 1 in the last scan's results, decided by step 1 (TPS_F_STEP1: longer than min_len and the
+ * better head count above min_count) or taken from tps_batch_set_tails (TPS_F_TAILS_IN: bit 1 set = skip).  For a read whose
+ * `pass` is 0, tps_batch_window_sums, tps_batch_window_raw and tps_batch_read_sums return ZEROS for all of its windows, and
+ * tps_batch_raw_to_fd writes zero rows for it (its CRC covers those zeros); tps_window_counts follows the same rule for the reads
+ * its `tails` mark as skipped.  The library clears those ranges on the host after the copy (tps::clear_skipped_windows,
+ * csrc/tps_plan.h), from the slot's own results: the scan launch itself clears nothing.  What these calls return therefore never
+ * depends on what the device buffers held before. */
+/* Download S_w (needs TPS_F_STORE_SUMS) / c'_p (needs TPS_F_STORE_RAW) of the last scan; zeros for the windows of reads that do
+ * not pass (above). */
 int  tps_batch_window_sums(tps_ctx* ctx, int32_t slot, int32_t* sums, int64_t n_windows);
 int  tps_batch_window_raw(tps_ctx* ctx, int32_t slot, uint8_t* raw, int64_t n_windows_times_p);
 /* c'_p of SELECTED reads of the last scan (needs TPS_F_STORE_RAW) straight to a file (ABI 4): the rows of reads[0 .. n_sel)
@@ -213,13 +223,16 @@ int  tps_batch_window_raw(tps_ctx* ctx, int32_t slot, uint8_t* raw, int64_t n_wi
  * NULL; e.g. libtopsicle_io.so's tps_crc32) is run over the bytes in file order, starting from 0: *crc_out (may be NULL) is the
  * CRC-32 of exactly what was written, *bytes_out its length -- a caller that lays the blocks of many batches into one zip / npy
  * member joins the per-block values with crc32_combine.  Replaces, for the columnar raw-count output, the per-read
- * DataFrame.to_csv of the reference (Topsicle/main.py:146-150; Topsicle/allsteps.py:398-411 builds the rows). */
+ * DataFrame.to_csv of the reference (Topsicle/main.py:146-150; Topsicle/allsteps.py:398-411 builds the rows).  A selected read
+ * that does not pass gets n_win x P zero bytes ("Reads that do not pass" above), and the CRC covers them. */
 typedef uint32_t (*tps_crc32_fn)(uint32_t crc, const uint8_t* p, int64_t n);
 int  tps_batch_raw_to_fd(tps_ctx* ctx, int32_t slot, const int64_t* reads, int64_t n_sel, int fd, int64_t file_off,
                          tps_crc32_fn crc_fn, uint32_t* crc_out, int64_t* bytes_out);
-/* S_w of ONE read of the last scan (any scan with TPS_F_WINDOWS; n_windows = the read's n_win). */
+/* S_w of ONE read of the last scan (any scan with TPS_F_WINDOWS; n_windows = the read's windows in the layout); zeros for a read
+ * that does not pass ("Reads that do not pass" above). */
 int  tps_batch_read_sums(tps_ctx* ctx, int32_t slot, int64_t read, int32_t* sums, int64_t n_windows);
-/* Step-1 per-pattern counts of the last scan: c_start[n*P], c_end[n*P] (int32). */
+/* Step-1 per-pattern counts of the last scan: c_start[n*P], c_end[n*P] (int32).  Every count of every read is written by every
+ * scan that runs step 1, whether the read passes or not (a read shorter than k letters counts zero everywhere). */
 int  tps_batch_trc_counts(tps_ctx* ctx, int32_t slot, int32_t* c_start, int32_t* c_end, int64_t n_reads);
 
 /* ---- one-shot host-pointer calls (parity tests, per-read API) -------------------------- */
@@ -229,7 +242,8 @@ int  tps_trc_counts(tps_ctx* ctx, const uint8_t* bases, const int64_t* offsets, 
                     int32_t no_bp, int32_t* c_start, int32_t* c_end);
 /* bound_detect / rawCountPattern window loops (allsteps.py:275-291, 398-411) for the given
  * tail per read.  win_off[n+1] must be the prefix of tps_window_count() over the reads.
- * sums: int32[win_off[n]]; raw: u8[win_off[n]*P] or NULL. */
+ * sums: int32[win_off[n]]; raw: u8[win_off[n]*P] or NULL.  tails[i]: bit 0 = the tail, bit 1 = skip the read -- the windows of
+ * a skipped read come back as zeros in sums and raw ("Reads that do not pass" above). */
 int  tps_window_counts(tps_ctx* ctx, const uint8_t* bases, const int64_t* offsets,
                        const uint8_t* tails, int64_t n_reads, int32_t window, int32_t slide,
                        int32_t trimfirst, int32_t maxlen, const int64_t* win_off,
@@ -431,7 +445,11 @@ int  tps_kernel_time_reset(tps_ctx* ctx);
  * (per-read phase clocks; only a -DTPS_STAMPS build writes them), "file_order" (wave slot i takes read i: switches
  * tps::plan_dispatch_order off, which otherwise starts the longest reads of a batch first), "no_stride" (a slide that is a multiple of a
  * fused kernel's slide keeps the generic kernel instead of running that kernel and keeping every m-th window: tps::stride_base), "no_inline_rows" (such a scan at twice the base
- * slide copies its raw rows like the other multiples instead of letting the tiles store every second row: ScanArgs::raw_m).  topsicle_amd.hiplib applies $TOPSICLE_HIP_DEBUG
+ * slide copies its raw rows like the other multiples instead of letting the tiles store every second row: ScanArgs::raw_m), "poison"
+ * (tests only; 0 = off, 1 .. 255 = a fill byte: while it is on, every call fills every device buffer it is about to use as output or
+ * scratch with that byte, over the buffer's whole capacity and on the context's stream, ahead of its own clearing memsets and of the
+ * launch, and the slot's mapped pinned result array likewise; buffers borrowed from another context or scan and inputs copied from the
+ * host are never filled.  Two runs with different bytes differ exactly where nobody wrote what the call hands out).  topsicle_amd.hiplib applies $TOPSICLE_HIP_DEBUG
  * ("key=value,key=value") to every context it creates: the ONE documented variable of the Python host. */
 int  tps_ctx_debug_option(tps_ctx* ctx, const char* key, int64_t value);
 /* The stamps of the last scan of `slot`: 16 uint64 per read. */

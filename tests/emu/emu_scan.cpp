@@ -159,10 +159,10 @@ extern "C" int emu_scan(const char* pats, int P, int k, const uint8_t* bases, co
         }
 #undef EMU_CASE
     }
-    if (a.variant && sums)
-        for (int64_t i = 0; i < n; ++i)
-            for (int64_t w = 0; w < win_off[(size_t)i + 1] - win_off[(size_t)i]; ++w)
-                sums[win_off[(size_t)i] + w] = (int32_t)sums16[(size_t)(win_off16[(size_t)i] + w)];
+    // the library's downloads: widen the 16-bit sums, then zeros for the windows of the reads that do not pass (tps_plan.h)
+    if (a.variant && sums) tps::widen_sums16(sums16.data(), win_off16.data(), win_off.data(), 0, n, sums);
+    if (sums) tps::clear_skipped_windows(results, win_off.data(), n, 1, 4, 0, win_off[(size_t)n], sums);
+    if (a.raw && g_raw_m != 2) tps::clear_skipped_windows(results, win_off.data(), n, P, 1, 0, win_off[(size_t)n] * P, raw);
     return TPS_OK;
 }
 

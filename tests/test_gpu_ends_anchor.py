@@ -1,12 +1,7 @@
 """Anchored lengths on the GPU (tps_batch_end_window, tps_window_offsets; HipScanner.end_window, HipScanner.anchor_offsets), through
 the C ABI: equal to the plain restatement of the rules on the cases the emulation is checked on (tests/anchor_cases.py); independent
 of the pattern table and of the scans around it; the same from launch to launch; one refusal per error the header lists; and
-`--ends --anchor` end to end on the planted-end detection set.
-
-(The file's name puts it behind tests/test_gpu_bam.py.  That module's test_nib4_scan_equals_packed_scan compares the window sums of two
-slots including those of reads that do not pass -- bytes no kernel writes -- and holds only while the process's device memory is still
-fresh: run behind ANY module that has used the GPU, tests/test_gpu_ends.py for one, it fails.  As the first GPU module of a session it
-passes, and so it stays the first.)"""
+`--ends --anchor` end to end on the planted-end detection set."""
 import ctypes as C
 import os
 

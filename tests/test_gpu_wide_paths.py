@@ -61,7 +61,8 @@ def gpu_scan(sc, slot, row, reads, prm, tails=None, file_order=0, times=1):
 
 
 def same_outputs(a, b, tag):
-    """Byte identity of two scans of one batch (the window regions of reads that do not pass are never written)."""
+    """Byte identity of two scans of one batch.  (The mask is from before the downloads handed out zeros for reads that do not
+    pass; tests/test_gpu_poison.py compares these rows unmasked.)"""
     assert a["results"].tobytes() == b["results"].tobytes(), (tag, "results")
     assert np.array_equal(a["win_off"], b["win_off"]), tag
     for key in ("c_start", "c_end"):

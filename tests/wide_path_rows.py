@@ -441,6 +441,11 @@ def check_scan(out, row, reads, prm, tails=None):
         assert r["tail"] == tail and r["pass"] == int(passes), where + ("tail / pass",)
         if not passes or not (prm.flags & hiplib.F_WINDOWS):
             assert r["n_win"] == 0 and r["bkp"] == -1, where
+            # no kernel writes the windows of a read that does not pass: they are handed out as zeros (include/topsicle_hip.h)
+            if "sums" in out:
+                assert not out["sums"][want_off[i]:want_off[i + 1]].any(), where + ("S_w of a read that does not pass",)
+            if row.raw and "raw" in out:
+                assert not out["raw"][want_off[i]:want_off[i + 1]].any(), where + ("raw rows of a read that does not pass",)
             continue
         assert r["n_win"] == nw[i], where
         sums, raw = windows_of(row, seq, tail)

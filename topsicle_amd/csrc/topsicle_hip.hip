@@ -447,6 +447,7 @@ struct tps_ctx {
     int no_inline_rows = 0;           // tps_ctx_debug_option "no_inline_rows": strided scans at twice the base slide copy their raw rows like the others (A/B of ScanArgs::raw_m)
     int no_stride = 0;                // tps_ctx_debug_option "no_stride": slides that are a multiple of a fused kernel's keep the generic kernel (A/B of tps::stride_base)
     int file_order = 0;               // tps_ctx_debug_option "file_order": wave slot i takes read i whatever the reads' lengths (A/B of tps::plan_dispatch_order)
+    int poison = 0;                   // tps_ctx_debug_option "poison": 1..255 = every call fills the output and scratch buffers it is about to use with this byte (tests: a byte nobody writes shows)
     int event_stride = 1;             // time every event_stride-th launch (tps_ctx_debug_option "event_stride"): timing costs ~3.5 us per launch
     uint64_t launch_seq = 0;
     size_t lds_set_generic = 0;      // hipFuncAttributeMaxDynamicSharedMemorySize as last raised, per scan kernel
@@ -466,6 +467,19 @@ int bind(tps_ctx* c) {
 }
 
 using tps::window_count;
+
+// Debug option "poison" (include/topsicle_hip.h): fills a device buffer this call is about to use as output or scratch, over its whole
+// capacity, on the context's stream -- ahead of the library's own clearing memsets and of the launch.  A borrowed buffer is another
+// context's (or another scan's) to fill, never this one's.  Call sites test c->poison themselves: one not-taken branch when it is off.
+int poison_fill(tps_ctx* c, DevBuf& b) {
+    if (b.borrowed || !b.p || !b.cap) return TPS_OK;
+    HIP_TRY(hipMemsetAsync(b.p, c->poison, b.cap, c->stream));
+    return TPS_OK;
+}
+#define TPS_POISON(buf)                                             \
+    do {                                                            \
+        if (c->poison && (rc = poison_fill(c, (buf)))) return rc;   \
+    } while (0)
 
 // LDS one workgroup may use, in dwords: what the device reports, at most gfx950's 160 KB; 64 KB where it reports nothing
 int64_t lds_budget_dw(const tps_ctx* c) {
@@ -519,11 +533,14 @@ void reset_slot(Slot& sl, int64_t n, int64_t n_words) {
     sl.scanned = false;
 }
 
-int ensure_packed(Slot& sl, int64_t n, int64_t n_words) {
+int ensure_packed(tps_ctx* c, Slot& sl, int64_t n, int64_t n_words) {
     int rc;
     if ((rc = sl.seq2.ensure((size_t)std::max<int64_t>(n_words, 4) * 4))) return rc;
     if ((rc = sl.inv.ensure((size_t)std::max<int64_t>(n_words, 4) * 2))) return rc;
     if ((rc = sl.desc.ensure((size_t)std::max<int64_t>(n, 1) * sizeof(tps_read_desc)))) return rc;
+    TPS_POISON(sl.seq2);          // (ahead of the copies and of the pack / expand kernel that write them)
+    TPS_POISON(sl.inv);
+    TPS_POISON(sl.desc);
     return TPS_OK;
 }
 
@@ -544,6 +561,15 @@ int ensure_h_results(Slot& sl, int64_t n) {
     size_t want = (size_t)n + (size_t)n / 8 + 16;
     HIP_TRY(hipHostMalloc((void**)&sl.h_results, want * sizeof(tps_read_result), hipHostMallocMapped));
     sl.h_results_cap = want;
+    return TPS_OK;
+}
+
+// option "poison" for the mapped pinned result array: filled by the host once the stream has drained, so the fill is ordered behind
+// whatever the stream still wrote there and ahead of the launch that follows
+int poison_h_results(tps_ctx* c, Slot& sl) {
+    if (!sl.h_results) return TPS_OK;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    memset(sl.h_results, c->poison, sl.h_results_cap * sizeof(tps_read_result));
     return TPS_OK;
 }
 
@@ -582,7 +608,7 @@ int do_upload(tps_ctx* c, Slot& sl, const uint8_t* bases, const int64_t* offsets
     c->h_desc.resize((size_t)std::max<int64_t>(n, 1));
     const int64_t n_words = tps::pack_layout(offsets, n, c->h_desc.data());
     int rc;
-    if ((rc = ensure_packed(sl, n, n_words))) return rc;
+    if ((rc = ensure_packed(c, sl, n, n_words))) return rc;
     if ((rc = c->ascii.ensure((size_t)(total + 2 * PAD + 32)))) return rc;
     if ((rc = c->ascii_off.ensure((size_t)(n + 1) * 8))) return rc;
     uint8_t* d = (uint8_t*)c->ascii.p;
@@ -621,7 +647,7 @@ int do_upload_packed(tps_ctx* c, Slot& sl, const uint32_t* seq2, const uint16_t*
     }
     sl.h_offsets[(size_t)n] = acc;
     if (flagged && !inv) return fail(TPS_E_ARG, "a read is flagged TPS_RD_HAS_INVALID but inv is NULL");
-    if ((rc = ensure_packed(sl, n, n_words))) return rc;
+    if ((rc = ensure_packed(c, sl, n, n_words))) return rc;
     if (n_words) HIP_TRY(hipMemcpyAsync(sl.seq2.p, seq2, (size_t)n_words * 4, hipMemcpyHostToDevice, c->stream));
     if (n_words && inv) HIP_TRY(hipMemcpyAsync(sl.inv.p, inv, (size_t)n_words * 2, hipMemcpyHostToDevice, c->stream));
     if (n) HIP_TRY(hipMemcpyAsync(sl.desc.p, desc, (size_t)n * sizeof(tps_read_desc), hipMemcpyHostToDevice, c->stream));
@@ -654,7 +680,7 @@ int do_upload_nib4(tps_ctx* c, Slot& sl, const uint8_t* nib, int64_t nib_bytes, 
         flagged = flagged || (d.flags & TPS_RD_HAS_INVALID);
     }
     sl.h_offsets[(size_t)n] = acc;
-    if ((rc = ensure_packed(sl, n, n_words))) return rc;
+    if ((rc = ensure_packed(c, sl, n, n_words))) return rc;
     if ((rc = c->nib.ensure((size_t)std::max<int64_t>(nib_bytes, 16)))) return rc;
     if ((rc = c->nib_src.ensure((size_t)std::max<int64_t>(n, 1) * sizeof(tps_nib_src)))) return rc;
     if (nib_bytes) HIP_TRY(hipMemcpyAsync(c->nib.p, nib, (size_t)nib_bytes, hipMemcpyHostToDevice, c->stream));
@@ -817,6 +843,12 @@ int do_scan_wide(tps_ctx* c, Slot& sl, const tps_params& prm) {
     a.n_reads = n;
     a.prm = prm;
     if (n == 0) { sl.scanned = true; return TPS_OK; }
+    if (c->poison) {
+        if ((rc = poison_h_results(c, sl))) return rc;
+        if (a.c_start) { TPS_POISON(sl.c_start); TPS_POISON(sl.c_end); }
+        if (a.sums) TPS_POISON(sl.sums);
+        if (a.raw) TPS_POISON(sl.raw);
+    }
     if (sl.lds_bytes > c->lds_set_wide) {
         HIP_TRY(hipFuncSetAttribute((const void*)tps_scan_kernel_wide, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sl.lds_bytes));
         c->lds_set_wide = sl.lds_bytes;
@@ -931,9 +963,20 @@ int do_scan(tps_ctx* c, Slot& sl, const tps_params& prm, bool inner, hipEvent_t 
         if ((rc = sl.lc.ensure((size_t)std::max<int64_t>(n, 1) * (size_t)a.lc_stride * 2))) return rc;
         a.lc_scratch = (uint16_t*)sl.lc.p;
     }
+    if (c->poison) {
+        // everything this scan writes or uses as scratch; borrowed buffers (a strided scan's base counts) and the rows an inner scan
+        // stores into the requesting scan's layout (ext_raw: that scan filled its own buffer before it came here) are left alone
+        if (inner) TPS_POISON(sl.results);
+        else if ((rc = poison_h_results(c, sl))) return rc;
+        if (a.c_start) { TPS_POISON(sl.c_start); TPS_POISON(sl.c_end); }
+        if (a.sums || a.sums16) TPS_POISON(sl.sums);
+        if (a.raw && !sl.rows_inline) TPS_POISON(sl.raw);
+        if (a.lc_scratch) TPS_POISON(sl.lc);
+    }
     a.stamps = nullptr;
     if (c->want_stamps) {
         if ((rc = sl.stamps.ensure((size_t)std::max<int64_t>(n, 1) * 16 * 8))) return rc;
+        TPS_POISON(sl.stamps);
         HIP_TRY(hipMemsetAsync(sl.stamps.p, 0, (size_t)std::max<int64_t>(n, 1) * 16 * 8, c->stream));
         a.stamps = (uint64_t*)sl.stamps.p;
     }
@@ -1290,6 +1333,8 @@ int tps_batch_kmer_followers(tps_ctx* c, int32_t slot, int32_t n_fwd, int32_t fo
     // scratch: the slot's raw / sums buffers are not touched; picks and counters get buffers of their own in the context
     if ((rc = c->follow_picks.ensure((size_t)want * 4))) return rc;
     if ((rc = c->follow_hist.ensure((size_t)2 * n_fwd * nbins * 8))) return rc;
+    TPS_POISON(c->follow_picks);
+    TPS_POISON(c->follow_hist);
     HIP_TRY(hipMemsetAsync(c->follow_picks.p, 0, (size_t)want * 4, c->stream));
     HIP_TRY(hipMemsetAsync(c->follow_hist.p, 0, (size_t)2 * n_fwd * nbins * 8, c->stream));
     tps::FollowArgs a{};
@@ -1338,9 +1383,11 @@ int tps_batch_kmer_followers_wide(tps_ctx* c, int32_t slot, int32_t n_fwd, int32
     if (hist && hist_len != 2ll * n_fwd * nbins) return fail(TPS_E_ARG, "hist must hold %lld counters", 2ll * n_fwd * nbins);
     if (n == 0) { if (hist) memset(hist, 0, (size_t)hist_len * 8); return TPS_OK; }
     if ((rc = c->follow_picks.ensure((size_t)want * 4))) return rc;
+    TPS_POISON(c->follow_picks);
     HIP_TRY(hipMemsetAsync(c->follow_picks.p, 0, (size_t)want * 4, c->stream));
     if (hist) {
         if ((rc = c->follow_hist.ensure((size_t)hist_len * 8))) return rc;
+        TPS_POISON(c->follow_hist);
         HIP_TRY(hipMemsetAsync(c->follow_hist.p, 0, (size_t)hist_len * 8, c->stream));
     }
     tps::FollowWideArgs a{};
@@ -1378,9 +1425,11 @@ int tps_batch_motif_census(tps_ctx* c, int32_t slot, int32_t u_min, int32_t u_ma
     // (the table, the slot's scan outputs and its plan are not touched: a scan before and after the census gives the same results)
     const size_t hit_bytes = (size_t)n * 2 * sizeof(tps_motif_hit), cnt_bytes = (size_t)n * 2 * nu * 4;
     if ((rc = c->motif_hits.ensure(hit_bytes))) return rc;
+    TPS_POISON(c->motif_hits);
     HIP_TRY(hipMemsetAsync(c->motif_hits.p, 0, hit_bytes, c->stream));
     if (counts) {
         if ((rc = c->motif_counts.ensure(cnt_bytes))) return rc;
+        TPS_POISON(c->motif_counts);
         HIP_TRY(hipMemsetAsync(c->motif_counts.p, 0, cnt_bytes, c->stream));
     }
     tps::MotifArgs a{};
@@ -1432,12 +1481,14 @@ int tps_batch_variant_census(tps_ctx* c, int32_t slot, uint64_t unit, int32_t m,
     const size_t off_begin = (((size_t)n + 15) & ~(size_t)15), off_end = off_begin + (size_t)n * 4;
     if ((rc = c->variant_in.ensure(off_end + (size_t)n * 4))) return rc;
     if ((rc = c->variant_counts.ensure(cnt_bytes))) return rc;
+    TPS_POISON(c->variant_counts);
     HIP_TRY(hipMemcpyAsync(c->variant_in.p, tails, (size_t)n, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync((char*)c->variant_in.p + off_begin, begin, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync((char*)c->variant_in.p + off_end, end, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemsetAsync(c->variant_counts.p, 0, cnt_bytes, c->stream));
     if (profile) {
         if ((rc = c->variant_prof.ensure(prof_bytes))) return rc;
+        TPS_POISON(c->variant_prof);
         HIP_TRY(hipMemsetAsync(c->variant_prof.p, 0, prof_bytes, c->stream));
     }
     tps::VariantArgs a{};
@@ -1487,6 +1538,7 @@ int tps_batch_tract_map(tps_ctx* c, int32_t slot, uint64_t unit, int32_t m, int3
     const size_t tab_bytes = table.size() * 4, tr_bytes = (size_t)n * 2 * max_tracts * sizeof(tps_tract), fo_bytes = (size_t)n * 2 * 4, to_bytes = (size_t)n * 4 * 4;
     if ((rc = c->tract_table.ensure(tab_bytes))) return rc;
     if ((rc = c->tract_out.ensure(tr_bytes + fo_bytes + to_bytes))) return rc;
+    TPS_POISON(c->tract_out);
     HIP_TRY(hipMemcpyAsync(c->tract_table.p, table.data(), tab_bytes, hipMemcpyHostToDevice, c->stream));      // (pageable: the copy has left `table` when the call returns)
     HIP_TRY(hipMemsetAsync(c->tract_out.p, 0, tr_bytes + fo_bytes + to_bytes, c->stream));
     tps::TractArgs a{};
@@ -1534,6 +1586,7 @@ int tps_batch_end_sketch(tps_ctx* c, int32_t slot, uint64_t unit, int32_t m, int
     if ((rc = c->tract_table.ensure(tab_bytes))) return rc;
     if ((rc = c->ends_in.ensure(off_end + (size_t)n * 4))) return rc;
     if ((rc = c->ends_out.ensure(sk_bytes + kp_bytes))) return rc;
+    TPS_POISON(c->ends_out);
     HIP_TRY(hipMemcpyAsync(c->tract_table.p, table.data(), tab_bytes, hipMemcpyHostToDevice, c->stream));      // (pageable: the copy has left `table` when the call returns)
     HIP_TRY(hipMemcpyAsync(c->ends_in.p, tails, (size_t)n, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync((char*)c->ends_in.p + off_begin, begin, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
@@ -1571,6 +1624,7 @@ int tps_sketch_links(tps_ctx* c, const uint32_t* sketch, int64_t n, int32_t buck
     const size_t t_bytes = t.size() * 4, dg_bytes = (size_t)n * 4, ln_bytes = (size_t)n * max_links * 4;
     if ((rc = c->links_t.ensure(t_bytes))) return rc;
     if ((rc = c->links_out.ensure(dg_bytes + 2 * ln_bytes))) return rc;
+    TPS_POISON(c->links_out);
     HIP_TRY(hipMemcpyAsync(c->links_t.p, t.data(), t_bytes, hipMemcpyHostToDevice, c->stream));      // (pageable: the copy has left `t` when the call returns)
     tps::LinkArgs a{};
     a.t = (const uint32_t*)c->links_t.p;
@@ -1619,6 +1673,7 @@ int tps_batch_end_window(tps_ctx* c, int32_t slot, uint64_t unit, int32_t m, int
     if ((rc = c->tract_table.ensure(tab_bytes))) return rc;
     if ((rc = c->ends_in.ensure(off_end + (size_t)n * 4))) return rc;
     if ((rc = c->window_out.ensure(co_bytes + kp_bytes))) return rc;
+    TPS_POISON(c->window_out);
     HIP_TRY(hipMemcpyAsync(c->tract_table.p, table.data(), tab_bytes, hipMemcpyHostToDevice, c->stream));      // (pageable: the copy has left `table` when the call returns)
     HIP_TRY(hipMemcpyAsync(c->ends_in.p, tails, (size_t)n, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync((char*)c->ends_in.p + off_begin, begin, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
@@ -1657,6 +1712,7 @@ int tps_window_offsets(tps_ctx* c, const uint32_t* codes, const uint32_t* keep, 
     const size_t co_bytes = (size_t)n * cdw * 4, kp_bytes = (size_t)n * kdw * 4, n_bytes = (size_t)n * 4;
     if ((rc = c->offsets_in.ensure(co_bytes + kp_bytes + 2 * n_bytes))) return rc;
     if ((rc = c->offsets_out.ensure(3 * n_bytes))) return rc;
+    TPS_POISON(c->offsets_out);
     char* in = (char*)c->offsets_in.p;
     HIP_TRY(hipMemcpyAsync(in, codes, co_bytes, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(in + co_bytes, keep, kp_bytes, hipMemcpyHostToDevice, c->stream));
@@ -1751,15 +1807,12 @@ int tps_batch_window_sums(tps_ctx* c, int32_t slot, int32_t* sums, int64_t nw) {
         const int64_t n16 = sl->lay.win_off16[(size_t)sl->n];
         sl->h_sums16.resize((size_t)n16);
         HIP_TRY(hipMemcpy(sl->h_sums16.data(), sl->sums.p, (size_t)n16 * 2, hipMemcpyDeviceToHost));
-        for (int64_t i = 0; i < sl->n; ++i) {
-            const uint16_t* src = sl->h_sums16.data() + sl->lay.win_off16[(size_t)i];
-            int32_t* dst = sums + sl->lay.win_off[(size_t)i];
-            const int64_t cnt = sl->lay.win_off[(size_t)i + 1] - sl->lay.win_off[(size_t)i];
-            for (int64_t w = 0; w < cnt; ++w) dst[w] = (int32_t)src[w];
-        }
+        tps::widen_sums16(sl->h_sums16.data(), sl->lay.win_off16.data(), sl->lay.win_off.data(), 0, sl->n, sums);
     } else if (nw) {
         HIP_TRY(hipMemcpy(sums, sl->sums.p, (size_t)nw * 4, hipMemcpyDeviceToHost));
     }
+    // (no kernel wrote the windows of the reads that do not pass: they are handed out as zeros)
+    tps::clear_skipped_windows(sl->h_results, sl->lay.win_off.data(), sl->n, 1, 4, 0, nw, sums);
     return TPS_OK;
 }
 
@@ -1779,6 +1832,7 @@ int tps_batch_read_sums(tps_ctx* c, int32_t slot, int64_t read, int32_t* sums, i
     } else {
         HIP_TRY(hipMemcpy(sums, (const int32_t*)sl->sums.p + lo, (size_t)nw * 4, hipMemcpyDeviceToHost));
     }
+    tps::clear_skipped_windows(sl->h_results, sl->lay.win_off.data(), sl->n, 1, 4, lo, lo + nw, sums);
     return TPS_OK;
 }
 
@@ -1790,6 +1844,7 @@ int tps_batch_window_raw(tps_ctx* c, int32_t slot, uint8_t* raw, int64_t nwp) {
     int64_t want = sl->lay.win_off[(size_t)sl->n] * sl->plan_p;
     if (nwp != want || (nwp > 0 && !raw)) return fail(TPS_E_ARG, "raw must hold %lld bytes", (long long)want);
     if (nwp) HIP_TRY(hipMemcpy(raw, sl->raw.p, (size_t)nwp, hipMemcpyDeviceToHost));
+    tps::clear_skipped_windows(sl->h_results, sl->lay.win_off.data(), sl->n, sl->plan_p, 1, 0, nwp, raw);
     return TPS_OK;
 }
 
@@ -1869,6 +1924,8 @@ int tps_batch_raw_to_fd(tps_ctx* c, int32_t slot, const int64_t* reads, int64_t 
         HIP_TRY(hipEventSynchronize(c->raw_ev[j & 1]));
         const Piece& pc = pieces[j];
         const uint8_t* base = (const uint8_t*)c->raw_stage[j & 1];
+        // (zero rows for the reads that do not pass, before the piece is checksummed and written)
+        tps::clear_skipped_windows(sl->h_results, sl->lay.win_off.data(), sl->n, P, 1, pc.lo, pc.hi, c->raw_stage[j & 1]);
         iov.clear();
         for (size_t r = pc.r0; r < pc.r1; ++r) {
             const uint8_t* p = base + (runs[r].lo - pc.lo);
@@ -1983,6 +2040,7 @@ int tps_binseg_l2_ties(tps_ctx* c, const int32_t* sums, const int64_t* win_off, 
     if ((rc = sl.sums.ensure((size_t)std::max<int64_t>(nw, 1) * 4))) return rc;
     if ((rc = sl.win_off.ensure((size_t)(n + 1) * 8))) return rc;
     if ((rc = sl.results.ensure((size_t)n * 17))) return rc;          // gain (8n), bkp (4n), tie (n): gain first for alignment
+    TPS_POISON(sl.results);
     sl.planned = false;                                                // the slot's plan buffers were overwritten
     sl.wplanned = false;
     sl.scanned = false;
@@ -2038,7 +2096,11 @@ int tps_ctx_debug_option(tps_ctx* c, const char* key, int64_t value) {
     else if (k == "file_order") c->file_order = value != 0;
     else if (k == "no_stride") c->no_stride = value != 0;
     else if (k == "no_inline_rows") c->no_inline_rows = value != 0;
-    else return fail(TPS_E_ARG, "unknown debug option '%s' (event_stride, no_events, force_generic, spans_per_tile, force_pair, so_order, wpg, stamps, file_order, no_stride, no_inline_rows)", key);
+    else if (k == "poison") {
+        if (value < 0 || value > 255) return fail(TPS_E_ARG, "poison must be 0 (off) or a fill byte 1..255");
+        c->poison = (int)value;
+    }
+    else return fail(TPS_E_ARG, "unknown debug option '%s' (event_stride, no_events, force_generic, spans_per_tile, force_pair, so_order, wpg, stamps, file_order, no_stride, no_inline_rows, poison)", key);
     drop_plans(c);
     return TPS_OK;
 }

@@ -5,6 +5,7 @@
 #include <cstdlib>
 #include <algorithm>
 #include <cstdint>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -84,6 +85,44 @@ inline void plan_batch_layout(const int64_t* offsets, int64_t n, const tps_param
     lay.win_off[(size_t)n] = acc;
     lay.win_off16[(size_t)n] = acc16;
     plan_dispatch_order(nwv.data(), longer.data(), n, lay.order);
+}
+
+// The fused kernels' 16-bit sums as downloaded (win_off16 layout, every read padded to sums16_slots) -> the callers' contiguous
+// int32 array (win_off layout), reads [r0, r1).  src16 points at slot win_off16[r0], dst at window win_off[r0].
+inline void widen_sums16(const uint16_t* src16, const int64_t* win_off16, const int64_t* win_off, int64_t r0, int64_t r1, int32_t* dst) {
+    for (int64_t i = r0; i < r1; ++i) {
+        const uint16_t* s = src16 + (win_off16[i] - win_off16[r0]);
+        int32_t* d = dst + (win_off[i] - win_off[r0]);
+        const int64_t cnt = win_off[i + 1] - win_off[i];
+        for (int64_t w = 0; w < cnt; ++w) d[w] = (int32_t)s[w];
+    }
+}
+
+// What a download hands out for bytes no kernel wrote (include/topsicle_hip.h, "Reads that do not pass"): the scan kernels store no
+// S_w and no raw row for a read whose `pass` is 0, the layout reserves its windows all the same, and the device buffer keeps whatever
+// it held.  `buf` is a downloaded piece of a per-window output: elements [lo, hi) of `unit` bytes each, read i owning elements
+// [win_off[i] * scale, win_off[i + 1] * scale) (S_w: scale 1, unit 4; raw rows: scale P, unit 1; the padded 16-bit layout: win_off16,
+// scale 1, unit 2).  Every element of the piece that belongs to a read with results[i].pass == 0 becomes zero; a piece may begin and
+// end inside a read.  Returns how many elements it cleared.
+inline int64_t clear_skipped_windows(const tps_read_result* results, const int64_t* win_off, int64_t n, int64_t scale, size_t unit,
+                                     int64_t lo, int64_t hi, void* buf) {
+    if (hi <= lo || n <= 0) return 0;
+    // the last read whose region starts at or before lo (reads without windows share their neighbour's start)
+    int64_t a = 0, b = n;
+    while (a < b) {
+        const int64_t mid = a + (b - a) / 2;
+        if (win_off[mid + 1] * scale <= lo) a = mid + 1; else b = mid;
+    }
+    int64_t cleared = 0;
+    for (int64_t i = a; i < n && win_off[i] * scale < hi; ++i) {
+        if (results[i].pass) continue;
+        const int64_t x = std::max(win_off[i] * scale, lo), y = std::min(win_off[i + 1] * scale, hi);
+        if (y > x) {
+            memset((char*)buf + (size_t)(x - lo) * unit, 0, (size_t)(y - x) * unit);
+            cleared += y - x;
+        }
+    }
+    return cleared;
 }
 
 inline int gcd_i(int a, int b) { while (b) { int t = a % b; a = b; b = t; } return a; }
