@@ -37,11 +37,12 @@ def _revcomp(s):
     return s[::-1].translate(str.maketrans("ACGTacgtNn", "TGCAtgcaNn"))
 
 
-def make_read(rng, motif, length, telomeric, noisy):
-    """A read of about `length` bases: a telomere tract (exact repeats from a random phase) followed by random sequence, as it is
-    or reverse-complemented; a few lower-case stretches and N's (the reference upper-cases and N never matches)."""
+def make_read(rng, motif, length, telomeric, noisy, tract_len=None):
+    """A read of about `length` bases: a telomere tract (exact repeats from a random phase; tract_len bases, or a sixth to a half of
+    the read) followed by random sequence, as it is or reverse-complemented; a few lower-case stretches and N's (the reference
+    upper-cases and N never matches)."""
     if telomeric:
-        t = int(rng.integers(max(300, length // 6), max(400, length // 2)))
+        t = int(rng.integers(max(300, length // 6), max(400, length // 2))) if tract_len is None else tract_len
         ph = int(rng.integers(0, len(motif)))
         tract = (motif * (t // len(motif) + 2))[ph:ph + t]
     else:
@@ -133,6 +134,30 @@ def make_case(seed):
     if "--read_check" not in argv and np.random.default_rng(seed ^ 0x7A3C).random() < 0.35:
         argv += ["--rawcountpattern"]
     return {"name": f"case{seed}", "files": files, "pre": pre, "argv": argv, "input": next(iter(files)) if single else "in", "exit": exit_code}
+
+
+LONG_SEEDS = (0, 1, 2, 3)
+
+
+def make_long_case(seed):
+    """A case beyond the default --maxlengthtelo: one file of 6 to 10 reads of 25 000 to 48 000 bases, telomeric on either strand,
+    --maxlengthtelo 30 000 or 45 000, --slide 6 or 10 (all four combinations over LONG_SEEDS), one case with --rawcountpattern.  Drawn
+    from a generator of its own: make_case(seed) and everything recorded from it stay as they are."""
+    rng = np.random.default_rng([0x10C6, seed])
+    motif = MOTIFS[int(rng.integers(0, len(MOTIFS)))]
+    maxlen = (30000, 45000)[seed % 2]
+    slide = (6, 10)[(seed // 2) % 2]
+    recs = []
+    for i in range(int(rng.integers(6, 11))):
+        length = int(rng.integers(25000, 48001))
+        tract = int(rng.integers(length // 3, length * 9 // 10))            # most tracts end beyond the default 20 000
+        recs.append((f"long{seed}_{i}", "", make_read(rng, motif, length, rng.random() < 0.85, rng.random() < 0.6, tract_len=tract)))
+    fmt = ("fastq", "fasta")[seed % 2]
+    files = {f"in/long_{seed}.{fmt}": file_text(rng, recs, fmt, wrap=80 if fmt == "fasta" else None)}
+    argv = ["--pattern", motif, "--minSeqLength", "9000", "--threads", "1", "--cutoff", "0.5", "--slide", str(slide), "--maxlengthtelo", str(maxlen)]
+    if seed == 2:
+        argv += ["--rawcountpattern"]
+    return {"name": f"long{seed}", "files": files, "pre": {}, "argv": argv, "input": next(iter(files)), "exit": None}
 
 
 def materialise(case, root):

@@ -15,6 +15,7 @@ Topsicle/allsteps.py unchanged through oracle/ref_import.py and records inputs +
   cli_<seed>.json      whole runs of the reference's main() on seeded inputs (oracle/cli_cases.py): flags, input files, and the
                        CSV rows / summary log lines / filtered files the run left behind   (main.py:52-154, 156-309)
   reference_runs.json  more runs of main() (outputs as digests) and of bound_detect, for tests/test_ref_cli_differential.py
+  reference_long_runs.json  runs of main() on reads of 25 000 to 48 000 bases with --maxlengthtelo raised (outputs as digests)
   demo_col0.fastq.gz, demo_telolengths_all.csv, demo_run_log.json
                        data files of the reference's demo (inputs / its only result goldens)
 
@@ -23,6 +24,7 @@ Boundaries come from the reference's bound_detect driven by the Binseg restateme
 
     python oracle/gen_golden.py                      # rewrites tests/golden/
     python oracle/gen_golden.py reference_runs       # rewrites tests/golden/reference_runs.json only
+    python oracle/gen_golden.py reference_long_runs  # rewrites tests/golden/reference_long_runs.json only
 """
 import csv
 import hashlib
@@ -332,6 +334,25 @@ def gen_reference_runs(ref):
     print("reference_runs.json:", len(seeds), "seeded runs,", sum("crashed" in r for r in seeds.values()), "of them crashed in the reference")
 
 
+def gen_reference_long_runs():
+    """The reference's main() on cli_cases.make_long_case (reads of 25 000 to 48 000 bases, --maxlengthtelo 30 000 / 45 000) ->
+    reference_long_runs.json, recorded like reference_runs.json: the case's digest, the exit code, the walk order and the outputs
+    (normalised, file contents as digests).  The inputs are not stored: the tests regenerate them from the seed."""
+    import cli_cases
+    seeds = {}
+    for seed in cli_cases.LONG_SEEDS:
+        case = cli_cases.make_long_case(seed)
+        with tempfile.TemporaryDirectory() as d:
+            inp, out = cli_cases.materialise(case, d)
+            code = ref_import.run_reference_main(["-i", inp, "-o", out] + case["argv"])
+            seeds[str(seed)] = {"case_sha256": cli_cases.case_digest(case), "exit": code, "walk": cli_cases.walk_order(inp),
+                                "expected": cli_cases.digest_outputs(cli_cases.normalise(out))}
+    with open(os.path.join(GOLD, "reference_long_runs.json"), "w") as h:
+        json.dump({"seeds": seeds}, h, indent=0, sort_keys=True, default=int)
+    rows = [r for s in seeds.values() for r in (s["expected"]["csv"] or [])[1:]]
+    print("reference_long_runs.json:", len(seeds), "runs,", len(rows), "rows,", sum(1 for r in rows if int(r[4]) > 20000), "boundaries beyond 20000")
+
+
 def main():
     os.makedirs(GOLD, exist_ok=True)
     ref = ref_import.load_reference_allsteps()
@@ -341,11 +362,14 @@ def main():
     gen_overview()
     gen_cli()
     gen_reference_runs(ref)
+    gen_reference_long_runs()
     print("fixture bytes:", sum(os.path.getsize(os.path.join(GOLD, f)) for f in os.listdir(GOLD)))
 
 
 if __name__ == "__main__":
     if sys.argv[1:] == ["reference_runs"]:          # that fixture alone
         gen_reference_runs(ref_import.load_reference_allsteps())
+    elif sys.argv[1:] == ["reference_long_runs"]:
+        gen_reference_long_runs()
     else:
         main()

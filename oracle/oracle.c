@@ -110,8 +110,10 @@ int64_t orc_window_counts(const char* seq, int64_t L, int tail, const char* pats
 
 /* ---------------------------------------------------------------- a6: Binseg(model="l2"), n_bkps=1
  * numpy float64 semantics: ndarray.var = mean(abs(x - x.mean())**2), sums are numpy's pairwise
- * summation (unrolled by 8, blocks of 128). */
-static double pairwise_sum(const double* a, int64_t n) {
+ * summation (unrolled by 8, blocks of 128) -- over at most 8192 elements at a time: a reduction hands
+ * its inner loop one buffer's worth (numpy's default bufsize), and the buffers' sums add up one after
+ * the other.  Series of up to 8192 windows are one buffer. */
+static double pairwise_block(const double* a, int64_t n) {
     if (n < 8) {
         double res = 0.0;
         for (int64_t i = 0; i < n; ++i) res += a[i];
@@ -128,8 +130,16 @@ static double pairwise_sum(const double* a, int64_t n) {
     } else {
         int64_t n2 = n / 2;
         n2 -= n2 % 8;
-        return pairwise_sum(a, n2) + pairwise_sum(a + n2, n - n2);
+        return pairwise_block(a, n2) + pairwise_block(a + n2, n - n2);
     }
+}
+
+#define NUMPY_BUFSIZE 8192
+static double pairwise_sum(const double* a, int64_t n) {
+    double res = 0.0;
+    for (int64_t i = 0; i < n; i += NUMPY_BUFSIZE)
+        res += pairwise_block(a + i, n - i < NUMPY_BUFSIZE ? n - i : NUMPY_BUFSIZE);
+    return res;
 }
 
 /* CostL2.error(a, b) = signal[a:b].var(axis=0).sum() * (b - a) */

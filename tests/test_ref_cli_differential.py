@@ -72,6 +72,37 @@ def test_cli_matches_the_reference_main(first, tmp_path, emu_engine_factory, rec
     assert len(crashed) <= 3, crashed
 
 
+@pytest.fixture(scope="module")
+def recorded_long(gold_dir):
+    """The reference's runs on the long cases (oracle/gen_golden.py gen_reference_long_runs)."""
+    return json.load(open(os.path.join(gold_dir, "reference_long_runs.json")))
+
+
+def replay_long_case(seed, recorded_long, root, run):
+    """One recorded long case (cli_cases.make_long_case: reads of 25 000 to 48 000 bases, --maxlengthtelo 30 000 / 45 000), regenerated
+    from its seed and run with `run(argv)` -> exit code; returns the recorded CSV rows."""
+    case = cli_cases.make_long_case(seed)
+    rec = recorded_run(recorded_long["seeds"][str(seed)], case)
+    inp, out = cli_cases.materialise(case, root)
+    code = run(["-i", inp, "-o", out] + case["argv"])
+    assert rec["exit"] == code == case["exit"], (seed, case["argv"], rec["exit"], code)
+    compare_recorded(rec, inp, cli_cases.normalise(out), (seed, case["argv"]))
+    return rec["expected"]["csv"][1:]
+
+
+def test_cli_matches_the_reference_main_beyond_the_default_maxlengthtelo(tmp_path, emu_engine_factory, recorded_long):
+    """The four long cases: --maxlengthtelo 30 000 and 45 000 with --slide 6 and 10, one with --rawcountpattern.  The recording holds
+    boundaries beyond 20 000 -- what no other recorded run has."""
+    rows = []
+    for seed in cli_cases.LONG_SEEDS:
+        rows += replay_long_case(seed, recorded_long, str(tmp_path / f"long{seed}"), lambda argv: run_product(emu_engine_factory(), argv))
+    argvs = [cli_cases.make_long_case(s)["argv"] for s in cli_cases.LONG_SEEDS]
+    pick = lambda flag: {a[a.index(flag) + 1] for a in argvs}
+    assert pick("--maxlengthtelo") == {"30000", "45000"} and pick("--slide") == {"6", "10"}
+    assert sum("--rawcountpattern" in a for a in argvs) == 1
+    assert len(rows) >= 20 and sum(1 for r in rows if int(r[4]) > 20000) >= 8
+
+
 def test_existing_fasta_temp_file_is_reused_like_upstream(tmp_path, emu_engine_factory, recorded):
     """main.py:64-66: a `<name>_trc_over_<cutoff>.fasta` that is already there is used, not rewritten -- also for FASTQ input."""
     # the file the first run wrote = every record as FASTA (upstream's step 2 reads ITS records; the product scans the input)

@@ -298,8 +298,10 @@ inline std::string plan_geometry_core(ScanArgs& a, const tps_params& prm, int k,
         //  * raw rows are bytes, and so are their accumulators (window_exact counts OCCURRENCES, overlapping ones included,
         //    before the greedy recount of self-overlapping patterns): a pattern may occur at most 255 times in a window;
         //  * the window sums of a read are added up in 32 bits (prefix sums, candidate sums, Binseg chunk sums);
-        //  * the exact change-point tournament compares d^2 * den in 128 bits with d <= n * T, T <= n * max S_w and
-        //    den <= n^2 / 4: n^6 * (max S_w)^2 / 4 < 2^128.
+        //  * the exact change-point tournament compares d^2 * den in 128 bits.  d = |n L_b - T b| = |(n - b) L_b - b (T - L_b)| with
+        //    0 <= L_b <= b max S_w and 0 <= T - L_b <= (n - b) max S_w, so d <= b (n - b) max S_w <= n^2 max S_w / 4; den = b (n - b)
+        //    <= n^2 / 4: n^6 (max S_w)^2 / 64 < 2^128, that is n^3 max S_w < 2^67.  (At window 100 the limit of 500 000 windows per
+        //    read binds first; a bound through d <= n T alone would refuse such reads from about 394 000 windows on.)
         int min_per = k;
         for (int i = 0; i < a.pat.n_periods; ++i) min_per = std::min(min_per, std::max(1, (int)a.pat.period[i]));
         const int64_t occ_max = a.lw > 0 ? (a.lw - 1) / min_per + 1 : 0;
@@ -308,7 +310,7 @@ inline std::string plan_geometry_core(ScanArgs& a, const tps_params& prm, int k,
                    std::to_string(prm.window) + " (max 255); use a smaller --windowSize with --rawcountpattern";
         const int64_t sw_max = (int64_t)P * ((a.lw + k - 1) / k + 1);            // S_w <= P * (non-overlapping maximum + 1)
         if (max_nwin * sw_max >= (1ll << 32)) return "window sums of one read exceed 32 bits (windows per read x window size too large)";
-        if ((double)max_nwin * (double)max_nwin * (double)max_nwin * (double)sw_max >= 18446744073709551616.0 /* 2^64 */)
+        if ((double)max_nwin * (double)max_nwin * (double)max_nwin * (double)sw_max >= 147573952589676412928.0 /* 2^67 */)
             return "change-point arithmetic would exceed 128 bits (windows per read x window size too large)";
     }
     const int jump = std::max(prm.jump, 1);
@@ -442,8 +444,11 @@ inline std::string plan_geometry_core(ScanArgs& a, const tps_params& prm, int k,
             if (with_pair >= 5 * WPG || waves_per_cu(WPG) <= with_pair) { a.pair_n = keep; if (keep16) { a.pair16 = 1; a.lut16 = 1; } }
         }
         if (wg_lds_dwords(a) <= budget_dw) return "";
-        // does not fit (very long maxlengthtelo: the candidate sums of 4 reads outgrow LDS): the generic kernel,
-        // whose tile size adapts, takes over
+        // does not fit.  maxlengthtelo cannot bring a scan here: the fused plan's LDS is the lookup tables and the tile buffers
+        // of compile-time size (the step-1 heads share the tile buffer, see `fused` above), and the candidate sums live off-chip
+        // (lc_scratch) -- variant, tw and the LDS bytes are the same from 3 301 to 500 000 windows per read
+        // (tests/test_long_series.py).  What is left is the budget itself: a caller or a device that offers less LDS per
+        // workgroup than these fixed sizes add up to.  Then the generic kernel, whose tile size adapts, takes over
         a.tw = 0; a.pair_n = 0; a.lc_global = 0; a.lc_stride = 0; a.pp_d = -1; a.so_fast = 0; a.seq_alias = 0; a.lut_fields = 0;
         a.lut16 = 0; a.xt_alias = 0; a.xt_own = 0; a.pair16 = 0;
     }
