@@ -434,6 +434,32 @@ int  tps_batch_end_window(tps_ctx* ctx, int32_t slot, uint64_t unit, int32_t m, 
 int  tps_window_offsets(tps_ctx* ctx, const uint32_t* codes, const uint32_t* keep, const int32_t* length, const int32_t* ref, int64_t n,
                         int32_t span, int32_t k, int32_t* offset, int32_t* votes, int32_t* second, int64_t out_len);
 
+/* ---- named ends (end groups placed on the ends of a reference) ------------------------- */
+/* n query windows placed on n_ref reference windows, all from the host (no resident batch and no pattern table needed).  Both sets
+ * are rows as tps_batch_end_window writes them -- codes, keep, length[i] letters -- with one span and one k; kept positions and
+ * x(p) = fmix32(c ^ 0x9E3779B9) are those of tps_window_offsets.
+ *   index    an ENTRY is (x, r, q) for every kept q of every reference row r.  A k-mer with more than max_occ entries over ALL
+ *            reference rows is dropped whole; every other entry takes part (no slot is fought over: no k-mer is lost to another,
+ *            and a k-mer several rows share counts for each of them, once per entry).
+ *   matches  of query i: every (r, q, p) with p kept in the query and (x(p), r, q) an entry.
+ *   total    total[r] = the matches on row r.  ref = the smallest r with the largest total, -1 where the query has no match.
+ *            runner_ref = the smallest r != ref with the largest total among the other rows, -1 where no other row has a match;
+ *            runner = that row's total, or 0.
+ *   coarse   over the matches of row ref only, d = q - p: H[(d + 4096) >> 6]++ over 128 bins; pair, best and second exactly as in
+ *            tps_window_offsets.
+ *   fine     the 128 diagonals of the best pair: votes = their number (= pair[best]), offset = their lower median.
+ * ref, total (of row ref), runner_ref, runner, offset, votes, second: int32[n] each, every entry written, offset in window
+ * coordinates.  A query with length < k or without a match gets -1, 0, -1, 0, 0, 0, 0.  A reference row with length < k or no keep
+ * bit has no entry.  Exact, identical from run to run (minima and counts do not depend on order).  TPS_E_CAPACITY: n over 262144,
+ * n_ref outside 1..1024, span outside k..4096, k outside 8..16, max_occ outside 1..64.  TPS_E_ARG: codes_len / keep_len /
+ * ref_codes_len / ref_keep_len that are not n resp. n_ref rows of (span + 15) / 16 resp. (span + 31) / 32 dwords, out_len != n, a
+ * length or ref_length outside 0..span.  The index is built on the host once per call (sorted entries behind a directory over
+ * the top bits of x; 16 bytes per entry, at most n_ref x 4096 entries = 64 MB); one launch; returns when the outputs are in place. */
+int  tps_window_place(tps_ctx* ctx, const uint32_t* codes, int64_t codes_len, const uint32_t* keep, int64_t keep_len, const int32_t* length,
+                      int64_t n, const uint32_t* ref_codes, int64_t ref_codes_len, const uint32_t* ref_keep, int64_t ref_keep_len,
+                      const int32_t* ref_length, int32_t n_ref, int32_t span, int32_t k, int32_t max_occ, int32_t* ref, int32_t* total,
+                      int32_t* runner_ref, int32_t* runner, int32_t* offset, int32_t* votes, int32_t* second, int64_t out_len);
+
 /* ---- measurement ----------------------------------------------------------------------- */
 /* hipEvent timings of the scan kernel launches since the last reset: number of launches,
  * total and mean milliseconds (events are recorded on the stream the kernel runs on). */

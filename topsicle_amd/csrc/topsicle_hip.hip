@@ -26,6 +26,7 @@
 #include "tps_tract.h"
 #include "tps_ends.h"
 #include "tps_anchor.h"
+#include "tps_place.h"
 #include "tps_pack.h"
 #include "tps_plan.h"
 #include "tps_wide.h"
@@ -165,6 +166,14 @@ __global__ void __launch_bounds__(NT * OFFSETS_WPG) window_offsets_kernel(Offset
     const int64_t i = (int64_t)blockIdx.x * OFFSETS_WPG + wave;
     if (i >= a.n) return;
     window_offsets_row(a, i, smem + wave * OFFSETS_LDS_DW);
+}
+// The windows placed on a reference's (tps_window_place; window_place_row in csrc/tps_place.h): one wave per query row.
+__global__ void __launch_bounds__(NT * PLACE_WPG) window_place_kernel(PlaceArgs a) {
+    __shared__ __attribute__((aligned(16))) uint32_t smem[PLACE_WPG * PLACE_LDS_DW];
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t i = (int64_t)blockIdx.x * PLACE_WPG + wave;
+    if (i >= a.n) return;
+    window_place_row(a, i, smem + wave * PLACE_LDS_DW);
 }
 }  // namespace tps
 
@@ -431,6 +440,7 @@ struct tps_ctx {
     DevBuf links_t, links_out;        // tps_sketch_links: the sketches bucket-major; degree, links and matches behind one another
     DevBuf window_out;                // tps_batch_end_window: codes and keep behind one another (its inputs are ends_in, its table tract_table)
     DevBuf offsets_in, offsets_out;   // tps_window_offsets: codes, keep, length and ref; offset, votes and second behind one another
+    DevBuf place_in, place_idx, place_out;   // tps_window_place: the queries' codes, keep and length; the index's dir, keys and ent; the seven outputs behind one another
     DevBuf ascii, ascii_off;          // staging of tps_batch_upload: ASCII bases + offsets, packed on the device right after the copy
     DevBuf nib, nib_src;              // staging of tps_batch_upload_nib4: BAM base codes + where each read's are, expanded right after the copy
     std::set<void*> pinned;           // host buffers handed out by tps_host_alloc
@@ -1733,6 +1743,58 @@ int tps_window_offsets(tps_ctx* c, const uint32_t* codes, const uint32_t* keep, 
     HIP_TRY(hipMemcpyAsync(offset, a.offset, n_bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(votes, a.votes, n_bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(second, a.second, n_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return TPS_OK;
+}
+
+int tps_window_place(tps_ctx* c, const uint32_t* codes, int64_t codes_len, const uint32_t* keep, int64_t keep_len, const int32_t* length, int64_t n,
+                     const uint32_t* ref_codes, int64_t ref_codes_len, const uint32_t* ref_keep, int64_t ref_keep_len, const int32_t* ref_length,
+                     int32_t n_ref, int32_t span, int32_t k, int32_t max_occ, int32_t* ref, int32_t* total, int32_t* runner_ref, int32_t* runner,
+                     int32_t* offset, int32_t* votes, int32_t* second, int64_t out_len) {
+    int rc;
+    if ((rc = bind(c))) return rc;
+    const char* why = "";
+    if ((rc = tps::place_check(n, n_ref, span, k, max_occ, codes_len, keep_len, ref_codes_len, ref_keep_len, out_len, &why))) return fail(rc, "%s", why);
+    if (!ref_codes || !ref_keep || !ref_length) return fail(TPS_E_ARG, "null ref_codes / ref_keep / ref_length");
+    int64_t at = 0;
+    if ((rc = tps::place_check_rows(ref_length, n_ref, span, &why, &at))) return fail(rc, "reference row %lld: %s", (long long)at, why);
+    if (n == 0) return TPS_OK;
+    if (!codes || !keep || !length || !ref || !total || !runner_ref || !runner || !offset || !votes || !second)
+        return fail(TPS_E_ARG, "null codes / keep / length / ref / total / runner_ref / runner / offset / votes / second");
+    if ((rc = tps::place_check_rows(length, n, span, &why, &at))) return fail(rc, "row %lld: %s", (long long)at, why);
+    const int cdw = (span + 15) / 16, kdw = (span + 31) / 32;
+    tps::PlaceIndex ix;
+    tps::place_index_build(ref_codes, ref_keep, ref_length, n_ref, cdw, kdw, k, max_occ, ix);
+    const size_t co_bytes = (size_t)n * cdw * 4, kp_bytes = (size_t)n * kdw * 4, n_bytes = (size_t)n * 4;
+    const size_t dir_bytes = ix.dir.size() * 4, key_bytes = ix.keys.size() * 4, ent_bytes = ix.ent.size() * 4;
+    if ((rc = c->place_in.ensure(co_bytes + kp_bytes + n_bytes))) return rc;
+    if ((rc = c->place_idx.ensure(dir_bytes + key_bytes + ent_bytes))) return rc;
+    if ((rc = c->place_out.ensure(tps::PLACE_OUTS * n_bytes))) return rc;
+    TPS_POISON(c->place_in);
+    TPS_POISON(c->place_idx);
+    TPS_POISON(c->place_out);
+    char* in = (char*)c->place_in.p;
+    char* idx = (char*)c->place_idx.p;
+    HIP_TRY(hipMemcpyAsync(in, codes, co_bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(in + co_bytes, keep, kp_bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(in + co_bytes + kp_bytes, length, n_bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(idx, ix.dir.data(), dir_bytes, hipMemcpyHostToDevice, c->stream));
+    if (key_bytes) HIP_TRY(hipMemcpyAsync(idx + dir_bytes, ix.keys.data(), key_bytes, hipMemcpyHostToDevice, c->stream));
+    if (ent_bytes) HIP_TRY(hipMemcpyAsync(idx + dir_bytes + key_bytes, ix.ent.data(), ent_bytes, hipMemcpyHostToDevice, c->stream));
+    tps::PlaceArgs a{};
+    a.codes = (const uint32_t*)in;
+    a.keep = (const uint32_t*)(in + co_bytes);
+    a.length = (const int32_t*)(in + co_bytes + kp_bytes);
+    a.dir = (const uint32_t*)idx;
+    a.keys = (const uint32_t*)(idx + dir_bytes);
+    a.ent = (const uint32_t*)(idx + dir_bytes + key_bytes);
+    a.out = (int32_t*)c->place_out.p;
+    a.n = n;
+    a.R = n_ref; a.k = k; a.cdw = cdw; a.kdw = kdw; a.shift = 32 - ix.bits;
+    hipLaunchKernelGGL(tps::window_place_kernel, dim3((unsigned)((n + tps::PLACE_WPG - 1) / tps::PLACE_WPG)), dim3(tps::NT * tps::PLACE_WPG), 0, c->stream, a);
+    HIP_TRY(hipGetLastError());
+    int32_t* outs[tps::PLACE_OUTS] = {ref, total, runner_ref, runner, offset, votes, second};
+    for (int j = 0; j < tps::PLACE_OUTS; ++j) HIP_TRY(hipMemcpyAsync(outs[j], (char*)c->place_out.p + j * n_bytes, n_bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return TPS_OK;
 }

@@ -213,6 +213,45 @@ TPS_DEV bool offsets_vote(const uint32_t* tbl, const uint32_t* cod, const uint32
 // are the 64 keep bits of step s clear?  (wave-uniform)
 TPS_DEV bool offsets_step_empty(const uint32_t* kp, int s) { return (uniform(kp[2 * s]) | uniform(kp[2 * s + 1])) == 0; }
 
+// coarse: best = the smallest c with the largest pair, votes = that pair, second = the largest pair at least two bins away (wave code)
+TPS_DEV void offsets_best(const uint32_t* H, int& best, uint32_t& votes, uint32_t& second) {
+    // the smallest c with the largest pair: the maximum of pair << 7 | 127 - c (a pair is at most 4096 votes)
+    Lane<uint32_t> key, sec;
+    TPS_PHASE {
+        uint32_t m = 0;
+        for (int c = tid; c < ANCHOR_BINS - 1; c += NT) {
+            const uint32_t kc = ((H[c] + H[c + 1]) << 7) | (uint32_t)(ANCHOR_BINS - 1 - c);
+            m = kc > m ? kc : m;
+        }
+        TPS_AT(key) = m;
+    }
+    const uint32_t top = wave_max_u32(key);
+    best = ANCHOR_BINS - 1 - (int)(top & 127u);
+    votes = top >> 7;
+    const int b = best;
+    TPS_PHASE {
+        uint32_t m = 0;
+        for (int c = tid; c < ANCHOR_BINS - 1; c += NT) {
+            const uint32_t pr = H[c] + H[c + 1];
+            if ((c >= b + 2 || c <= b - 2) && pr > m) m = pr;
+        }
+        TPS_AT(sec) = m;
+    }
+    second = wave_max_u32(sec);
+}
+// fine: *out = the lower median of the votes (> 0) counted in F, the 128 diagonals from dlo on (wave code; one lane stores)
+TPS_DEV void offsets_median(const uint32_t* F, uint32_t votes, int dlo, int32_t* out) {
+    // the diagonal that holds vote (votes - 1) / 2 of the sorted ones; a lane looks at two neighbouring diagonals
+    Lane<uint32_t> two;
+    TPS_PHASE { TPS_AT(two) = F[2 * tid] + F[2 * tid + 1]; }
+    const Lane<uint32_t> before = wave_excl_sum(two);
+    const uint32_t mid = (votes - 1u) / 2u;
+    TPS_PHASE {
+        const uint32_t e0 = TPS_AT(before), f0 = F[2 * tid];
+        if (mid >= e0 && mid < e0 + TPS_AT(two)) *out = dlo + 2 * tid + (mid >= e0 + f0 ? 1 : 0);
+    }
+}
+
 // row i of the offsets; `lds`: OFFSETS_LDS_DW dwords of the wave's own
 TPS_DEV void window_offsets_row(const OffsetArgs& a, int64_t i, uint32_t* lds) {
     uint32_t* tbl = lds;
@@ -259,28 +298,9 @@ TPS_DEV void window_offsets_row(const OffsetArgs& a, int64_t i, uint32_t* lds) {
         }
     }
     TPS_SYNC();
-    // the smallest c with the largest pair: the maximum of pair << 7 | 127 - c (a pair is at most 4096 votes)
-    Lane<uint32_t> key, sec;
-    TPS_PHASE {
-        uint32_t m = 0;
-        for (int c = tid; c < ANCHOR_BINS - 1; c += NT) {
-            const uint32_t kc = ((H[c] + H[c + 1]) << 7) | (uint32_t)(ANCHOR_BINS - 1 - c);
-            m = kc > m ? kc : m;
-        }
-        TPS_AT(key) = m;
-    }
-    const uint32_t top = wave_max_u32(key);
-    const int best = ANCHOR_BINS - 1 - (int)(top & 127u);
-    const uint32_t votes = top >> 7;
-    TPS_PHASE {
-        uint32_t m = 0;
-        for (int c = tid; c < ANCHOR_BINS - 1; c += NT) {
-            const uint32_t pr = H[c] + H[c + 1];
-            if ((c >= best + 2 || c <= best - 2) && pr > m) m = pr;
-        }
-        TPS_AT(sec) = m;
-    }
-    const uint32_t second = wave_max_u32(sec);
+    int best;
+    uint32_t votes, second;
+    offsets_best(H, best, votes, second);
     if (votes != 0) {
         const int dlo = 64 * best - ANCHOR_MAX_SPAN;
         for (int s = 0; s < steps_q; ++s) {
@@ -291,15 +311,7 @@ TPS_DEV void window_offsets_row(const OffsetArgs& a, int64_t i, uint32_t* lds) {
             }
         }
         TPS_SYNC();
-        // the lower median: the diagonal that holds vote (votes - 1) / 2 of the sorted ones; a lane looks at two neighbouring diagonals
-        Lane<uint32_t> two;
-        TPS_PHASE { TPS_AT(two) = F[2 * tid] + F[2 * tid + 1]; }
-        const Lane<uint32_t> before = wave_excl_sum(two);
-        const uint32_t mid = (votes - 1u) / 2u;
-        TPS_PHASE {
-            const uint32_t e0 = TPS_AT(before), f0 = F[2 * tid];
-            if (mid >= e0 && mid < e0 + TPS_AT(two)) a.offset[i] = dlo + 2 * tid + (mid >= e0 + f0 ? 1 : 0);
-        }
+        offsets_median(F, votes, dlo, &a.offset[i]);
     }
     TPS_PHASE {
         if (tid == 0) {

@@ -7,7 +7,7 @@ bucket over the k-mers that hold no word of the telomere repeat (tps_batch_end_s
 all sketches with each other (tps_sketch_links).  This module holds what the host adds: the windows, the collector, the groups
 (connected components of the links, by union-find), the two CSV files and the summary for the log.
 
-What comes out are GROUPS OF READS, numbered by size -- not chromosome names: no reference is read.  The defaults rest on synthetic,
+What comes out are GROUPS OF READS, numbered by size -- not chromosome names: no reference is read (endref.py names them against one).  The defaults rest on synthetic,
 independent subtelomeres (README, "End groups").
 """
 from __future__ import annotations

@@ -23,7 +23,7 @@ FOLLOW_MAX_FWD, FOLLOW_WIDE_MAX_FWD, FOLLOW_HIST_MAX = 15, 32, 8      # k-mers t
 EXPORTS = [
     "tps_abi_version", "tps_device_count", "tps_ctx_create", "tps_ctx_destroy", "tps_last_error",
     "tps_set_patterns", "tps_set_patterns_wide", "tps_batch_upload", "tps_batch_upload_packed", "tps_batch_upload_nib4", "tps_batch_share", "tps_host_alloc", "tps_host_free",
-    "tps_batch_download_packed", "tps_batch_kmer_followers", "tps_batch_kmer_followers_wide", "tps_batch_motif_census", "tps_batch_variant_census", "tps_batch_tract_map", "tps_batch_end_sketch", "tps_sketch_links", "tps_batch_end_window", "tps_window_offsets", "tps_batch_set_tails", "tps_batch_scan", "tps_sync",
+    "tps_batch_download_packed", "tps_batch_kmer_followers", "tps_batch_kmer_followers_wide", "tps_batch_motif_census", "tps_batch_variant_census", "tps_batch_tract_map", "tps_batch_end_sketch", "tps_sketch_links", "tps_batch_end_window", "tps_window_offsets", "tps_window_place", "tps_batch_set_tails", "tps_batch_scan", "tps_sync",
     "tps_batch_results", "tps_batch_window_offsets", "tps_batch_window_sums", "tps_batch_window_raw",
     "tps_batch_raw_to_fd", "tps_batch_trc_counts", "tps_trc_counts", "tps_window_counts", "tps_binseg_l2", "tps_binseg_l2_ties", "tps_batch_read_sums", "tps_window_count",
     "tps_kernel_time_ms", "tps_kernel_time_reset", "tps_device_info", "tps_batch_kernel_info", "tps_ctx_debug_option", "tps_debug_stamps_get",
@@ -68,6 +68,8 @@ ENDS_K_RANGE, ENDS_BUCKETS, ENDS_MAX_WINDOW, LINKS_MAX_N, LINKS_MAX_LINKS = (8, 
 ENDS_EMPTY = 0xFFFFFFFF           # an empty bucket of a sketch
 # tps_batch_end_window / tps_window_offsets: letters of a window, rows of one call
 ANCHOR_MAX_SPAN, ANCHOR_MAX_ROWS = 4096, 262144
+# tps_window_place: reference rows of one call, entries of a k-mer that still takes part
+PLACE_MAX_REFS, PLACE_MAX_OCC = 1024, 64
 RES_TIE = 1            # TPS_RES_TIE: the exact tournament decided the change-point (candidates within float64 noise of each other)
 
 
@@ -117,6 +119,7 @@ def load_library(path: str | None = None) -> C.CDLL:
         "tps_sketch_links": (C.c_int, [vp, vp, i64, i32, i64, i32, i32, vp, i64, vp, i64, vp, i64]),
         "tps_batch_end_window": (C.c_int, [vp, i32, C.c_uint64, i32, i32, vp, vp, vp, i64, i32, vp, i64, vp, i64]),
         "tps_window_offsets": (C.c_int, [vp, vp, vp, vp, vp, i64, i32, i32, vp, vp, vp, i64]),
+        "tps_window_place": (C.c_int, [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64]),
         "tps_batch_set_tails": (C.c_int, [vp, i32, vp]),
         "tps_batch_scan": (C.c_int, [vp, i32, C.POINTER(Params)]),
         "tps_sync": (C.c_int, [vp]),
@@ -570,6 +573,28 @@ class HipScanner:
         self._check(self.lib.tps_window_offsets(self._h, _ptr(codes), _ptr(keep), _ptr(length), _ptr(ref), n, span, k,
                                                 _ptr(offset), _ptr(votes), _ptr(second), n))
         return offset, votes, second
+
+    def place_windows(self, codes, keep, length, ref_codes, ref_keep, ref_length, span: int, k: int = 12, max_occ: int = 16):
+        """n query windows placed on R reference windows (tps_window_place; the rule is in include/topsicle_hip.h): both sets as rows
+        the way end_window returns them, length[i] letters each.  Returns (ref, total, runner_ref, runner, offset, votes, second),
+        int32[n] each -- the reference row with the most matching k-mers and their number, the same for the best other row, and the
+        offset of the window against that reference row's with its votes and runner-up as anchor_offsets gives them.  A k-mer with
+        more than max_occ entries over all reference rows takes no part.  Needs no resident batch and no pattern table."""
+        codes = np.ascontiguousarray(codes, dtype=np.uint32)
+        keep = np.ascontiguousarray(keep, dtype=np.uint32)
+        length = np.ascontiguousarray(length, dtype=np.int32)
+        ref_codes = np.ascontiguousarray(ref_codes, dtype=np.uint32)
+        ref_keep = np.ascontiguousarray(ref_keep, dtype=np.uint32)
+        ref_length = np.ascontiguousarray(ref_length, dtype=np.int32)
+        n, n_ref = len(length), len(ref_length)
+        sp = span if 1 <= span <= ANCHOR_MAX_SPAN else 1                       # (a bad span is the library's to refuse)
+        cdw, kdw = (sp + 15) // 16, (sp + 31) // 32
+        if codes.shape != (n, cdw) or keep.shape != (n, kdw) or ref_codes.shape != (n_ref, cdw) or ref_keep.shape != (n_ref, kdw):
+            raise TopsicleHipError("place_windows: codes / keep and ref_codes / ref_keep must hold one row of `span` letters per window")
+        out = [np.zeros(n, dtype=np.int32) for _ in range(7)]
+        self._check(self.lib.tps_window_place(self._h, _ptr(codes), codes.size, _ptr(keep), keep.size, _ptr(length), n, _ptr(ref_codes), ref_codes.size,
+                                              _ptr(ref_keep), ref_keep.size, _ptr(ref_length), n_ref, span, k, max_occ, *[_ptr(o) for o in out], n))
+        return tuple(out)
 
     def set_tails(self, slot: int, tails: np.ndarray):
         tails = np.ascontiguousarray(tails, dtype=np.uint8)

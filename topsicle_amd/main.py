@@ -20,7 +20,7 @@ from collections import defaultdict
 
 import numpy as np
 
-from . import allsteps, anchor, batch, ends, hiplib, motif, rawnpz, seqio, tracts, variants
+from . import allsteps, anchor, batch, endref, ends, hiplib, motif, rawnpz, seqio, tracts, variants
 
 version_number = "1.0.0"
 Topsicle_output_prefix = "Topsicle"
@@ -117,6 +117,18 @@ def _formats(seq_loc: str):
 _CSV_LOCK = __import__("threading").Lock()      # telolengths_all.csv is appended batch by batch from every file in flight
 
 
+NO_BP = 1000                                    # bases of a read end that step 1 counts in (main.py:52-60)
+
+
+def _scan_params(args, slide):
+    """The parameters of one k's scan: of the reads of every input file, and of the pieces of --endref."""
+    min_cutoff = min(args.cutoff) if isinstance(args.cutoff, (list, tuple)) else args.cutoff
+    return hiplib.make_params(
+        no_bp=NO_BP, min_len=args.minSeqLength, min_count=allsteps.min_count_for_cutoff(min_cutoff, NO_BP / len(args.pattern), NO_BP),
+        window=args.windowSize, slide=slide, trimfirst=args.trimfirst, maxlen=args.maxlengthtelo,
+        flags=hiplib.F_STEP1 | hiplib.F_WINDOWS | hiplib.F_BINSEG)
+
+
 def process_file(args, seq_loc, telo_phrase, pattern, sliding_val, engines):
     """One input file, one k (main.py:52-154).  Returns [(file_name, telo_phrase, [[readID, telolen]], trc), ...] in read order."""
     return process_file_multi(args, seq_loc, [(telo_phrase, pattern, sliding_val)], engines)[0]
@@ -134,7 +146,7 @@ def process_file_multi(args, seq_loc, phrases, engines):
     base_name = os.path.basename(seq_loc)
     file_name = os.path.splitext(base_name)[0]
     min_cutoff = min(args.cutoff) if isinstance(args.cutoff, (list, tuple)) else args.cutoff
-    no_bp = 1000
+    no_bp = NO_BP
     ratio = no_bp / len(args.pattern)
     want_sums = bool(args.plot)
     want_raw = bool(args.rawcountpattern)
@@ -148,11 +160,8 @@ def process_file_multi(args, seq_loc, phrases, engines):
     # --ends: the same per k; the sketch runs on the batch workers, the links once per run (analysis_run)
     ecols = getattr(args, "end_collectors", None) or [None] * len(phrases)
     erows = [[] for _ in phrases]
-    jobs = [batch.Job(pattern, hiplib.make_params(
-        no_bp=no_bp, min_len=args.minSeqLength, min_count=allsteps.min_count_for_cutoff(min_cutoff, ratio, no_bp),
-        window=args.windowSize, slide=slide, trimfirst=args.trimfirst, maxlen=args.maxlengthtelo,
-        flags=hiplib.F_STEP1 | hiplib.F_WINDOWS | hiplib.F_BINSEG), want_sums, want_raw, raw_sink=sink, variants=None if col is None else col.spec,
-        ends=None if ecol is None else ecol.spec)
+    jobs = [batch.Job(pattern, _scan_params(args, slide), want_sums, want_raw, raw_sink=sink, variants=None if col is None else col.spec,
+                      ends=None if ecol is None else ecol.spec)
         for (_k, pattern, slide), sink, col, ecol in zip(phrases, raw_npz, vcols, ecols)]
     # --tracts: one collector for the whole run; the map runs once per batch, with the first k's job
     tcol = getattr(args, "tract_collector", None)
@@ -377,6 +386,11 @@ def analysis_run(args, engines=None, engine_factory=None, wait_plots=True):
         if why is not None:
             tprint(f"--anchor needs {why}")
             sys.exit(2)
+    if getattr(args, "endref", None):
+        why = endref.check(getattr(args, "ends", False), args.endspan, args.endrefmaxocc, args.endrefminvotes, args.endrefratio)
+        if why is not None:
+            tprint(f"--endref needs {why}")
+            sys.exit(2)
     if args.pattern.strip().lower() == "auto":
         # the motif comes from the reads (motif.py); from here on the run is the one `--pattern <that motif>` would have been
         if engines is None:
@@ -453,8 +467,21 @@ def analysis_run(args, engines=None, engine_factory=None, wait_plots=True):
         if unit != args.pattern.upper():
             tprint(f"--ends: {args.pattern} is a power of {unit}; k-mers with words of {unit} are left out of the sketches")
         args.end_collectors = [ends.Collector(unit, args.endk, args.endbuckets, args.endspan, args.endminmatch, args.endminkmers, args.endminreads,
-                                              args.trimfirst, slide, args.maxlengthtelo, anchor=bool(getattr(args, "anchor", False)))
+                                              args.trimfirst, slide, args.maxlengthtelo,
+                                              anchor=bool(getattr(args, "anchor", False) or getattr(args, "endref", None)))      # (either keeps the windows)
                                for _k, _pattern, slide in phrases]
+    ref_ends = None
+    if getattr(args, "endref", None):
+        # the reference's ends: its pieces scanned like reads, every k's table at once, into collectors of their own
+        rcols = [ends.Collector(unit, args.endk, args.endbuckets, args.endspan, args.endminmatch, args.endminkmers, args.endminreads,
+                                args.trimfirst, slide, args.maxlengthtelo, anchor=True) for _k, _pattern, slide in phrases]
+        ref_ends = endref.scan_reference(args.endref, engines[0], [batch.Job(pattern, _scan_params(args, slide), ends=col.spec)
+                                                                   for (_k, pattern, slide), col in zip(phrases, rcols)],
+                                         rcols, args.maxlengthtelo, args.endminkmers)
+        for (telo_phrase, _pattern, _slide), listed in zip(phrases, ref_ends):
+            if sum(e.indexed for e in listed) > endref.MAX_REFS:
+                tprint(f"--endref: {sum(e.indexed for e in listed)} usable reference ends for k = {telo_phrase}, {endref.MAX_REFS} at most")
+                sys.exit(2)
 
     args.tract_collector = None
     if getattr(args, "tracts", False):
@@ -507,7 +534,7 @@ def analysis_run(args, engines=None, engine_factory=None, wait_plots=True):
         for line in variants.summary(col.unit, col.total, col.n_tracts):
             tprint(line)
 
-    for (telo_phrase, _pattern, _slide), col in zip(phrases, args.end_collectors or []):
+    for n, ((telo_phrase, _pattern, _slide), col) in enumerate(zip(phrases, args.end_collectors or [])):
         # all pairs of the run's sketches: one call per k, on one context, after the last file
         try:
             read_rows, group_rows, stats = col.finish(filenames, engines[0])
@@ -519,7 +546,7 @@ def analysis_run(args, engines=None, engine_factory=None, wait_plots=True):
         tprint(f"end groups (k = {telo_phrase}): {args.outputDir}/end_reads_{telo_phrase}.csv, {args.outputDir}/ends_{telo_phrase}.csv")
         for line in ends.summary(col, stats):
             tprint(line)
-        if col.spec.anchor:
+        if getattr(args, "anchor", False):
             # one boundary per group: every grouped read's window against its group's reference, one call per k
             a_reads, a_groups, a_stats = anchor.run(col.rows_in_order(filenames), read_rows, engines[0], col.spec.k, col.spec.span,
                                                     args.anchorminvotes, args.anchorratio)
@@ -527,6 +554,16 @@ def analysis_run(args, engines=None, engine_factory=None, wait_plots=True):
             ends.write_csv(f"{args.outputDir}/anchored_ends_{telo_phrase}.csv", anchor.GROUP_HEADER, a_groups)
             tprint(f"anchored lengths (k = {telo_phrase}): {args.outputDir}/anchored_reads_{telo_phrase}.csv, {args.outputDir}/anchored_ends_{telo_phrase}.csv")
             for line in anchor.summary(a_stats, args.anchorminvotes, args.anchorratio):
+                tprint(line)
+        if ref_ends is not None:
+            # one name per read: every read's window on all the reference's ends, one call per k
+            r_refs, r_reads, r_groups, r_stats = endref.run(col.rows_in_order(filenames), read_rows, ref_ends[n], engines[0], col.spec.k, col.spec.span,
+                                                            args.endminkmers, args.endrefmaxocc, args.endrefminvotes, args.endrefratio)
+            names = [f"{args.outputDir}/{stem}_{telo_phrase}.csv" for stem in ("ref_ends", "named_reads", "named_ends")]
+            for path, header, out_rows in zip(names, (endref.REF_HEADER, endref.READ_HEADER, endref.GROUP_HEADER), (r_refs, r_reads, r_groups)):
+                ends.write_csv(path, header, out_rows)
+            tprint(f"named ends (k = {telo_phrase}): " + ", ".join(names))
+            for line in endref.summary(r_stats, args.endminkmers, args.endrefminvotes, args.endrefratio):
                 tprint(line)
 
     if args.tract_collector is not None:
@@ -699,6 +736,13 @@ def build_parser():
                              "group and measure every read's telomere to it (anchored_reads_{k}.csv, anchored_ends_{k}.csv); needs --endspan of at most 4096")
     parser.add_argument("--anchorminvotes", metavar="INT", type=int, default=anchor.DEFAULT_MIN_VOTES, help="--anchor: k-mer votes a read needs on its best diagonals to be anchored")
     parser.add_argument("--anchorratio", metavar="INT", type=int, default=anchor.DEFAULT_RATIO, help="--anchor: ... and how many times the votes of the runner-up diagonals")
+    parser.add_argument("--endref", metavar="REF", default=None,
+                        help="MI355X build, with --ends: name the end groups against a reference -- a FASTA or FASTQ (plain or gzip) of chromosomes, contigs or subtelomeres; the "
+                             "first and last maxlengthtelo bases of every record are scanned like reads, and every read's window is placed on the ends found "
+                             "(ref_ends_{k}.csv, named_reads_{k}.csv, named_ends_{k}.csv); needs --endspan of at most 4096")
+    parser.add_argument("--endrefmaxocc", metavar="INT", type=int, default=endref.DEFAULT_MAX_OCC, help="--endref: a k-mer that occurs more often than this over all reference ends takes no part (1..64)")
+    parser.add_argument("--endrefminvotes", metavar="INT", type=int, default=endref.DEFAULT_MIN_VOTES, help="--endref: k-mer votes a read needs on its best diagonals to be named")
+    parser.add_argument("--endrefratio", metavar="INT", type=int, default=endref.DEFAULT_RATIO, help="--endref: ... and how many times the votes of the runner-up diagonals")
     parser.add_argument("--tracts", action="store_true",
                         help="MI355X build: map the telomere-repeat tracts of every WHOLE read, on both strands -- one row per tract (tracts.csv) and one per "
                              "read with a tract and its class: fusion, both_ends, interstitial, terminal (tract_reads.csv).  Runs the files as --twopass off")
