@@ -460,6 +460,30 @@ int  tps_window_place(tps_ctx* ctx, const uint32_t* codes, int64_t codes_len, co
                       const int32_t* ref_length, int32_t n_ref, int32_t span, int32_t k, int32_t max_occ, int32_t* ref, int32_t* total,
                       int32_t* runner_ref, int32_t* runner, int32_t* offset, int32_t* votes, int32_t* second, int64_t out_len);
 
+/* ---- adapters at the telomere end (which reads start at the real chromosome end, and with which barcode) ---- */
+/* Up to 64 given sequences searched approximately in a region of every read of the resident batch; no pattern table (the
+ * reference has nothing comparable).  For read r, h = the upper-cased read (tails[r] = 0) or its reverse complement
+ * (tails[r] = 1) -- "telomere first", as in tps_batch_variant_census.
+ *   region   T = h[begin[r] .. min(end[r], L)), n = |T|, 0 <= n <= 1024 (begin at or past the read's end: n = 0).
+ *   patterns pattern j = A_j, m_j = pat_len[j] letters of ACGT, 12 <= m_j <= 64, 0 <= j < n_pat, 1 <= n_pat <= 64, in the
+ *            orientation of h: a sequence expected at the 3' end of tail-1 reads is given reverse-complemented; the same list is
+ *            searched on both tails.  2-bit codes A C T G = 0 1 2 3, letter i in bits [2i, 2i + 1] of the 128 bits of
+ *            patterns[2j] (letters 0 .. 31) and patterns[2j + 1] (letters 32 .. 63), nothing behind the m_j letters.
+ *   distance D_j(e), e = 0 .. n: the smallest unit-cost edit distance (substitution, insertion, deletion: 1 each) between A_j and
+ *            any substring T[s .. e), 0 <= s <= e -- Sellers' recurrence D[0][e] = 0, D[i][0] = i,
+ *            D[i][e] = min(D[i-1][e-1] + (A_j[i-1] != T[e-1]), D[i-1][e] + 1, D[i][e-1] + 1), D_j(e) = D[m_j][e].  A letter of T that
+ *            is not ACGT matches nothing.  D_j(0) = m_j.
+ *   hits     uint16[n_reads][n_pat][2] = (dist_j, end_j): dist_j = the minimum of D_j(e) over e, end_j = the smallest e that
+ *            reaches it, relative to begin[r]; an empty region gives (m_j, 0).  Every entry is written.
+ * Exact, identical from run to run; the answer depends on nothing outside the region.  TPS_E_CAPACITY: n_pat outside 1..64, a
+ * pat_len outside 12..64, end - begin > 1024.  TPS_E_ARG: codes behind a pattern's letters, a tail other than 0 / 1, a negative
+ * begin / end, begin > end, n_reads or hits_len that does not match the slot and n_pat.  TPS_E_STATE: an empty slot.  One launch
+ * (one wave per read, one lane per pattern, Myers' bit-vector recurrence); returns when the outputs are in place.  The slot's scan
+ * state (tails, results, sums, raw rows) is not touched. */
+int  tps_batch_adapter_find(tps_ctx* ctx, int32_t slot, const uint64_t* patterns, const int32_t* pat_len, int32_t n_pat,
+                            const uint8_t* tails, const int32_t* begin, const int32_t* end, int64_t n_reads, uint16_t* hits,
+                            int64_t hits_len);
+
 /* ---- measurement ----------------------------------------------------------------------- */
 /* hipEvent timings of the scan kernel launches since the last reset: number of launches,
  * total and mean milliseconds (events are recorded on the stream the kernel runs on). */

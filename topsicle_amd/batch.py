@@ -42,7 +42,7 @@ class Job:
     batch = `--telophrase 4 5 6`: the batch is parsed, packed and uploaded ONCE and scanned once per k (the reference
     re-parses the input for every k, main.py:206-235)."""
 
-    def __init__(self, patterns, prm: hiplib.Params, want_sums=False, want_raw=False, raw_sink=None, variants=None, tracts=None, ends=None):
+    def __init__(self, patterns, prm: hiplib.Params, want_sums=False, want_raw=False, raw_sink=None, variants=None, tracts=None, ends=None, adapters=None):
         """raw_sink (with want_raw; rawnpz.RawNpzWriter): the raw rows of the reads the sink selects are written to its file by
         the worker that scanned the batch, device -> file, and the caller gets a `RawKept` in place of the rows.
         variants (variants.VariantSpec: unit, bin, n_bins, sink): the worker that scanned the batch runs the variant census of the
@@ -52,12 +52,15 @@ class Job:
         in heads mode is refused.  One job of a batch carries it (the map does not depend on the pattern table).
         ends (ends.EndSpec: unit, k, buckets, span, sink): the worker that scanned the batch sketches the subtelomere window behind every
         called boundary while the batch is still resident and hands (recs, results, sketch, kept) to the spec's sink -- and, for a
-        spec with `anchor` set, the windows' packed letters and keep bits behind them (recs, results, sketch, kept, codes, keep)."""
+        spec with `anchor` set, the windows' packed letters and keep bits behind them (recs, results, sketch, kept, codes, keep).
+        adapters (adapters.AdapterSpec: sequences, search, sink): the same worker searches the sequences in the first `search` bases of
+        every read with a called boundary while the batch is still resident and hands (recs, results, dist, end) to the spec's sink."""
         self.patterns, self.prm, self.want_sums, self.want_raw = list(patterns), prm, bool(want_sums), bool(want_raw)
         self.raw_sink = raw_sink if want_raw else None
         self.variants = variants
         self.tracts = tracts
         self.ends = ends
+        self.adapters = adapters
 
 
 class CensusJob:
@@ -165,6 +168,25 @@ def _sketch_ends(job, eng, slot, recs, res, slot_index=None):
         spec.sink(recs, res, sketch, kept, codes, keep)
     else:
         spec.sink(recs, res, sketch, kept)
+
+
+def _find_adapters(job, eng, slot, recs, res, slot_index=None):
+    """The adapter search at the telomere end of the reads the scan has just called (Job.adapters), on the engine and slot that were
+    scanned: the region [0, search) of the telomere-first string of every read whose boundary the CLI would store
+    (adapters.search_regions), begin = end = 0 -- the answer of an empty region, (m_j, 0) -- for every other read.  `slot_index` as in
+    _census_variants (search <= maxlen: the region lies inside the span packed for the second pass)."""
+    from . import adapters
+    spec = job.adapters
+    begin, end = adapters.search_regions(res, int(job.prm.trimfirst), int(job.prm.slide), int(job.prm.maxlen), spec.search)
+    tails = np.where(end > begin, res["tail"], 0).astype(np.uint8)
+    dist = np.tile(spec.lens.astype(np.uint16), (len(res), 1))
+    aend = np.zeros((len(res), len(spec.lens)), np.uint16)
+    if slot_index is None:
+        if eng is not None:
+            dist, aend = eng.adapter_find(slot, spec.seqs, tails, begin, end)
+    elif len(slot_index):
+        dist[slot_index], aend[slot_index] = eng.adapter_find(slot, spec.seqs, tails[slot_index], begin[slot_index], end[slot_index])
+    spec.sink(recs, res, dist, aend)
 
 
 def _map_tracts(job, eng, slot, recs):
@@ -284,6 +306,8 @@ def scan_jobs_heads(engine, recs, jobs, slot: int = 0, seq=None):
                     _census_variants(job, eng, slot_b, recs, res, slot_index=idx)
                 if getattr(job, "ends", None) is not None:
                     _sketch_ends(job, eng, slot_b, recs, res, slot_index=idx)
+                if getattr(job, "adapters", None) is not None:
+                    _find_adapters(job, eng, slot_b, recs, res, slot_index=idx)
                 np.cumsum(np.where(passing, res["n_win"], 0), out=win_off[1:])
                 if job.want_sums:
                     sums, wo_b = eng.window_sums(slot_b)
@@ -298,6 +322,8 @@ def scan_jobs_heads(engine, recs, jobs, slot: int = 0, seq=None):
                     _census_variants(job, None, slot_b, recs, res)             # (no read passed: an all-zero answer)
                 if getattr(job, "ends", None) is not None:
                     _sketch_ends(job, None, slot_b, recs, res)
+                if getattr(job, "adapters", None) is not None:
+                    _find_adapters(job, None, slot_b, recs, res)
                 if job.want_sums:
                     sums = np.zeros(0, np.int32)
                 if job.want_raw and job.raw_sink is not None and seq is not None:
@@ -373,6 +399,8 @@ def scan_jobs(engine, recs, jobs, slot: int = 0, seq=None):
                 _census_variants(job, eng, slot, recs, res)
             if getattr(job, "ends", None) is not None:
                 _sketch_ends(job, eng, slot, recs, res)
+            if getattr(job, "adapters", None) is not None:
+                _find_adapters(job, eng, slot, recs, res)
             if getattr(job, "tracts", None) is not None:
                 _map_tracts(job, eng, slot, recs)
             sums = raw = win_off = None

@@ -27,6 +27,7 @@
 #include "tps_ends.h"
 #include "tps_anchor.h"
 #include "tps_place.h"
+#include "tps_adapter.h"
 #include "tps_pack.h"
 #include "tps_plan.h"
 #include "tps_wide.h"
@@ -174,6 +175,15 @@ __global__ void __launch_bounds__(NT * PLACE_WPG) window_place_kernel(PlaceArgs 
     const int64_t i = (int64_t)blockIdx.x * PLACE_WPG + wave;
     if (i >= a.n) return;
     window_place_row(a, i, smem + wave * PLACE_LDS_DW);
+}
+// The adapters at the telomere end (tps_batch_adapter_find; adapter_read in csrc/tps_adapter.h): no table, one wave per read, one lane
+// per pattern.
+__global__ void __launch_bounds__(NT * ADAPTER_WPG) adapter_find_kernel(AdapterArgs a) {
+    __shared__ __attribute__((aligned(16))) uint32_t smem[ADAPTER_WPG * ADAPTER_LDS_DW];
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t r = (int64_t)blockIdx.x * ADAPTER_WPG + wave;
+    if (r >= a.n_reads) return;
+    adapter_read(a, r, smem + wave * ADAPTER_LDS_DW);
 }
 }  // namespace tps
 
@@ -441,6 +451,7 @@ struct tps_ctx {
     DevBuf window_out;                // tps_batch_end_window: codes and keep behind one another (its inputs are ends_in, its table tract_table)
     DevBuf offsets_in, offsets_out;   // tps_window_offsets: codes, keep, length and ref; offset, votes and second behind one another
     DevBuf place_in, place_idx, place_out;   // tps_window_place: the queries' codes, keep and length; the index's dir, keys and ent; the seven outputs behind one another
+    DevBuf adapter_in, adapter_out;   // tps_batch_adapter_find: Peq, lengths, tails / begin / end; the hits
     DevBuf ascii, ascii_off;          // staging of tps_batch_upload: ASCII bases + offsets, packed on the device right after the copy
     DevBuf nib, nib_src;              // staging of tps_batch_upload_nib4: BAM base codes + where each read's are, expanded right after the copy
     std::set<void*> pinned;           // host buffers handed out by tps_host_alloc
@@ -1795,6 +1806,57 @@ int tps_window_place(tps_ctx* c, const uint32_t* codes, int64_t codes_len, const
     HIP_TRY(hipGetLastError());
     int32_t* outs[tps::PLACE_OUTS] = {ref, total, runner_ref, runner, offset, votes, second};
     for (int j = 0; j < tps::PLACE_OUTS; ++j) HIP_TRY(hipMemcpyAsync(outs[j], (char*)c->place_out.p + j * n_bytes, n_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return TPS_OK;
+}
+
+int tps_batch_adapter_find(tps_ctx* c, int32_t slot, const uint64_t* patterns, const int32_t* pat_len, int32_t n_pat, const uint8_t* tails,
+                           const int32_t* begin, const int32_t* end, int64_t n_reads, uint16_t* hits, int64_t hits_len) {
+    int rc;
+    if ((rc = bind(c))) return rc;
+    Slot* sl = get_slot(c, slot);
+    if (!sl) return TPS_E_ARG;
+    if (sl->n < 0) return fail(TPS_E_STATE, "no batch uploaded in this slot");
+    const char* why = "";
+    int pat_at = 0;
+    if ((rc = tps::adapter_check(patterns, pat_len, n_pat, &why, &pat_at))) return fail(rc, "pattern %d: %s", pat_at, why);
+    const int64_t n = sl->n;
+    if (n_reads != n) return fail(TPS_E_ARG, "tails, begin and end must hold %lld reads", (long long)n);
+    if (hits_len != n * n_pat * 2) return fail(TPS_E_ARG, "hits must hold %lld values", (long long)(n * n_pat * 2));
+    if (n == 0) return TPS_OK;
+    if (!tails || !begin || !end || !hits) return fail(TPS_E_ARG, "null tails / begin / end / hits");
+    int64_t at = 0;
+    if ((rc = tps::adapter_check_reads(tails, begin, end, n, &why, &at))) return fail(rc, "read %lld: %s", (long long)at, why);
+    // (no pattern table; the slot's tails, its scan outputs and its plan are not touched: a scan before and after the call gives the same results)
+    uint64_t peq[4 * tps::ADAPTER_MAX_PATTERNS];
+    tps::adapter_build_peq(patterns, pat_len, n_pat, peq);
+    const size_t peq_bytes = (size_t)n_pat * 32, len_bytes = (size_t)n_pat * 4, out_bytes = (size_t)n * n_pat * 4;
+    const size_t off_len = peq_bytes, off_tails = (off_len + len_bytes + 15) & ~(size_t)15, off_begin = (off_tails + (size_t)n + 15) & ~(size_t)15,
+                 off_end = off_begin + (size_t)n * 4;
+    if ((rc = c->adapter_in.ensure(off_end + (size_t)n * 4))) return rc;
+    if ((rc = c->adapter_out.ensure(out_bytes))) return rc;
+    TPS_POISON(c->adapter_out);
+    char* in = (char*)c->adapter_in.p;
+    HIP_TRY(hipMemcpyAsync(in, peq, peq_bytes, hipMemcpyHostToDevice, c->stream));      // (pageable: the copy has left `peq` when the call returns)
+    HIP_TRY(hipMemcpyAsync(in + off_len, pat_len, len_bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(in + off_tails, tails, (size_t)n, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(in + off_begin, begin, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(in + off_end, end, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    tps::AdapterArgs a{};
+    a.seq2 = (const uint32_t*)sl->seq2.p;
+    a.inv = (const uint16_t*)sl->inv.p;
+    a.desc = (const tps_read_desc*)sl->desc.p;
+    a.peq = (const uint64_t*)in;
+    a.pat_len = (const int32_t*)(in + off_len);
+    a.tails = (const uint8_t*)(in + off_tails);
+    a.begin = (const int32_t*)(in + off_begin);
+    a.end = (const int32_t*)(in + off_end);
+    a.hits = (uint32_t*)c->adapter_out.p;
+    a.n_reads = n;
+    a.n_pat = n_pat;
+    hipLaunchKernelGGL(tps::adapter_find_kernel, dim3((unsigned)((n + tps::ADAPTER_WPG - 1) / tps::ADAPTER_WPG)), dim3(tps::NT * tps::ADAPTER_WPG), 0, c->stream, a);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(hits, a.hits, out_bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return TPS_OK;
 }

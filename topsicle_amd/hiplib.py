@@ -23,7 +23,7 @@ FOLLOW_MAX_FWD, FOLLOW_WIDE_MAX_FWD, FOLLOW_HIST_MAX = 15, 32, 8      # k-mers t
 EXPORTS = [
     "tps_abi_version", "tps_device_count", "tps_ctx_create", "tps_ctx_destroy", "tps_last_error",
     "tps_set_patterns", "tps_set_patterns_wide", "tps_batch_upload", "tps_batch_upload_packed", "tps_batch_upload_nib4", "tps_batch_share", "tps_host_alloc", "tps_host_free",
-    "tps_batch_download_packed", "tps_batch_kmer_followers", "tps_batch_kmer_followers_wide", "tps_batch_motif_census", "tps_batch_variant_census", "tps_batch_tract_map", "tps_batch_end_sketch", "tps_sketch_links", "tps_batch_end_window", "tps_window_offsets", "tps_window_place", "tps_batch_set_tails", "tps_batch_scan", "tps_sync",
+    "tps_batch_download_packed", "tps_batch_kmer_followers", "tps_batch_kmer_followers_wide", "tps_batch_motif_census", "tps_batch_variant_census", "tps_batch_tract_map", "tps_batch_end_sketch", "tps_sketch_links", "tps_batch_end_window", "tps_window_offsets", "tps_window_place", "tps_batch_adapter_find", "tps_batch_set_tails", "tps_batch_scan", "tps_sync",
     "tps_batch_results", "tps_batch_window_offsets", "tps_batch_window_sums", "tps_batch_window_raw",
     "tps_batch_raw_to_fd", "tps_batch_trc_counts", "tps_trc_counts", "tps_window_counts", "tps_binseg_l2", "tps_binseg_l2_ties", "tps_batch_read_sums", "tps_window_count",
     "tps_kernel_time_ms", "tps_kernel_time_reset", "tps_device_info", "tps_batch_kernel_info", "tps_ctx_debug_option", "tps_debug_stamps_get",
@@ -70,6 +70,8 @@ ENDS_EMPTY = 0xFFFFFFFF           # an empty bucket of a sketch
 ANCHOR_MAX_SPAN, ANCHOR_MAX_ROWS = 4096, 262144
 # tps_window_place: reference rows of one call, entries of a k-mer that still takes part
 PLACE_MAX_REFS, PLACE_MAX_OCC = 1024, 64
+# tps_batch_adapter_find: letters of a pattern, patterns of one call, letters of a region
+ADAPTER_LEN_RANGE, ADAPTER_MAX_PATTERNS, ADAPTER_MAX_REGION = (12, 64), 64, 1024
 RES_TIE = 1            # TPS_RES_TIE: the exact tournament decided the change-point (candidates within float64 noise of each other)
 
 
@@ -120,6 +122,7 @@ def load_library(path: str | None = None) -> C.CDLL:
         "tps_batch_end_window": (C.c_int, [vp, i32, C.c_uint64, i32, i32, vp, vp, vp, i64, i32, vp, i64, vp, i64]),
         "tps_window_offsets": (C.c_int, [vp, vp, vp, vp, vp, i64, i32, i32, vp, vp, vp, i64]),
         "tps_window_place": (C.c_int, [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64]),
+        "tps_batch_adapter_find": (C.c_int, [vp, i32, vp, vp, i32, vp, vp, vp, i64, vp, i64]),
         "tps_batch_set_tails": (C.c_int, [vp, i32, vp]),
         "tps_batch_scan": (C.c_int, [vp, i32, C.POINTER(Params)]),
         "tps_sync": (C.c_int, [vp]),
@@ -595,6 +598,26 @@ class HipScanner:
         self._check(self.lib.tps_window_place(self._h, _ptr(codes), codes.size, _ptr(keep), keep.size, _ptr(length), n, _ptr(ref_codes), ref_codes.size,
                                               _ptr(ref_keep), ref_keep.size, _ptr(ref_length), n_ref, span, k, max_occ, *[_ptr(o) for o in out], n))
         return tuple(out)
+
+    def adapter_find(self, slot: int, patterns, tails, begin, end):
+        """Every sequence of `patterns` (strings of ACGT, 12 .. 64 letters, at most 64 of them, telomere first like the region)
+        searched approximately in the region [begin, end) of every read of the resident batch (tails: 0 = the read, 1 = its reverse
+        complement; at most 1024 letters; tps_batch_adapter_find, the rule is in include/topsicle_hip.h; names and files:
+        topsicle_amd.adapters): (dist uint16[n, P], end uint16[n, P]) -- the smallest edit distance between the pattern and any
+        substring of the region, and the smallest end of such a substring, relative to begin.  No pattern table needed; the slot's
+        scan outputs stay as they are."""
+        from . import adapters
+        codes, lens = adapters.pattern_codes(patterns)
+        n = self._n[slot]
+        tails = np.ascontiguousarray(tails, dtype=np.uint8)
+        begin = np.ascontiguousarray(begin, dtype=np.int32)
+        end = np.ascontiguousarray(end, dtype=np.int32)
+        if not (len(tails) == len(begin) == len(end)):
+            raise TopsicleHipError("adapter_find: tails, begin and end must have one entry per read")
+        hits = np.zeros((n, len(lens), 2), dtype=np.uint16)
+        self._check(self.lib.tps_batch_adapter_find(self._h, slot, _ptr(codes), _ptr(lens), len(lens), _ptr(tails), _ptr(begin), _ptr(end), len(tails),
+                                                    _ptr(hits), hits.size))
+        return hits[:, :, 0].copy(), hits[:, :, 1].copy()
 
     def set_tails(self, slot: int, tails: np.ndarray):
         tails = np.ascontiguousarray(tails, dtype=np.uint8)

@@ -20,7 +20,7 @@ from collections import defaultdict
 
 import numpy as np
 
-from . import allsteps, anchor, batch, endref, ends, hiplib, motif, rawnpz, seqio, tracts, variants
+from . import adapters, allsteps, anchor, batch, endref, ends, hiplib, motif, rawnpz, seqio, tracts, variants
 
 version_number = "1.0.0"
 Topsicle_output_prefix = "Topsicle"
@@ -160,9 +160,12 @@ def process_file_multi(args, seq_loc, phrases, engines):
     # --ends: the same per k; the sketch runs on the batch workers, the links once per run (analysis_run)
     ecols = getattr(args, "end_collectors", None) or [None] * len(phrases)
     erows = [[] for _ in phrases]
+    # --adapters: the same per k; the search runs on the batch workers, the naming rule once per run (analysis_run)
+    acols = getattr(args, "adapter_collectors", None) or [None] * len(phrases)
+    arows = [[] for _ in phrases]
     jobs = [batch.Job(pattern, _scan_params(args, slide), want_sums, want_raw, raw_sink=sink, variants=None if col is None else col.spec,
-                      ends=None if ecol is None else ecol.spec)
-        for (_k, pattern, slide), sink, col, ecol in zip(phrases, raw_npz, vcols, ecols)]
+                      ends=None if ecol is None else ecol.spec, adapters=None if acol is None else acol.spec)
+        for (_k, pattern, slide), sink, col, ecol, acol in zip(phrases, raw_npz, vcols, ecols, acols)]
     # --tracts: one collector for the whole run; the map runs once per batch, with the first k's job
     tcol = getattr(args, "tract_collector", None)
     if tcol is not None:
@@ -255,6 +258,7 @@ def process_file_multi(args, seq_loc, phrases, engines):
                 vout = vcols[n].take(pb) if vcols[n] is not None else None
                 eout = ecols[n].take(pb) if ecols[n] is not None else None
                 ewin = ecols[n].take_windows(pb) if ecols[n] is not None else None          # (--anchor: the windows themselves)
+                aout = acols[n].take(pb) if acols[n] is not None else None
                 if wthread is not None and len(idx) and n == writer_k:
                     write_passing(pb, idx)                                   # every passing record (main.py:83-86)
                 ids = [pb.read_id(int(i)) for i in idx]
@@ -286,6 +290,10 @@ def process_file_multi(args, seq_loc, phrases, engines):
                     if ewin is not None:                                     # the letters the window really has: end clamped to the read
                         new = [row + (max(0, min(row[5], int(lens[j])) - row[4]), ewin[0][idx[j]].copy(), ewin[1][idx[j]].copy()) for row, j in zip(new, stored)]
                     erows[n] += new
+                if aout is not None:                                         # one row per read with a stored boundary
+                    a_dist, a_end = aout
+                    arows[n] += [(file_name, ids[j], int(r["tail"][j]), telo_l[j], a_dist[idx[j]].copy(), a_end[idx[j]].copy())
+                                 for j in np.nonzero(telolen != 0)[0]]
                 if n == 0:
                     with _CSV_LOCK, open(csv_path, mode="a", newline="") as fh:
                         csv.writer(fh).writerows(zip([file_name] * len(ids), [telo_phrase] * len(ids), ["%.3f" % t for t in trc_l], ids, telo_l))
@@ -336,6 +344,9 @@ def process_file_multi(args, seq_loc, phrases, engines):
     for col, er in zip(ecols, erows):
         if col is not None:
             col.add_file_rows(seq_loc, er)
+    for col, ar in zip(acols, arows):
+        if col is not None:
+            col.add_file_rows(seq_loc, ar)
     st = pool.stats
     if st.get("shards", 0) > 1:
         tprint(f"{base_name}: read as {st['shards']} byte ranges, one reader team each")
@@ -390,6 +401,14 @@ def analysis_run(args, engines=None, engine_factory=None, wait_plots=True):
         why = endref.check(getattr(args, "ends", False), args.endspan, args.endrefmaxocc, args.endrefminvotes, args.endrefratio)
         if why is not None:
             tprint(f"--endref needs {why}")
+            sys.exit(2)
+    adapter_pats = None
+    if getattr(args, "adapters", None):
+        # (before any input file is read or written; the sequences come from the command line or from their own small file)
+        adapter_pats = adapters.load_patterns(args.adapters)
+        why = adapters.check(adapter_pats, args.adaptersearch, args.adaptererr, args.adaptermargin, args.maxlengthtelo)
+        if why is not None:
+            tprint(f"--adapters needs {why}")
             sys.exit(2)
     if args.pattern.strip().lower() == "auto":
         # the motif comes from the reads (motif.py); from here on the run is the one `--pattern <that motif>` would have been
@@ -483,6 +502,10 @@ def analysis_run(args, engines=None, engine_factory=None, wait_plots=True):
                 tprint(f"--endref: {sum(e.indexed for e in listed)} usable reference ends for k = {telo_phrase}, {endref.MAX_REFS} at most")
                 sys.exit(2)
 
+    args.adapter_collectors = None
+    if adapter_pats is not None:
+        args.adapter_collectors = [adapters.Collector(adapter_pats, args.adaptersearch, args.adaptererr, args.adaptermargin) for _ in phrases]
+
     args.tract_collector = None
     if getattr(args, "tracts", False):
         unit = variants.primitive_root(args.pattern.upper())
@@ -565,6 +588,14 @@ def analysis_run(args, engines=None, engine_factory=None, wait_plots=True):
             tprint(f"named ends (k = {telo_phrase}): " + ", ".join(names))
             for line in endref.summary(r_stats, args.endminkmers, args.endrefminvotes, args.endrefratio):
                 tprint(line)
+
+    for (telo_phrase, _pattern, _slide), col in zip(phrases, args.adapter_collectors or []):
+        a_reads, a_summary, a_stats = col.finish(filenames)
+        adapters.write_csv(f"{args.outputDir}/adapters_{telo_phrase}.csv", adapters.READ_HEADER, a_reads)
+        adapters.write_csv(f"{args.outputDir}/adapter_summary_{telo_phrase}.csv", adapters.SUMMARY_HEADER, a_summary)
+        tprint(f"adapters (k = {telo_phrase}): {args.outputDir}/adapters_{telo_phrase}.csv, {args.outputDir}/adapter_summary_{telo_phrase}.csv")
+        for line in adapters.summary(col, a_stats):
+            tprint(line)
 
     if args.tract_collector is not None:
         tcol = args.tract_collector
@@ -743,6 +774,14 @@ def build_parser():
     parser.add_argument("--endrefmaxocc", metavar="INT", type=int, default=endref.DEFAULT_MAX_OCC, help="--endref: a k-mer that occurs more often than this over all reference ends takes no part (1..64)")
     parser.add_argument("--endrefminvotes", metavar="INT", type=int, default=endref.DEFAULT_MIN_VOTES, help="--endref: k-mer votes a read needs on its best diagonals to be named")
     parser.add_argument("--endrefratio", metavar="INT", type=int, default=endref.DEFAULT_RATIO, help="--endref: ... and how many times the votes of the runner-up diagonals")
+    parser.add_argument("--adapters", metavar="FILE|SEQ", nargs="+", default=None,
+                        help="MI355X build: locate adapters at the telomere end of every read with a called boundary -- a FASTA / FASTQ of named sequences, or "
+                             "literal sequences (adapter1 ...), 12..64 letters of ACGT each, 64 at most, given as they stand in front of the --pattern repeats; one row "
+                             "per read (adapters_{k}.csv: adapter, edit distance, where it ends, the length measured from there) and one per sequence "
+                             "(adapter_summary_{k}.csv)")
+    parser.add_argument("--adaptersearch", metavar="INT", type=int, default=adapters.DEFAULT_SEARCH, help="--adapters: bases at the telomere end that are searched (16..1024; never beyond maxlengthtelo)")
+    parser.add_argument("--adaptererr", metavar="FLOAT", type=float, default=adapters.DEFAULT_ERR, help="--adapters: edits allowed per letter of a sequence (a sequence of m letters: floor(err m) edits)")
+    parser.add_argument("--adaptermargin", metavar="INT", type=int, default=adapters.DEFAULT_MARGIN, help="--adapters: edits by which the best sequence must beat every other to name the read")
     parser.add_argument("--tracts", action="store_true",
                         help="MI355X build: map the telomere-repeat tracts of every WHOLE read, on both strands -- one row per tract (tracts.csv) and one per "
                              "read with a tract and its class: fusion, both_ends, interstitial, terminal (tract_reads.csv).  Runs the files as --twopass off")
