@@ -2,8 +2,8 @@
 // topsicle_amd/csrc/tps_anchor.h).
 //
 // Like emu_ends.cpp: the header compiled with -DTPS_EMU, the batch packed by the library's own packer, the argument checks of
-// tps_batch_end_window and tps_window_offsets (the library's own: ends_check, ends_check_reads, window_check_span,
-// window_check_reads, offsets_check, offsets_check_rows) with their return codes, the hit table built by the function the library
+// tps_batch_end_window and tps_window_offsets (the library's own: end_window_check,
+// window_offsets_check) with their return codes, the hit table built by the function the library
 // calls.  Never linked into the product.  emu_anchor_main.cpp includes this file and adds a main() for the stand-alone sanitizer run.
 #define TPS_EMU 1
 #include <cstdlib>
@@ -12,7 +12,7 @@
 #include <vector>
 
 #include "../../topsicle_amd/csrc/tps_anchor.h"
-#include "../../topsicle_amd/csrc/tps_pack.h"
+#include "emu_batch.h"
 
 static std::string g_err;
 extern "C" const char* emu_anchor_last_error() { return g_err.c_str(); }
@@ -22,42 +22,24 @@ extern "C" const char* emu_anchor_last_error() { return g_err.c_str(); }
 extern "C" int emu_end_window(const uint8_t* bases, const int64_t* offsets, int64_t n, uint64_t unit, int m, int k, const uint8_t* tails, const int32_t* begin,
                               const int32_t* end, int64_t n_reads, int span, int base_shift, uint32_t* codes, int64_t codes_len, uint32_t* keep,
                               int64_t keep_len) {
-    const char* why = "";
-    int rc = tps::ends_check(unit, m, k, tps::ENDS_MIN_BUCKETS, &why);
-    if (rc) { g_err = why; return rc; }
-    if ((rc = tps::window_check_span(span, k, &why))) { g_err = why; return rc; }
-    const int cdw = (span + 15) / 16, kdw = (span + 31) / 32;
-    if (n_reads != n || codes_len != n * cdw || keep_len != n * kdw) { g_err = "an array does not match the slot"; return TPS_E_ARG; }
+    tps::Why why;
+    if (const int rc = tps::end_window_check(n, unit, m, k, tails, begin, end, n_reads, span, codes, codes_len, keep, keep_len, &why)) { g_err = why.msg; return rc; }
     if (n == 0) return TPS_OK;
-    if (!tails || !begin || !end || !codes || !keep) { g_err = "null array"; return TPS_E_ARG; }
-    int64_t at = 0;
-    if ((rc = tps::ends_check_reads(tails, begin, end, n, &why, &at))) { g_err = why; return rc; }
-    if ((rc = tps::window_check_reads(begin, end, n, span, &why, &at))) { g_err = why; return rc; }
-    std::vector<tps_read_desc> desc((size_t)n);
-    const int64_t n_words = tps::pack_layout(offsets, n, desc.data());
-    const int64_t lead = 4 * (int64_t)(base_shift & 3);
-    std::vector<uint32_t> seq2buf((size_t)(n_words + lead + 8), 0xDEADBEEFu);
-    std::vector<uint16_t> invbuf((size_t)(n_words + lead + 8), (uint16_t)0xFFFFu);
-    for (int64_t i = 0; i < n; ++i) desc[(size_t)i].word_off += lead;
-    tps::pack_range(bases, offsets, 0, n, desc.data(), seq2buf.data(), invbuf.data());
+    const int cdw = (span + 15) / 16, kdw = (span + 31) / 32;
+    const emu::Batch batch(bases, offsets, n, base_shift);
     // exactly the rows: a sanitizer build sees a store past them (the kernel writes every entry)
     std::vector<uint32_t> co((size_t)codes_len, 0xEEEEEEEEu), kp((size_t)keep_len, 0xEEEEEEEEu);
     const int w = m < tps::TRACT_MAX_WORD ? m : tps::TRACT_MAX_WORD;
     std::vector<uint32_t> table((size_t)tps::tract_table_dw(w));
     tps::tract_hit_table(unit, m, table.data());
     tps::EndWindowArgs a{};
-    a.seq2 = seq2buf.data(); a.inv = invbuf.data(); a.desc = desc.data();
+    batch.set(a);
     a.table = table.data();
     a.tails = tails; a.begin = begin; a.end = end;
     a.codes = co.data(); a.keep = kp.data(); a.n_reads = n;
     a.w = w; a.k = k; a.cdw = cdw; a.kdw = kdw;
-    uint32_t* lds = nullptr;
-    if (posix_memalign((void**)&lds, 16, (size_t)tps::ENDS_LDS_DW * 4)) { g_err = "out of memory"; return TPS_E_ARG; }
-    for (int64_t r = 0; r < n; ++r) {
-        for (int i = 0; i < tps::ENDS_LDS_DW; ++i) lds[i] = 0xDEADBEEFu;        // LDS content is undefined at workgroup start
-        tps::end_window_read(a, r, lds, a.table);
-    }
-    free(lds);
+    emu::WaveLds lds(tps::ENDS_LDS_DW);
+    for (int64_t r = 0; r < n; ++r) tps::end_window_read(a, r, lds.poisoned(), a.table);
     memcpy(codes, co.data(), co.size() * 4);
     memcpy(keep, kp.data(), kp.size() * 4);
     return TPS_OK;
@@ -66,13 +48,9 @@ extern "C" int emu_end_window(const uint8_t* bases, const int64_t* offsets, int6
 // tps_window_offsets
 extern "C" int emu_window_offsets(const uint32_t* codes, const uint32_t* keep, const int32_t* length, const int32_t* ref, int64_t n, int span, int k,
                                   int32_t* offset, int32_t* votes, int32_t* second, int64_t out_len) {
-    const char* why = "";
-    int rc = tps::offsets_check(n, span, k, out_len, &why);
-    if (rc) { g_err = why; return rc; }
+    tps::Why why;
+    if (const int rc = tps::window_offsets_check(codes, keep, length, ref, n, span, k, offset, votes, second, out_len, &why)) { g_err = why.msg; return rc; }
     if (n == 0) return TPS_OK;
-    if (!codes || !keep || !length || !ref || !offset || !votes || !second) { g_err = "null array"; return TPS_E_ARG; }
-    int64_t at = 0;
-    if ((rc = tps::offsets_check_rows(length, ref, n, span, &why, &at))) { g_err = why; return rc; }
     const int cdw = (span + 15) / 16, kdw = (span + 31) / 32;
     // exactly the rows, as the device buffers are long: a sanitizer build sees a load past them
     std::vector<uint32_t> co(codes, codes + n * cdw), kp(keep, keep + n * kdw);
@@ -81,13 +59,8 @@ extern "C" int emu_window_offsets(const uint32_t* codes, const uint32_t* keep, c
     a.codes = co.data(); a.keep = kp.data(); a.length = length; a.ref = ref;
     a.offset = out.data(); a.votes = out.data() + n; a.second = out.data() + 2 * n;
     a.n = n; a.k = k; a.cdw = cdw; a.kdw = kdw;
-    uint32_t* lds = nullptr;
-    if (posix_memalign((void**)&lds, 16, (size_t)tps::OFFSETS_LDS_DW * 4)) { g_err = "out of memory"; return TPS_E_ARG; }
-    for (int64_t i = 0; i < n; ++i) {
-        for (int j = 0; j < tps::OFFSETS_LDS_DW; ++j) lds[j] = 0xDEADBEEFu;
-        tps::window_offsets_row(a, i, lds);
-    }
-    free(lds);
+    emu::WaveLds lds(tps::OFFSETS_LDS_DW);
+    for (int64_t i = 0; i < n; ++i) tps::window_offsets_row(a, i, lds.poisoned());
     memcpy(offset, a.offset, (size_t)n * 4);
     memcpy(votes, a.votes, (size_t)n * 4);
     memcpy(second, a.second, (size_t)n * 4);

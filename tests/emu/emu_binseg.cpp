@@ -30,14 +30,8 @@ extern "C" int emu_scan_lc(const char* pats, int P, int k, const uint8_t* bases,
     if (lc_cap_force > 0 && lc_cap_force < a.lc_cap) a.lc_cap = lc_cap_force;
     *lc_cap_out = a.lc_cap;
 
-    std::vector<tps_read_desc> desc((size_t)(n > 0 ? n : 1));
-    const int64_t n_words = tps::pack_layout(offsets, n, desc.data());
-    std::vector<uint32_t> seq2buf((size_t)(n_words + 8), 0xDEADBEEFu);
-    std::vector<uint16_t> invbuf((size_t)(n_words + 8), (uint16_t)0xFFFFu);
-    tps::pack_range(bases, offsets, 0, n, desc.data(), seq2buf.data(), invbuf.data());
-    a.seq2 = seq2buf.data();
-    a.inv = invbuf.data();
-    a.desc = desc.data();
+    const emu::Batch batch(bases, offsets, n);
+    batch.set(a);
     a.lut = lut.data();
     a.results = results;
     a.win_off = win_off.data();

@@ -2,7 +2,7 @@
 // topsicle_amd/csrc/tps_ends.h).
 //
 // Like emu_tract.cpp: the header compiled with -DTPS_EMU, the batch packed by the library's own packer, the argument checks of
-// tps_batch_end_sketch and tps_sketch_links (ends_check, ends_check_reads, links_check: the library's own) with their return codes,
+// tps_batch_end_sketch and tps_sketch_links (end_sketch_check, sketch_links_check: the library's own) with their return codes,
 // the hit table and the bucket-major copy built by the functions the library calls.  Never linked into the product.
 // emu_ends_main.cpp includes this file and adds a main() for the stand-alone sanitizer run.
 #define TPS_EMU 1
@@ -12,7 +12,7 @@
 #include <vector>
 
 #include "../../topsicle_amd/csrc/tps_ends.h"
-#include "../../topsicle_amd/csrc/tps_pack.h"
+#include "emu_batch.h"
 
 static std::string g_err;
 extern "C" const char* emu_ends_last_error() { return g_err.c_str(); }
@@ -25,51 +25,35 @@ extern "C" int emu_ends_piece() { return tps::ENDS_PIECE; }
 extern "C" int emu_end_sketch(const uint8_t* bases, const int64_t* offsets, int64_t n, uint64_t unit, int m, int k, int buckets, const uint8_t* tails,
                               const int32_t* begin, const int32_t* end, int64_t n_reads, int base_shift, uint32_t* sketch, int64_t sketch_len,
                               uint32_t* kept, int64_t kept_len) {
-    const char* why = "";
-    int rc = tps::ends_check(unit, m, k, buckets, &why);
-    if (rc) { g_err = why; return rc; }
-    if (n_reads != n || sketch_len != n * buckets || kept_len != n) { g_err = "an array does not match the slot"; return TPS_E_ARG; }
+    tps::Why why;
+    if (const int rc = tps::end_sketch_check(n, unit, m, k, buckets, tails, begin, end, n_reads, sketch, sketch_len, kept, kept_len, &why)) { g_err = why.msg; return rc; }
     if (n == 0) return TPS_OK;
-    if (!tails || !begin || !end || !sketch || !kept) { g_err = "null array"; return TPS_E_ARG; }
-    int64_t at = 0;
-    if ((rc = tps::ends_check_reads(tails, begin, end, n, &why, &at))) { g_err = why; return rc; }
-    std::vector<tps_read_desc> desc((size_t)n);
-    const int64_t n_words = tps::pack_layout(offsets, n, desc.data());
-    const int64_t lead = 4 * (int64_t)(base_shift & 3);
-    std::vector<uint32_t> seq2buf((size_t)(n_words + lead + 8), 0xDEADBEEFu);
-    std::vector<uint16_t> invbuf((size_t)(n_words + lead + 8), (uint16_t)0xFFFFu);
-    for (int64_t i = 0; i < n; ++i) desc[(size_t)i].word_off += lead;
-    tps::pack_range(bases, offsets, 0, n, desc.data(), seq2buf.data(), invbuf.data());
+    const emu::Batch batch(bases, offsets, n, base_shift);
     memset(sketch, 0xEE, (size_t)sketch_len * 4);                             // (the kernel writes every entry of these two)
     memset(kept, 0xEE, (size_t)kept_len * 4);
     const int w = m < tps::TRACT_MAX_WORD ? m : tps::TRACT_MAX_WORD;
     std::vector<uint32_t> table((size_t)tps::tract_table_dw(w));              // exactly the table: a sanitizer build sees a look-up past it
     tps::tract_hit_table(unit, m, table.data());
     tps::EndSketchArgs a{};
-    a.seq2 = seq2buf.data(); a.inv = invbuf.data(); a.desc = desc.data();
+    batch.set(a);
     a.table = table.data();
     a.tails = tails; a.begin = begin; a.end = end;
     a.sketch = sketch; a.kept = kept; a.n_reads = n;
     a.w = w; a.k = k; a.buckets = buckets; a.shift = 32 - tps::ends_log2(buckets);
-    // exactly one wave's slice, 16-byte aligned like LDS: a sanitizer build sees every access past it
-    uint32_t* lds = nullptr;
-    if (posix_memalign((void**)&lds, 16, (size_t)tps::ENDS_LDS_DW * 4)) { g_err = "out of memory"; return TPS_E_ARG; }
-    for (int64_t r = 0; r < n; ++r) {
-        for (int i = 0; i < tps::ENDS_LDS_DW; ++i) lds[i] = 0xDEADBEEFu;        // LDS content is undefined at workgroup start
-        tps::end_sketch_read(a, r, lds, a.table);
-    }
-    free(lds);
+    emu::WaveLds lds(tps::ENDS_LDS_DW);
+    for (int64_t r = 0; r < n; ++r) tps::end_sketch_read(a, r, lds.poisoned(), a.table);
     return TPS_OK;
 }
 
 // tps_sketch_links
 extern "C" int emu_sketch_links(const uint32_t* sketch, int64_t n, int buckets, int64_t sketch_len, int min_match, int max_links, int32_t* degree,
                                 int64_t degree_len, int32_t* links, int64_t links_len, int32_t* matches, int64_t matches_len) {
-    const char* why = "";
-    const int rc = tps::links_check(n, buckets, sketch_len, min_match, max_links, degree_len, links_len, matches_len, &why);
-    if (rc) { g_err = why; return rc; }
+    tps::Why why;
+    if (const int rc = tps::sketch_links_check(sketch, n, buckets, sketch_len, min_match, max_links, degree, degree_len, links, links_len, matches, matches_len, &why)) {
+        g_err = why.msg;
+        return rc;
+    }
     if (n == 0) return TPS_OK;
-    if (!sketch || !degree || !links || !matches) { g_err = "null array"; return TPS_E_ARG; }
     std::vector<uint32_t> t((size_t)(n * buckets));                           // exactly the copy: a sanitizer build sees a load past it
     tps::links_transpose(sketch, n, buckets, t.data());
     memset(degree, 0xEE, (size_t)degree_len * 4);                             // (the kernel writes every entry)

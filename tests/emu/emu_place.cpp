@@ -1,7 +1,7 @@
 // TEST INFRASTRUCTURE ONLY -- sequential host emulation of the placement kernel (window_place_row, topsicle_amd/csrc/tps_place.h).
 //
-// Like emu_anchor.cpp: the header compiled with -DTPS_EMU, the argument checks of tps_window_place (the library's own: place_check,
-// place_check_rows) with their return codes, the index built by the function the library calls (place_index_build).  Never linked
+// Like emu_anchor.cpp: the header compiled with -DTPS_EMU, the argument checks of tps_window_place (the library's own:
+// window_place_check) with its return codes, the index built by the function the library calls (place_index_build).  Never linked
 // into the product.  emu_place_main.cpp includes this file and adds a main() for the stand-alone sanitizer run.
 #define TPS_EMU 1
 #include <cstdlib>
@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../topsicle_amd/csrc/tps_place.h"
+#include "emu_batch.h"
 
 static std::string g_place_err;
 static int g_place_bits = 0;
@@ -21,15 +22,13 @@ extern "C" int emu_place_dir_bits() { return g_place_bits; }
 extern "C" int emu_window_place(const uint32_t* codes, int64_t codes_len, const uint32_t* keep, int64_t keep_len, const int32_t* length, int64_t n,
                                 const uint32_t* ref_codes, int64_t ref_codes_len, const uint32_t* ref_keep, int64_t ref_keep_len, const int32_t* ref_length,
                                 int n_ref, int span, int k, int max_occ, int32_t* outs, int64_t out_len) {
-    const char* why = "";
-    int rc = tps::place_check(n, n_ref, span, k, max_occ, codes_len, keep_len, ref_codes_len, ref_keep_len, out_len, &why);
-    if (rc) { g_place_err = why; return rc; }
-    if (!ref_codes || !ref_keep || !ref_length) { g_place_err = "null array"; return TPS_E_ARG; }
-    int64_t at = 0;
-    if ((rc = tps::place_check_rows(ref_length, n_ref, span, &why, &at))) { g_place_err = why; return rc; }
+    tps::Why why;
+    if (const int rc = tps::window_place_check(codes, codes_len, keep, keep_len, length, n, ref_codes, ref_codes_len, ref_keep, ref_keep_len, ref_length, n_ref,
+                                               span, k, max_occ, outs != nullptr, out_len, &why)) {
+        g_place_err = why.msg;
+        return rc;
+    }
     if (n == 0) return TPS_OK;
-    if (!codes || !keep || !length || !outs) { g_place_err = "null array"; return TPS_E_ARG; }
-    if ((rc = tps::place_check_rows(length, n, span, &why, &at))) { g_place_err = why; return rc; }
     const int cdw = (span + 15) / 16, kdw = (span + 31) / 32;
     // exactly the rows and the index, as the device buffers are long: a sanitizer build sees a load past them
     std::vector<uint32_t> rc_(ref_codes, ref_codes + (int64_t)n_ref * cdw), rk_(ref_keep, ref_keep + (int64_t)n_ref * kdw);
@@ -47,13 +46,8 @@ extern "C" int emu_window_place(const uint32_t* codes, int64_t codes_len, const 
     a.out = out.data();
     a.n = n;
     a.R = n_ref; a.k = k; a.cdw = cdw; a.kdw = kdw; a.shift = 32 - ix.bits;
-    uint32_t* lds = nullptr;
-    if (posix_memalign((void**)&lds, 16, (size_t)tps::PLACE_LDS_DW * 4)) { g_place_err = "out of memory"; return TPS_E_ARG; }
-    for (int64_t i = 0; i < n; ++i) {
-        for (int j = 0; j < tps::PLACE_LDS_DW; ++j) lds[j] = 0xDEADBEEFu;           // LDS content is undefined at workgroup start
-        tps::window_place_row(a, i, lds);
-    }
-    free(lds);
+    emu::WaveLds lds(tps::PLACE_LDS_DW);
+    for (int64_t i = 0; i < n; ++i) tps::window_place_row(a, i, lds.poisoned());
     memcpy(outs, out.data(), out.size() * 4);
     return TPS_OK;
 }

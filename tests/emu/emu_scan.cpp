@@ -12,7 +12,7 @@
 #include <vector>
 
 #include "../../topsicle_amd/csrc/tps_device.h"
-#include "../../topsicle_amd/csrc/tps_pack.h"
+#include "emu_batch.h"
 #include "../../topsicle_amd/csrc/tps_plan.h"
 
 static std::string g_err;
@@ -72,19 +72,8 @@ extern "C" int emu_scan(const char* pats, int P, int k, const uint8_t* bases, co
     err = tps::plan_geometry(a, *prm, k, P, lay.max_nwin, lds_budget_bytes / 4, knobs_with(spans_pref, force_generic));
     if (!err.empty()) { g_err = err; return TPS_E_CAPACITY; }
 
-    // the packed batch, exactly as the library keeps it in HBM (tps_pack.h).  Words the layout does not own are filled
-    // with garbage: the kernel must never let them count.  base_shift moves the batch inside its buffer by whole quads
-    // (the device only ever sees 16-byte aligned quads).
-    std::vector<tps_read_desc> desc((size_t)(n > 0 ? n : 1));
-    const int64_t n_words = tps::pack_layout(offsets, n, desc.data());
-    const int64_t lead = 4 * (int64_t)(base_shift & 3);
-    std::vector<uint32_t> seq2buf((size_t)(n_words + lead + 8), 0xDEADBEEFu);
-    std::vector<uint16_t> invbuf((size_t)(n_words + lead + 8), (uint16_t)0xFFFFu);
-    for (int64_t i = 0; i < n; ++i) desc[(size_t)i].word_off += lead;
-    tps::pack_range(bases, offsets, 0, n, desc.data(), seq2buf.data(), invbuf.data());
-    a.seq2 = seq2buf.data();
-    a.inv = invbuf.data();
-    a.desc = desc.data();
+    const emu::Batch batch(bases, offsets, n, base_shift);       // (the packed batch as the library keeps it in HBM, garbage around it)
+    batch.set(a);
     a.tails_in = ((prm->flags & TPS_F_TAILS_IN) && !(prm->flags & TPS_F_STEP1)) ? tails : nullptr;
     a.lut = lut.data();
     a.results = results;
@@ -168,26 +157,20 @@ extern "C" int emu_scan(const char* pats, int P, int k, const uint8_t* bases, co
 
 // tps_batch_kmer_followers through the emulation: picks[n][2][n_fwd][pw], hist[2][n_fwd][4^follow + 1] (may be NULL)
 extern "C" int emu_followers(const char* pats, int P, int k, const uint8_t* bases, const int64_t* offsets, int64_t n, int n_fwd, int follow,
-                             int lo, int hi, int min_len, uint32_t* picks, unsigned long long* hist) {
+                             int lo, int hi, int min_len, uint32_t* picks, int64_t picks_words, unsigned long long* hist, int64_t hist_len) {
     std::vector<uint32_t> lut;
     tps::FollowArgs a{};
     std::string err = tps::build_patterns(pats, P, k, lut, a.pat);
     if (!err.empty()) { g_err = err; return TPS_E_PATTERN; }
-    if (n_fwd < 1 || n_fwd > 15 || 2 * n_fwd > P || follow < 0 || follow > 8 || lo < 0 || hi <= lo || hi - lo > tps::FOLLOW_MAX_SPAN) { g_err = "bad arguments"; return TPS_E_ARG; }
-    std::vector<tps_read_desc> desc((size_t)(n > 0 ? n : 1));
-    const int64_t n_words = tps::pack_layout(offsets, n, desc.data());
-    std::vector<uint32_t> seq2buf((size_t)(n_words + 8), 0xDEADBEEFu);
-    std::vector<uint16_t> invbuf((size_t)(n_words + 8), (uint16_t)0xFFFFu);
-    tps::pack_range(bases, offsets, 0, n, desc.data(), seq2buf.data(), invbuf.data());
-    a.seq2 = seq2buf.data(); a.inv = invbuf.data(); a.desc = desc.data(); a.lut = lut.data();
+    tps::Why why;
+    if (const int rc = tps::followers_check(P, n, n_fwd, follow, lo, hi, picks, picks_words, hist, hist_len, &why)) { g_err = why.msg; return rc; }
+    const emu::Batch batch(bases, offsets, n);
+    batch.set(a);
+    a.lut = lut.data();
     a.picks = picks; a.hist = hist; a.n_reads = n;
     a.n_fwd = n_fwd; a.follow = follow; a.lo = lo; a.hi = hi; a.min_len = min_len; a.pw = (hi - lo + 31) / 32; a.nbins = (1 << (2 * follow)) + 1;
-    std::vector<uint32_t> ldsbuf((size_t)tps::FOLLOW_LDS_DW + 16);
-    uint32_t* lds = (uint32_t*)(((uintptr_t)ldsbuf.data() + 15) & ~(uintptr_t)15);
-    for (int64_t r = 0; r < n; ++r) {
-        for (int i = 0; i < tps::FOLLOW_LDS_DW; ++i) lds[i] = 0xDEADBEEFu;
-        tps::followers_read(a, r, lds);
-    }
+    emu::WaveLds lds(tps::FOLLOW_LDS_DW);
+    for (int64_t r = 0; r < n; ++r) tps::followers_read(a, r, lds.poisoned());
     return TPS_OK;
 }
 

@@ -1,7 +1,7 @@
 // TEST INFRASTRUCTURE ONLY -- sequential host emulation of the tract map kernel (tract_read, topsicle_amd/csrc/tps_tract.h).
 //
 // Like emu_variant.cpp: the header compiled with -DTPS_EMU, the batch packed by the library's own packer, the argument checks of
-// tps_batch_tract_map (tract_check, the library's own) with its return codes, the hit table built by the function the library calls.
+// tps_batch_tract_map (tract_map_check, the library's own) with its return codes, the hit table built by the function the library calls.
 // Never linked into the product.  emu_tract_main.cpp includes this file and adds a main() for the stand-alone sanitizer run.
 #define TPS_EMU 1
 #include <cstdlib>
@@ -10,7 +10,7 @@
 #include <vector>
 
 #include "../../topsicle_amd/csrc/tps_tract.h"
-#include "../../topsicle_amd/csrc/tps_pack.h"
+#include "emu_batch.h"
 
 static std::string g_err;
 extern "C" const char* emu_tract_last_error() { return g_err.c_str(); }
@@ -30,19 +30,13 @@ extern "C" int emu_tract_table(uint64_t unit, int m, uint32_t* tab) {
 extern "C" int emu_tract_map(const uint8_t* bases, const int64_t* offsets, int64_t n, uint64_t unit, int m, int block, int min_hits, int gap,
                              int min_blocks, int max_tracts, int base_shift, tps_tract* tracts, int64_t tracts_len, int32_t* found,
                              int64_t found_len, uint32_t* totals, int64_t totals_len) {
-    const char* why = "";
-    const int rc = tps::tract_check(unit, m, block, min_hits, gap, min_blocks, max_tracts, &why);
-    if (rc) { g_err = why; return rc; }
-    if (tracts_len != n * 2 * max_tracts || found_len != n * 2 || totals_len != n * 4) { g_err = "an output array does not match the slot"; return TPS_E_ARG; }
+    tps::Why why;
+    if (const int rc = tps::tract_map_check(n, unit, m, block, min_hits, gap, min_blocks, max_tracts, tracts, tracts_len, found, found_len, totals, totals_len, &why)) {
+        g_err = why.msg;
+        return rc;
+    }
     if (n == 0) return TPS_OK;
-    if (!tracts || !found || !totals) { g_err = "null output"; return TPS_E_ARG; }
-    std::vector<tps_read_desc> desc((size_t)n);
-    const int64_t n_words = tps::pack_layout(offsets, n, desc.data());
-    const int64_t lead = 4 * (int64_t)(base_shift & 3);
-    std::vector<uint32_t> seq2buf((size_t)(n_words + lead + 8), 0xDEADBEEFu);
-    std::vector<uint16_t> invbuf((size_t)(n_words + lead + 8), (uint16_t)0xFFFFu);
-    for (int64_t i = 0; i < n; ++i) desc[(size_t)i].word_off += lead;
-    tps::pack_range(bases, offsets, 0, n, desc.data(), seq2buf.data(), invbuf.data());
+    const emu::Batch batch(bases, offsets, n, base_shift);
     memset(tracts, 0, (size_t)tracts_len * sizeof(tps_tract));                // (the library's hipMemsetAsync)
     memset(found, 0xEE, (size_t)found_len * 4);                               // (the kernel writes every entry of these two)
     memset(totals, 0xEE, (size_t)totals_len * 4);
@@ -50,17 +44,11 @@ extern "C" int emu_tract_map(const uint8_t* bases, const int64_t* offsets, int64
     std::vector<uint32_t> table((size_t)tps::tract_table_dw(w));              // exactly the table: a sanitizer build sees a look-up past it
     tps::tract_hit_table(unit, m, table.data());
     tps::TractArgs a{};
-    a.seq2 = seq2buf.data(); a.inv = invbuf.data(); a.desc = desc.data();
+    batch.set(a);
     a.table = table.data();
     a.tracts = tracts; a.found = found; a.totals = totals; a.n_reads = n;
     a.w = w; a.block = block; a.min_hits = min_hits; a.gap = gap; a.min_blocks = min_blocks; a.max_tracts = max_tracts;
-    // exactly one wave's slice, 16-byte aligned like LDS: a sanitizer build sees every access past it
-    uint32_t* lds = nullptr;
-    if (posix_memalign((void**)&lds, 16, (size_t)tps::TRACT_LDS_DW * 4)) { g_err = "out of memory"; return TPS_E_ARG; }
-    for (int64_t r = 0; r < n; ++r) {
-        for (int i = 0; i < tps::TRACT_LDS_DW; ++i) lds[i] = 0xDEADBEEFu;       // LDS content is undefined at workgroup start
-        tps::tract_read(a, r, lds, a.table);
-    }
-    free(lds);
+    emu::WaveLds lds(tps::TRACT_LDS_DW);
+    for (int64_t r = 0; r < n; ++r) tps::tract_read(a, r, lds.poisoned(), a.table);
     return TPS_OK;
 }

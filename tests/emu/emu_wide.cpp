@@ -10,7 +10,7 @@
 
 #include "../../topsicle_amd/csrc/tps_wide.h"
 #include "../../topsicle_amd/csrc/tps_wide_plan.h"
-#include "../../topsicle_amd/csrc/tps_pack.h"
+#include "emu_batch.h"
 #include "../../topsicle_amd/csrc/tps_plan.h"
 
 static std::string g_err;
@@ -62,16 +62,8 @@ extern "C" int emu_wide_scan(const char* pats, int P, int k, const uint8_t* base
     const std::vector<int64_t>& win_off = lay.win_off;
     if (win_off_out) memcpy(win_off_out, win_off.data(), (size_t)(n + 1) * 8);
 
-    std::vector<tps_read_desc> desc((size_t)(n > 0 ? n : 1));
-    const int64_t n_words = tps::pack_layout(offsets, n, desc.data());
-    const int64_t lead = 4 * (int64_t)(base_shift & 3);
-    std::vector<uint32_t> seq2buf((size_t)(n_words + lead + 8), 0xDEADBEEFu);
-    std::vector<uint16_t> invbuf((size_t)(n_words + lead + 8), (uint16_t)0xFFFFu);
-    for (int64_t i = 0; i < n; ++i) desc[(size_t)i].word_off += lead;
-    tps::pack_range(bases, offsets, 0, n, desc.data(), seq2buf.data(), invbuf.data());
-    a.seq2 = seq2buf.data();
-    a.inv = invbuf.data();
-    a.desc = desc.data();
+    const emu::Batch batch(bases, offsets, n, base_shift);
+    batch.set(a);
     a.tails_in = ((prm->flags & TPS_F_TAILS_IN) && !(prm->flags & TPS_F_STEP1)) ? tails : nullptr;
     a.results = results;
     a.c_start = (prm->flags & TPS_F_STEP1) ? c_start : nullptr;
@@ -87,14 +79,10 @@ extern "C" int emu_wide_scan(const char* pats, int P, int k, const uint8_t* base
     memcpy(img_al, img.data(), (size_t)tps::WIDE_IMG_DW * 4);
     a.img = img_al;
     // exactly the planned wave slice: the sanitizer build sees every access past it
-    const size_t dw = (size_t)tps::wide_lds_dwords(a);
-    uint32_t* lds = nullptr;
-    if (posix_memalign((void**)&lds, 16, dw * 4)) { g_err = "out of memory"; return TPS_E_ARG; }
+    emu::WaveLds lds((int)tps::wide_lds_dwords(a));
     for (int64_t slot = 0; slot < n; ++slot) {
         const int64_t r = lay.order.empty() ? slot : lay.order[(size_t)slot];       // (results do not depend on the order)
-        for (size_t i = 0; i < dw; ++i) lds[i] = 0xDEADBEEFu;       // LDS content is undefined at workgroup start
-        tps::wide_read(a, r, lds, img_al);
+        tps::wide_read(a, r, lds.poisoned(), img_al);
     }
-    free(lds);
     return TPS_OK;
 }

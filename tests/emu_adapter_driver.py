@@ -1,33 +1,22 @@
 """Test helper: builds and drives tests/emu/emu_adapter.cpp (host emulation of the adapter kernel, csrc/tps_adapter.h), and builds
 tests/emu/emu_adapter_main.cpp, the stand-alone program the sanitizers run."""
 import ctypes as C
-import os
 
 import numpy as np
 
-from emu_ends_driver import FLAGS, _compile, _fresh
+import emu_build
 from topsicle_amd import adapters, hiplib
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "emu", "emu_adapter.cpp")
-MAIN_SRC = os.path.join(HERE, "emu", "emu_adapter_main.cpp")
-DEPS = [SRC] + [os.path.join(HERE, "..", "topsicle_amd", "csrc", f) for f in ("tps_adapter.h", "tps_device.h", "tps_wave.h", "tps_pack.h")] + \
-       [os.path.join(HERE, "..", "include", "topsicle_hip.h")]
+DEPS = emu_build.deps("emu_adapter.cpp", headers=("tps_adapter.h", "tps_device.h", "tps_wave.h", "tps_pack.h"))
 
 
 def build():
-    out = os.path.join(HERE, "emu", "_build", "libtps_emu_adapter.so")
-    if _fresh(out, DEPS):
-        return out
-    return _compile(["g++", "-O2"] + FLAGS + ["-shared", "-fPIC", SRC], out)
+    return emu_build.shared("libtps_emu_adapter.so", "emu_adapter.cpp", DEPS)
 
 
 def build_main():
     """The stand-alone program (its own main, nothing loaded into Python) under -fsanitize=address,undefined."""
-    out = os.path.join(HERE, "emu", "_build", "emu_adapter_main_asan")
-    if _fresh(out, DEPS + [MAIN_SRC]):
-        return out
-    return _compile(["g++", "-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"] + FLAGS + [MAIN_SRC], out)
+    return emu_build.program("emu_adapter_main_asan", "emu_adapter_main.cpp", DEPS)
 
 
 _lib = None

@@ -1,33 +1,22 @@
 """Test helper: builds and drives tests/emu/emu_anchor.cpp (host emulation of the window and offset kernels, csrc/tps_anchor.h), and
 builds tests/emu/emu_anchor_main.cpp, the stand-alone program the sanitizers run."""
 import ctypes as C
-import os
 
 import numpy as np
 
-from emu_ends_driver import FLAGS, _compile, _fresh
+import emu_build
 from topsicle_amd import hiplib, variants
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "emu", "emu_anchor.cpp")
-MAIN_SRC = os.path.join(HERE, "emu", "emu_anchor_main.cpp")
-DEPS = [SRC] + [os.path.join(HERE, "..", "topsicle_amd", "csrc", f) for f in ("tps_anchor.h", "tps_ends.h", "tps_tract.h", "tps_device.h", "tps_wave.h", "tps_pack.h")] + \
-       [os.path.join(HERE, "..", "include", "topsicle_hip.h")]
+DEPS = emu_build.deps("emu_anchor.cpp", headers=("tps_anchor.h", "tps_ends.h", "tps_tract.h", "tps_device.h", "tps_wave.h", "tps_pack.h"))
 
 
 def build():
-    out = os.path.join(HERE, "emu", "_build", "libtps_emu_anchor.so")
-    if _fresh(out, DEPS):
-        return out
-    return _compile(["g++", "-O2"] + FLAGS + ["-shared", "-fPIC", SRC], out)
+    return emu_build.shared("libtps_emu_anchor.so", "emu_anchor.cpp", DEPS)
 
 
 def build_main():
     """The stand-alone program (its own main, nothing loaded into Python) under -fsanitize=address,undefined."""
-    out = os.path.join(HERE, "emu", "_build", "emu_anchor_main_asan")
-    if _fresh(out, DEPS + [MAIN_SRC]):
-        return out
-    return _compile(["g++", "-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"] + FLAGS + [MAIN_SRC], out)
+    return emu_build.program("emu_anchor_main_asan", "emu_anchor_main.cpp", DEPS)
 
 
 _lib = None

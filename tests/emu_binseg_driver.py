@@ -3,17 +3,14 @@ exports every emulation counter (csrc/tps_wave.h: which change-point finish ran,
 scan that hands back the candidate-sum scratch blocks."""
 import contextlib
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
+import emu_build
 import emu_driver as emu
 from topsicle_amd import hiplib
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "emu", "emu_binseg.cpp")
-DEPS = [SRC] + emu.DEPS
+DEPS = emu_build.deps("emu_binseg.cpp") + emu.DEPS
 
 # counters (csrc/tps_wave.h)
 EXACT_TOURNAMENTS, LANE_CANDS, ONE_LANE_FINISH, WAVE_FINISH, CROWDED, F64_ROUTE = 4, 7, 8, 9, 10, 11
@@ -22,13 +19,7 @@ _lib = None
 
 
 def build():
-    out = os.path.join(HERE, "emu", "_build", "libtps_emu_binseg.so")
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    if os.path.exists(out) and all(os.path.getmtime(out) >= os.path.getmtime(d) for d in DEPS):
-        return out
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas", "-Wno-unused-variable",
-                           "-shared", "-fPIC", "-o", out, SRC])
-    return out
+    return emu_build.shared("libtps_emu_binseg.so", "emu_binseg.cpp", DEPS)
 
 
 def lib():

@@ -1,28 +1,17 @@
 """Test helper: builds and drives tests/emu (host emulation of the HIP kernel source)."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
+import emu_build
 from topsicle_amd import hiplib
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "emu", "emu_scan.cpp")
-DEPS = [SRC] + [os.path.join(HERE, "..", "topsicle_amd", "csrc", f) for f in ("tps_device.h", "tps_wave.h", "tps_plan.h", "tps_pack.h")] + \
-       [os.path.join(HERE, "..", "include", "topsicle_hip.h")]
+DEPS = emu_build.deps("emu_scan.cpp", headers=("tps_device.h", "tps_wave.h", "tps_plan.h", "tps_pack.h"))
 
 
 def build(asan=False):
-    out = os.path.join(HERE, "emu", "_build", "libtps_emu_asan.so" if asan else "libtps_emu.so")
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    if os.path.exists(out) and all(os.path.getmtime(out) >= os.path.getmtime(d) for d in DEPS):
-        return out
-    cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas", "-shared", "-fPIC"]
-    if asan:
-        cmd += ["-O1", "-fno-omit-frame-pointer", "-fsanitize=address,undefined"]      # (-O2 -g takes three times as long to compile)
-    subprocess.check_call(cmd + ["-o", out, SRC])
-    return out
+    return emu_build.shared("libtps_emu_asan.so" if asan else "libtps_emu.so", "emu_scan.cpp", DEPS, asan)
 
 
 _lib = None
@@ -74,14 +63,16 @@ def scan(patterns, seqs, prm, tails=None, spans_pref=0, lds_budget=160 * 1024, b
 
 
 def followers(patterns, seqs, n_fwd, follow, lo=100, hi=2000, min_len=0):
-    """(picks uint32[n, 2, n_fwd, pw], hist int64[2, n_fwd, 4**follow + 1]) like HipScanner.kmer_followers."""
+    """(picks uint32[n, 2, n_fwd, pw], hist int64[2, n_fwd, 4**follow + 1]) like HipScanner.kmer_followers; raises RuntimeError with
+    the C ABI's return code and message where tps_batch_kmer_followers refuses (the arrays are stand-ins then)."""
     L = lib()
     bases, offsets = hiplib.pack_reads(seqs)
     n, P, k = len(seqs), len(patterns), len(patterns[0])
-    pw = (hi - lo + 31) // 32
-    picks = np.zeros((n, 2, n_fwd, pw), np.uint32)
-    hist = np.zeros((2, n_fwd, 4 ** follow + 1), np.uint64)
-    rc = L.emu_followers("".join(patterns).encode(), P, k, _p(bases), _p(offsets), C.c_int64(n), n_fwd, follow, lo, hi, min_len, _p(picks), _p(hist))
+    pw = max((hi - lo + 31) // 32, 1)
+    picks = np.zeros((n, 2, max(n_fwd, 1), pw), np.uint32)
+    hist = np.zeros((2, max(n_fwd, 1), 4 ** follow + 1 if 0 <= follow <= 8 else 1), np.uint64)
+    rc = L.emu_followers("".join(patterns).encode(), P, k, _p(bases), _p(offsets), C.c_int64(n), n_fwd, follow, lo, hi, min_len, _p(picks),
+                         C.c_int64(picks.size), _p(hist), C.c_int64(hist.size))
     if rc != 0:
         raise RuntimeError(f"emu_followers rc={rc}: {L.emu_last_error().decode()}")
     return picks, hist.astype(np.int64)

@@ -1,30 +1,17 @@
 """Test helper: builds and drives tests/emu/emu_follow_wide.cpp (host emulation of the wide followers kernel, csrc/tps_wide.h)."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
+import emu_build
 from topsicle_amd import hiplib
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "emu", "emu_follow_wide.cpp")
-DEPS = [SRC] + [os.path.join(HERE, "..", "topsicle_amd", "csrc", f) for f in ("tps_wide.h", "tps_wide_plan.h", "tps_device.h", "tps_wave.h", "tps_plan.h", "tps_pack.h")] + \
-       [os.path.join(HERE, "..", "include", "topsicle_hip.h")]
+DEPS = emu_build.deps("emu_follow_wide.cpp", headers=("tps_wide.h", "tps_wide_plan.h", "tps_device.h", "tps_wave.h", "tps_plan.h", "tps_pack.h"))
 
 
 def build(asan=False):
-    out = os.path.join(HERE, "emu", "_build", "libtps_emu_follow_wide_asan.so" if asan else "libtps_emu_follow_wide.so")
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    if os.path.exists(out) and all(os.path.getmtime(out) >= os.path.getmtime(d) for d in DEPS):
-        return out
-    cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas", "-shared", "-fPIC"]
-    if asan:
-        cmd += ["-O1", "-fno-omit-frame-pointer", "-fsanitize=address,undefined"]
-    tmp = out + ".tmp%d" % os.getpid()
-    subprocess.check_call(cmd + ["-o", tmp, SRC])
-    os.replace(tmp, out)
-    return out
+    return emu_build.shared("libtps_emu_follow_wide_asan.so" if asan else "libtps_emu_follow_wide.so", "emu_follow_wide.cpp", DEPS, asan)
 
 
 _lib = None
@@ -54,7 +41,7 @@ def followers_wide(patterns, seqs, n_fwd, follow, lo=100, hi=2000, min_len=0, wa
     # (asked for beyond 8 followers: a one-counter stand-in, so that the refusal is the kernel driver's own)
     hist = (np.zeros((2, max(n_fwd, 1), 4 ** follow + 1), np.uint64) if 0 <= follow <= 8 else np.zeros(1, np.uint64)) if want_hist else None
     rc = L.emu_followers_wide("".join(patterns).encode(), P, k, _p(bases), _p(offsets), C.c_int64(n), n_fwd, follow, lo, hi, min_len,
-                              base_shift, _p(picks), _p(hist))
+                              base_shift, _p(picks), C.c_int64(picks.size), _p(hist), C.c_int64(0 if hist is None else hist.size))
     if rc != 0:
         raise hiplib.TopsicleHipError(f"emu_followers_wide rc={rc}: {L.emu_follow_wide_last_error().decode()}")
     return picks, (None if hist is None else hist.astype(np.int64))

@@ -1,33 +1,22 @@
 """Test helper: builds and drives tests/emu/emu_place.cpp (host emulation of the placement kernel, csrc/tps_place.h), and builds
 tests/emu/emu_place_main.cpp, the stand-alone program the sanitizers run."""
 import ctypes as C
-import os
 
 import numpy as np
 
-from emu_ends_driver import FLAGS, _compile, _fresh
+import emu_build
 from topsicle_amd import hiplib
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "emu", "emu_place.cpp")
-MAIN_SRC = os.path.join(HERE, "emu", "emu_place_main.cpp")
-DEPS = [SRC] + [os.path.join(HERE, "..", "topsicle_amd", "csrc", f) for f in ("tps_place.h", "tps_anchor.h", "tps_ends.h", "tps_tract.h", "tps_device.h", "tps_wave.h")] + \
-       [os.path.join(HERE, "..", "include", "topsicle_hip.h")]
+DEPS = emu_build.deps("emu_place.cpp", headers=("tps_place.h", "tps_anchor.h", "tps_ends.h", "tps_tract.h", "tps_device.h", "tps_wave.h"))
 
 
 def build():
-    out = os.path.join(HERE, "emu", "_build", "libtps_emu_place.so")
-    if _fresh(out, DEPS):
-        return out
-    return _compile(["g++", "-O2"] + FLAGS + ["-shared", "-fPIC", SRC], out)
+    return emu_build.shared("libtps_emu_place.so", "emu_place.cpp", DEPS)
 
 
 def build_main():
     """The stand-alone program (its own main, nothing loaded into Python) under -fsanitize=address,undefined."""
-    out = os.path.join(HERE, "emu", "_build", "emu_place_main_asan")
-    if _fresh(out, DEPS + [MAIN_SRC]):
-        return out
-    return _compile(["g++", "-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"] + FLAGS + [MAIN_SRC], out)
+    return emu_build.program("emu_place_main_asan", "emu_place_main.cpp", DEPS)
 
 
 _lib = None

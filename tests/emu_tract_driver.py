@@ -1,46 +1,22 @@
 """Test helper: builds and drives tests/emu/emu_tract.cpp (host emulation of the tract map kernel, csrc/tps_tract.h), and builds
 tests/emu/emu_tract_main.cpp, the stand-alone program the sanitizers run."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
+import emu_build
 from topsicle_amd import hiplib, variants
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "emu", "emu_tract.cpp")
-MAIN_SRC = os.path.join(HERE, "emu", "emu_tract_main.cpp")
-DEPS = [SRC] + [os.path.join(HERE, "..", "topsicle_amd", "csrc", f) for f in ("tps_tract.h", "tps_device.h", "tps_wave.h", "tps_pack.h")] + \
-       [os.path.join(HERE, "..", "include", "topsicle_hip.h")]
-FLAGS = ["-std=c++17", "-Wall", "-Wno-unused-function", "-Wno-unused-variable", "-Wno-unknown-pragmas"]
-
-
-def _fresh(out, deps):
-    return os.path.exists(out) and all(os.path.getmtime(out) >= os.path.getmtime(d) for d in deps)
-
-
-def _compile(cmd, out):
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    tmp = out + ".tmp%d" % os.getpid()
-    subprocess.check_call(cmd + ["-o", tmp])
-    os.replace(tmp, out)
-    return out
+DEPS = emu_build.deps("emu_tract.cpp", headers=("tps_tract.h", "tps_device.h", "tps_wave.h", "tps_pack.h"))
 
 
 def build():
-    out = os.path.join(HERE, "emu", "_build", "libtps_emu_tract.so")
-    if _fresh(out, DEPS):
-        return out
-    return _compile(["g++", "-O2"] + FLAGS + ["-shared", "-fPIC", SRC], out)
+    return emu_build.shared("libtps_emu_tract.so", "emu_tract.cpp", DEPS)
 
 
 def build_main():
     """The stand-alone program (its own main, nothing loaded into Python) under -fsanitize=address,undefined."""
-    out = os.path.join(HERE, "emu", "_build", "emu_tract_main_asan")
-    if _fresh(out, DEPS + [MAIN_SRC]):
-        return out
-    return _compile(["g++", "-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"] + FLAGS + [MAIN_SRC], out)
+    return emu_build.program("emu_tract_main_asan", "emu_tract_main.cpp", DEPS)
 
 
 _lib = None

@@ -1,43 +1,22 @@
 """Test helper: builds and drives tests/emu/emu_wide.cpp (host emulation of the wide-table scan kernel, csrc/tps_wide.h)."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
+import emu_build
 from topsicle_amd import hiplib
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "emu", "emu_wide.cpp")
-MAIN_SRC = os.path.join(HERE, "emu", "emu_wide_main.cpp")
-DEPS = [SRC] + [os.path.join(HERE, "..", "topsicle_amd", "csrc", f) for f in ("tps_wide.h", "tps_wide_plan.h", "tps_device.h", "tps_wave.h", "tps_plan.h", "tps_pack.h")] + \
-       [os.path.join(HERE, "..", "include", "topsicle_hip.h")]
+DEPS = emu_build.deps("emu_wide.cpp", headers=("tps_wide.h", "tps_wide_plan.h", "tps_device.h", "tps_wave.h", "tps_plan.h", "tps_pack.h"))
 
 
 def build(asan=False):
-    out = os.path.join(HERE, "emu", "_build", "libtps_emu_wide_asan.so" if asan else "libtps_emu_wide.so")
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    if os.path.exists(out) and all(os.path.getmtime(out) >= os.path.getmtime(d) for d in DEPS):
-        return out
-    cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas", "-shared", "-fPIC"]
-    if asan:
-        cmd += ["-O1", "-fno-omit-frame-pointer", "-fsanitize=address,undefined"]
-    tmp = out + ".tmp%d" % os.getpid()
-    subprocess.check_call(cmd + ["-o", tmp, SRC])
-    os.replace(tmp, out)
-    return out
+    return emu_build.shared("libtps_emu_wide_asan.so" if asan else "libtps_emu_wide.so", "emu_wide.cpp", DEPS, asan)
 
 
 def build_main():
     """tests/emu/emu_wide_main.cpp under -fsanitize=address,undefined: a program of its own, nothing loaded into Python."""
-    out = os.path.join(HERE, "emu", "_build", "emu_wide_main_asan")
-    if os.path.exists(out) and all(os.path.getmtime(out) >= os.path.getmtime(d) for d in DEPS + [MAIN_SRC]):
-        return out
-    tmp = out + ".tmp%d" % os.getpid()
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wno-unused-function", "-Wno-unused-variable", "-Wno-unknown-pragmas",
-                           "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", tmp, MAIN_SRC])
-    os.replace(tmp, out)
-    return out
+    return emu_build.program("emu_wide_main_asan", "emu_wide_main.cpp", DEPS)
 
 
 _lib = None

@@ -113,3 +113,10 @@ def assert_equal(got_hits, got_counts, name, with_counts=True):
         assert len(bad) == 0, f"{name}: C_u differs at (read, end, period index) {bad[:5].tolist()}"
     else:
         assert got_counts is None
+
+
+# ---- the refusals: (what differs from a good call, the return code in the message)
+REFUSALS = [
+    (dict(u_min=0), "rc=-3"), (dict(u_min=5, u_max=4), "rc=-3"), (dict(u_max=33), "rc=-3"),
+    (dict(lo=-1), "rc=-5"), (dict(lo=10, hi=10), "rc=-5"), (dict(lo=0, hi=4097), "rc=-5"),
+]

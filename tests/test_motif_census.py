@@ -54,10 +54,7 @@ def test_cases_reach_what_they_are_for():
     assert h[withn, 0]["period"] == 32 and h[withn, 0]["run_start"] == 0 and motif.unit_string(h[withn, 0]["unit"], 32)[20] == "G"
 
 
-@pytest.mark.parametrize("kw, code", [
-    (dict(u_min=0), "rc=-3"), (dict(u_min=5, u_max=4), "rc=-3"), (dict(u_max=33), "rc=-3"),
-    (dict(lo=-1), "rc=-5"), (dict(lo=10, hi=10), "rc=-5"), (dict(lo=0, hi=4097), "rc=-5"),
-])
+@pytest.mark.parametrize("kw, code", mc.REFUSALS)
 def test_refusals_carry_the_librarys_codes(kw, code):
     """TPS_E_ARG (-3) for the periods, TPS_E_CAPACITY (-5) for the range, as tps_batch_motif_census returns them (test_gpu_motif.py
     asks the library the same)."""

@@ -102,14 +102,7 @@ def test_hit_table_equals_the_oracles_word_set(key):
         assert got == tract_oracle.word_set(u)
 
 
-@pytest.mark.parametrize("kw, code", [
-    (dict(code=variants.unit_code("CCT")[0], m=3), "rc=-3"), (dict(code=0, m=33), "rc=-3"), (dict(code=variants.unit_code("CCACCA")[0]), "rc=-3"),
-    (dict(code=variants.unit_code("CCCTAA")[0] | 1 << 12), "rc=-3"),
-    (dict(lens=(15, 2, 4)), "rc=-3"), (dict(lens=(16, 3, 4)), "rc=-3"), (dict(lens=(16, 2, 5)), "rc=-3"),
-    (dict(block=0), "rc=-5"), (dict(block=96), "rc=-5"), (dict(block=1088), "rc=-5"),
-    (dict(min_hits=0), "rc=-5"), (dict(min_hits=65), "rc=-5"), (dict(gap=-1), "rc=-5"), (dict(gap=65), "rc=-5"),
-    (dict(min_blocks=0), "rc=-5"), (dict(min_blocks=65), "rc=-5"), (dict(max_tracts=0, lens=(0, 2, 4)), "rc=-5"), (dict(max_tracts=17, lens=(34, 2, 4)), "rc=-5"),
-])
+@pytest.mark.parametrize("kw, code", tc.REFUSALS)
 def test_refusals_carry_the_librarys_codes(kw, code):
     """TPS_E_ARG (-3) and TPS_E_CAPACITY (-5) as tps_batch_tract_map returns them (test_gpu_tract.py asks the library the same)."""
     a = dict(code=variants.unit_code("CCCTAA")[0], m=6, block=64, min_hits=20, gap=1, min_blocks=2, max_tracts=8, lens=None)

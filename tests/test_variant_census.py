@@ -66,13 +66,7 @@ def test_isolated_variants_count_m_each(unit, place, letter, name, tail):
         assert np.array_equal(profile.sum(axis=0), counts[0].astype(np.int64))
 
 
-@pytest.mark.parametrize("kw, code", [
-    (dict(code=0b0110, m=1), "rc=-3"), (dict(code=0, m=33), "rc=-3"), (dict(code=variants.unit_code("CCACCA")[0]), "rc=-3"),
-    (dict(code=variants.unit_code("AA")[0], m=2), "rc=-3"), (dict(code=1 << 12), "rc=-3"),
-    (dict(begin=[-1]), "rc=-3"), (dict(end=[-1], begin=[-2]), "rc=-3"), (dict(begin=[5], end=[4]), "rc=-3"), (dict(tails=[2]), "rc=-3"),
-    (dict(tails=[0, 0], begin=[0, 0], end=[1, 1]), "rc=-3"),
-    (dict(bin=63), "rc=-5"), (dict(bin=4065), "rc=-5"), (dict(n_bins=0), "rc=-5"), (dict(n_bins=65), "rc=-5"),
-])
+@pytest.mark.parametrize("kw, code", vc.REFUSALS)
 def test_refusals_carry_the_librarys_codes(kw, code):
     """TPS_E_ARG (-3) and TPS_E_CAPACITY (-5) as tps_batch_variant_census returns them (test_gpu_variant.py asks the library the same)."""
     a = dict(code=variants.unit_code("CCCTAA")[0], m=6, tails=[0], begin=[0], end=[100], bin=500, n_bins=40)

@@ -10,6 +10,7 @@ import functools
 import numpy as np
 
 import tract_oracle
+from topsicle_amd import variants
 
 M32 = "ACGGTTCAGTCCATGACTTGCAAGTCTGATCC"           # 32 letters, no shorter period: fills the uint64
 UNITS = {
@@ -338,3 +339,14 @@ def check_cli_outputs(outdir, reads, unit, edge=256, file_name="reads", **kw):
     assert got_t[1:] == want_t
     assert got_r[1:] == want_r
     return classes
+
+
+# ---- the refusals: (what differs from a good call, the return code in the message)
+REFUSALS = [
+    (dict(code=variants.unit_code("CCT")[0], m=3), "rc=-3"), (dict(code=0, m=33), "rc=-3"), (dict(code=variants.unit_code("CCACCA")[0]), "rc=-3"),
+    (dict(code=variants.unit_code("CCCTAA")[0] | 1 << 12), "rc=-3"),
+    (dict(lens=(15, 2, 4)), "rc=-3"), (dict(lens=(16, 3, 4)), "rc=-3"), (dict(lens=(16, 2, 5)), "rc=-3"),
+    (dict(block=0), "rc=-5"), (dict(block=96), "rc=-5"), (dict(block=1088), "rc=-5"),
+    (dict(min_hits=0), "rc=-5"), (dict(min_hits=65), "rc=-5"), (dict(gap=-1), "rc=-5"), (dict(gap=65), "rc=-5"),
+    (dict(min_blocks=0), "rc=-5"), (dict(min_blocks=65), "rc=-5"), (dict(max_tracts=0, lens=(0, 2, 4)), "rc=-5"), (dict(max_tracts=17, lens=(34, 2, 4)), "rc=-5"),
+]

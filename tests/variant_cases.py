@@ -9,6 +9,7 @@ import functools
 import numpy as np
 
 import variant_oracle
+from topsicle_amd import variants
 
 M32 = "ACGGTTCAGTCCATGACTTGCAAGTCTGATCC"           # 32 letters, no shorter period: fills the uint64
 UNITS = {
@@ -242,3 +243,13 @@ def check_cli_outputs(outdir, reads, unit, ks, bin=500, n_bins=40, trimfirst=100
             s = variants.split_row(profile[b], unit)
             assert [int(x) for x in pr] == [b * bin] + list(s[:3]) + s[3], (k, b)
     return checked
+
+
+# ---- the refusals: (what differs from a good call, the return code in the message)
+REFUSALS = [
+    (dict(code=0b0110, m=1), "rc=-3"), (dict(code=0, m=33), "rc=-3"), (dict(code=variants.unit_code("CCACCA")[0]), "rc=-3"),
+    (dict(code=variants.unit_code("AA")[0], m=2), "rc=-3"), (dict(code=1 << 12), "rc=-3"),
+    (dict(begin=[-1]), "rc=-3"), (dict(end=[-1], begin=[-2]), "rc=-3"), (dict(begin=[5], end=[4]), "rc=-3"), (dict(tails=[2]), "rc=-3"),
+    (dict(tails=[0, 0], begin=[0, 0], end=[1, 1]), "rc=-3"),
+    (dict(bin=63), "rc=-5"), (dict(bin=4065), "rc=-5"), (dict(n_bins=0), "rc=-5"), (dict(n_bins=65), "rc=-5"),
+]

@@ -14,6 +14,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <deque>
+#include <initializer_list>
 #include <map>
 #include <mutex>
 #include <set>
@@ -28,6 +29,7 @@
 #include "tps_anchor.h"
 #include "tps_place.h"
 #include "tps_adapter.h"
+#include "tps_layout.h"
 #include "tps_pack.h"
 #include "tps_plan.h"
 #include "tps_wide.h"
@@ -1046,6 +1048,77 @@ Slot* get_slot(tps_ctx* c, int slot) {
     return &c->slots[slot];
 }
 
+// ---- the steps the read-analysis calls share (tps_batch_kmer_followers .. tps_batch_adapter_find; DESIGN.md, "How a read-analysis
+// call is put together").  Each call: need_batch (or bind alone, where it takes no batch), its check function from the feature's
+// header, its layouts (tps_layout.h), ensure + TPS_POISON, its clearing memsets and input copies, launch_waves, download.
+
+// bind and the slot; ... and a batch in it (the sibling of need_scanned below)
+int need_slot(tps_ctx* c, int slot, Slot** out) {
+    int rc;
+    if ((rc = bind(c))) return rc;
+    return (*out = get_slot(c, slot)) ? TPS_OK : TPS_E_ARG;
+}
+int have_batch(const Slot& sl) { return sl.n < 0 ? fail(TPS_E_STATE, "no batch uploaded in this slot") : TPS_OK; }
+int need_batch(tps_ctx* c, int slot, Slot** out) {
+    int rc;
+    if ((rc = need_slot(c, slot, out))) return rc;
+    return have_batch(**out);
+}
+
+// the slot's packed batch in a kernel's arguments
+template <class A>
+void set_batch(A& a, const Slot& sl) {
+    a.seq2 = (const uint32_t*)sl.seq2.p;
+    a.inv = (const uint16_t*)sl.inv.p;
+    a.desc = (const tps_read_desc*)sl.desc.p;
+}
+
+// piece `off` of a device buffer laid out with tps::Layout
+template <class T>
+T* at(const DevBuf& b, size_t off) { return (T*)((char*)b.p + off); }
+
+// tails / begin / end of n reads into `buf` where region_layout put them, and into the kernel's arguments
+template <class A>
+int upload_region(tps_ctx* c, const DevBuf& buf, const tps::RegionAt& r, const uint8_t* tails, const int32_t* begin, const int32_t* end, int64_t n, A& a) {
+    a.tails = at<const uint8_t>(buf, r.tails);
+    a.begin = at<const int32_t>(buf, r.begin);
+    a.end = at<const int32_t>(buf, r.end);
+    HIP_TRY(hipMemcpyAsync((void*)a.tails, tails, (size_t)n, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync((void*)a.begin, begin, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync((void*)a.end, end, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    return TPS_OK;
+}
+
+// The telomere hit table of (unit, m), built into `table` and copied to c->tract_table; *w = the letters of its words.  `table` is the
+// CALLER's local: the copy is from pageable memory and has left it when the call returns -- every call ends in download(), which
+// waits for the stream -- so it must live that long, not just as long as this function.
+int upload_hit_table(tps_ctx* c, uint64_t unit, int m, std::vector<uint32_t>& table, int* w) {
+    int rc;
+    *w = m < tps::TRACT_MAX_WORD ? m : tps::TRACT_MAX_WORD;
+    table.resize((size_t)tps::tract_table_dw(*w));
+    tps::tract_hit_table(unit, m, table.data());
+    if ((rc = c->tract_table.ensure(table.size() * 4))) return rc;
+    HIP_TRY(hipMemcpyAsync(c->tract_table.p, table.data(), table.size() * 4, hipMemcpyHostToDevice, c->stream));
+    return TPS_OK;
+}
+
+// one wave per read (or row), wpg waves per workgroup
+template <class A>
+int launch_waves(tps_ctx* c, void (*kernel)(A), int64_t n, int wpg, const A& a) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((n + wpg - 1) / wpg)), dim3(tps::NT * wpg), 0, c->stream, a);
+    HIP_TRY(hipGetLastError());
+    return TPS_OK;
+}
+
+// the outputs back to the host (a piece without a host pointer was not asked for), then the wait for the stream
+struct Down { void* host; const void* dev; size_t bytes; };
+int download(tps_ctx* c, std::initializer_list<Down> parts) {
+    for (const Down& d : parts)
+        if (d.host) HIP_TRY(hipMemcpyAsync(d.host, d.dev, d.bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return TPS_OK;
+}
+
 }  // namespace
 
 // ======================================================================== C ABI
@@ -1335,116 +1408,87 @@ int tps_batch_download_packed(tps_ctx* c, int32_t slot, uint32_t* seq2, uint16_t
 int tps_batch_kmer_followers(tps_ctx* c, int32_t slot, int32_t n_fwd, int32_t follow, int32_t lo, int32_t hi, int32_t min_len,
                              uint32_t* picks, int64_t picks_words, int64_t* hist, int64_t hist_len) {
     int rc;
-    if ((rc = bind(c))) return rc;
-    Slot* sl = get_slot(c, slot);
-    if (!sl) return TPS_E_ARG;
+    Slot* sl;
+    tps::Why why;
+    if ((rc = need_slot(c, slot, &sl))) return rc;
     if (!c->have_pat) return fail(TPS_E_PATTERN, "tps_set_patterns has not been called");
     if (c->wide_cur) return fail(TPS_E_PATTERN, "tps_batch_kmer_followers does not take a wide pattern table (n_fwd <= 15: set the table with tps_set_patterns)");
-    if (sl->n < 0) return fail(TPS_E_STATE, "no batch uploaded in this slot");
-    if (n_fwd < 1 || n_fwd > 15 || 2 * n_fwd > c->pat.P) return fail(TPS_E_ARG, "n_fwd must be 1..15 and the table must hold the complements behind the k-mers");
-    if (follow < 0 || follow > 8) return fail(TPS_E_CAPACITY, "follow must be 0..8 bases");
-    if (lo < 0 || hi <= lo || hi - lo > tps::FOLLOW_MAX_SPAN) return fail(TPS_E_CAPACITY, "the scanned range [lo, hi) must hold 1..%d bases", tps::FOLLOW_MAX_SPAN);
-    const int pw = (hi - lo + 31) / 32;
+    if ((rc = have_batch(*sl))) return rc;
     const int64_t n = sl->n;
-    const int64_t want = n * 2 * n_fwd * pw;
-    if (!picks || picks_words != want) return fail(TPS_E_ARG, "picks must hold %lld words", (long long)want);
-    const int nbins = (1 << (2 * follow)) + 1;
-    if (hist && hist_len != 2ll * n_fwd * nbins) return fail(TPS_E_ARG, "hist must hold %lld counters", 2ll * n_fwd * nbins);
+    if ((rc = tps::followers_check(c->pat.P, n, n_fwd, follow, lo, hi, picks, picks_words, hist, hist_len, &why))) return fail(rc, "%s", why.msg);
     if (n == 0) { if (hist) memset(hist, 0, (size_t)hist_len * 8); return TPS_OK; }
+    const int pw = (hi - lo + 31) / 32, nbins = (1 << (2 * follow)) + 1;
+    const size_t picks_bytes = (size_t)picks_words * 4, hist_bytes = (size_t)2 * n_fwd * nbins * 8;
     // scratch: the slot's raw / sums buffers are not touched; picks and counters get buffers of their own in the context
-    if ((rc = c->follow_picks.ensure((size_t)want * 4))) return rc;
-    if ((rc = c->follow_hist.ensure((size_t)2 * n_fwd * nbins * 8))) return rc;
+    if ((rc = c->follow_picks.ensure(picks_bytes))) return rc;
+    if ((rc = c->follow_hist.ensure(hist_bytes))) return rc;
     TPS_POISON(c->follow_picks);
     TPS_POISON(c->follow_hist);
-    HIP_TRY(hipMemsetAsync(c->follow_picks.p, 0, (size_t)want * 4, c->stream));
-    HIP_TRY(hipMemsetAsync(c->follow_hist.p, 0, (size_t)2 * n_fwd * nbins * 8, c->stream));
+    HIP_TRY(hipMemsetAsync(c->follow_picks.p, 0, picks_bytes, c->stream));
+    HIP_TRY(hipMemsetAsync(c->follow_hist.p, 0, hist_bytes, c->stream));
     tps::FollowArgs a{};
-    a.seq2 = (const uint32_t*)sl->seq2.p;
-    a.inv = (const uint16_t*)sl->inv.p;
-    a.desc = (const tps_read_desc*)sl->desc.p;
+    set_batch(a, *sl);
     a.lut = (const uint32_t*)c->lut_cur->dev.p;
     a.picks = (uint32_t*)c->follow_picks.p;
     a.hist = hist ? (unsigned long long*)c->follow_hist.p : nullptr;
     a.n_reads = n;
     a.pat = c->pat;
     a.n_fwd = n_fwd; a.follow = follow; a.lo = lo; a.hi = hi; a.min_len = min_len; a.pw = pw; a.nbins = nbins;
-    hipLaunchKernelGGL(tps_followers_kernel, dim3((unsigned)((n + tps::WPG - 1) / tps::WPG)), dim3(tps::NT * tps::WPG), 0, c->stream, a);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(picks, c->follow_picks.p, (size_t)want * 4, hipMemcpyDeviceToHost, c->stream));
-    if (hist) HIP_TRY(hipMemcpyAsync(hist, c->follow_hist.p, (size_t)hist_len * 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return TPS_OK;
+    if ((rc = launch_waves(c, tps_followers_kernel, n, tps::WPG, a))) return rc;
+    return download(c, {{picks, a.picks, picks_bytes}, {hist, c->follow_hist.p, hist_bytes}});
 }
 
 int tps_batch_kmer_followers_wide(tps_ctx* c, int32_t slot, int32_t n_fwd, int32_t follow, int32_t lo, int32_t hi, int32_t min_len,
                                   uint32_t* picks, int64_t picks_words, int64_t* hist, int64_t hist_len) {
     int rc;
-    if ((rc = bind(c))) return rc;
-    Slot* sl = get_slot(c, slot);
-    if (!sl) return TPS_E_ARG;
+    Slot* sl;
+    tps::Why why;
+    if ((rc = need_slot(c, slot, &sl))) return rc;
     if (!c->have_pat || !c->wide_cur) return fail(TPS_E_PATTERN, "tps_batch_kmer_followers_wide needs a table set with tps_set_patterns_wide");
-    if (sl->n < 0) return fail(TPS_E_STATE, "no batch uploaded in this slot");
-    const tps_ctx::WideTable& wt = *c->wide_cur;
-    if (n_fwd < 1 || n_fwd > tps::FOLLOWW_MAX_FWD || 2 * n_fwd > wt.P)
-        return fail(TPS_E_ARG, "n_fwd must be 1..%d and the table must hold the complements behind the k-mers", tps::FOLLOWW_MAX_FWD);
-    if (follow < 0) return fail(TPS_E_ARG, "follow must not be negative");
-    if (lo < 0 || hi <= lo || hi - lo > tps::FOLLOW_MAX_SPAN) return fail(TPS_E_CAPACITY, "the scanned range [lo, hi) must hold 1..%d bases", tps::FOLLOW_MAX_SPAN);
-    if (hist && follow > 8) return fail(TPS_E_CAPACITY, "the followers histogram has 4^follow bins: follow must be 0..8 bases with it (pass no hist for more)");
+    if ((rc = have_batch(*sl))) return rc;
     // (static LDS of at most 64 KB: the 160 KB cap of lds_budget_dw never decides here.  The assertion restates the sum of
     // followers_wide_wg_lds_dwords(), which is not constexpr; should the two drift apart, the kernel's own static array, sized by
     // the same constants, still refuses to compile beyond 64 KB)
     static_assert((tps::WIDE_IMG_DW + tps::WPG * tps::FOLLOWW_LDS_DW) * 4 <= 64 * 1024, "tps_followers_kernel_wide: followers_wide_wg_lds_dwords() within every device's budget cap");
     if (tps::followers_wide_wg_lds_dwords() > lds_budget_dw(c))
         return fail(TPS_E_CAPACITY, "the wide followers kernel needs %lld bytes of LDS per workgroup", (long long)tps::followers_wide_wg_lds_dwords() * 4);
-    const int pw = (hi - lo + 31) / 32;
+    const tps_ctx::WideTable& wt = *c->wide_cur;
     const int64_t n = sl->n;
-    const int64_t want = n * 2 * n_fwd * pw;
-    if (!picks || picks_words != want) return fail(TPS_E_ARG, "picks must hold %lld words", (long long)want);
-    const int nbins = hist ? (1 << (2 * follow)) + 1 : 0;
-    if (hist && hist_len != 2ll * n_fwd * nbins) return fail(TPS_E_ARG, "hist must hold %lld counters", 2ll * n_fwd * nbins);
+    if ((rc = tps::followers_wide_check(wt.P, n, n_fwd, follow, lo, hi, picks, picks_words, hist, hist_len, &why))) return fail(rc, "%s", why.msg);
     if (n == 0) { if (hist) memset(hist, 0, (size_t)hist_len * 8); return TPS_OK; }
-    if ((rc = c->follow_picks.ensure((size_t)want * 4))) return rc;
+    const int pw = (hi - lo + 31) / 32, nbins = hist ? (1 << (2 * follow)) + 1 : 0;
+    const size_t picks_bytes = (size_t)picks_words * 4, hist_bytes = (size_t)hist_len * 8;
+    if ((rc = c->follow_picks.ensure(picks_bytes))) return rc;
     TPS_POISON(c->follow_picks);
-    HIP_TRY(hipMemsetAsync(c->follow_picks.p, 0, (size_t)want * 4, c->stream));
+    HIP_TRY(hipMemsetAsync(c->follow_picks.p, 0, picks_bytes, c->stream));
     if (hist) {
-        if ((rc = c->follow_hist.ensure((size_t)hist_len * 8))) return rc;
+        if ((rc = c->follow_hist.ensure(hist_bytes))) return rc;
         TPS_POISON(c->follow_hist);
-        HIP_TRY(hipMemsetAsync(c->follow_hist.p, 0, (size_t)hist_len * 8, c->stream));
+        HIP_TRY(hipMemsetAsync(c->follow_hist.p, 0, hist_bytes, c->stream));
     }
     tps::FollowWideArgs a{};
-    a.seq2 = (const uint32_t*)sl->seq2.p;
-    a.inv = (const uint16_t*)sl->inv.p;
-    a.desc = (const tps_read_desc*)sl->desc.p;
+    set_batch(a, *sl);
     a.img = (const uint32_t*)wt.dev.p;
     a.picks = (uint32_t*)c->follow_picks.p;
     a.hist = hist ? (unsigned long long*)c->follow_hist.p : nullptr;
     a.n_reads = n;
     a.pat = wt.pat;
     a.n_fwd = n_fwd; a.follow = follow; a.lo = lo; a.hi = hi; a.min_len = min_len; a.pw = pw; a.nbins = nbins;
-    hipLaunchKernelGGL(tps_followers_kernel_wide, dim3((unsigned)((n + tps::WPG - 1) / tps::WPG)), dim3(tps::NT * tps::WPG), 0, c->stream, a);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(picks, c->follow_picks.p, (size_t)want * 4, hipMemcpyDeviceToHost, c->stream));
-    if (hist) HIP_TRY(hipMemcpyAsync(hist, c->follow_hist.p, (size_t)hist_len * 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return TPS_OK;
+    if ((rc = launch_waves(c, tps_followers_kernel_wide, n, tps::WPG, a))) return rc;
+    return download(c, {{picks, a.picks, picks_bytes}, {hist, c->follow_hist.p, hist_bytes}});
 }
 
 int tps_batch_motif_census(tps_ctx* c, int32_t slot, int32_t u_min, int32_t u_max, int32_t lo, int32_t hi, int32_t min_len,
                            tps_motif_hit* hits, int64_t n_hits, int32_t* counts, int64_t counts_len) {
     int rc;
-    if ((rc = bind(c))) return rc;
-    Slot* sl = get_slot(c, slot);
-    if (!sl) return TPS_E_ARG;
-    if (sl->n < 0) return fail(TPS_E_STATE, "no batch uploaded in this slot");
-    if (u_min < 1 || u_max < u_min || u_max > tps::MOTIF_MAX_PERIOD) return fail(TPS_E_ARG, "the periods must be 1 <= u_min <= u_max <= %d", tps::MOTIF_MAX_PERIOD);
-    if (lo < 0 || hi <= lo || hi - lo > tps::FOLLOW_MAX_SPAN) return fail(TPS_E_CAPACITY, "the scanned range [lo, hi) must hold 1..%d bases", tps::FOLLOW_MAX_SPAN);
+    Slot* sl;
+    tps::Why why;
+    if ((rc = need_batch(c, slot, &sl))) return rc;
     const int64_t n = sl->n;
-    const int nu = u_max - u_min + 1;
-    if ((!hits && n > 0) || n_hits != 2 * n) return fail(TPS_E_ARG, "hits must hold %lld entries", (long long)(2 * n));
-    if (counts && counts_len != 2 * n * nu) return fail(TPS_E_ARG, "counts must hold %lld counters", (long long)(2 * n * nu));
+    if ((rc = tps::motif_census_check(n, u_min, u_max, lo, hi, hits, n_hits, counts, counts_len, &why))) return fail(rc, "%s", why.msg);
     if (n == 0) return TPS_OK;
     // (the table, the slot's scan outputs and its plan are not touched: a scan before and after the census gives the same results)
-    const size_t hit_bytes = (size_t)n * 2 * sizeof(tps_motif_hit), cnt_bytes = (size_t)n * 2 * nu * 4;
+    const size_t hit_bytes = (size_t)n * 2 * sizeof(tps_motif_hit), cnt_bytes = (size_t)n * 2 * (u_max - u_min + 1) * 4;
     if ((rc = c->motif_hits.ensure(hit_bytes))) return rc;
     TPS_POISON(c->motif_hits);
     HIP_TRY(hipMemsetAsync(c->motif_hits.p, 0, hit_bytes, c->stream));
@@ -1454,83 +1498,50 @@ int tps_batch_motif_census(tps_ctx* c, int32_t slot, int32_t u_min, int32_t u_ma
         HIP_TRY(hipMemsetAsync(c->motif_counts.p, 0, cnt_bytes, c->stream));
     }
     tps::MotifArgs a{};
-    a.seq2 = (const uint32_t*)sl->seq2.p;
-    a.inv = (const uint16_t*)sl->inv.p;
-    a.desc = (const tps_read_desc*)sl->desc.p;
+    set_batch(a, *sl);
     a.hits = (tps_motif_hit*)c->motif_hits.p;
     a.counts = counts ? (int32_t*)c->motif_counts.p : nullptr;
     a.n_reads = n;
     a.u_min = u_min; a.u_max = u_max; a.lo = lo; a.hi = hi; a.min_len = min_len;
-    hipLaunchKernelGGL(tps::motif_census_kernel, dim3((unsigned)((n + tps::WPG - 1) / tps::WPG)), dim3(tps::NT * tps::WPG), 0, c->stream, a);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(hits, c->motif_hits.p, hit_bytes, hipMemcpyDeviceToHost, c->stream));
-    if (counts) HIP_TRY(hipMemcpyAsync(counts, c->motif_counts.p, cnt_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return TPS_OK;
+    if ((rc = launch_waves(c, tps::motif_census_kernel, n, tps::WPG, a))) return rc;
+    return download(c, {{hits, a.hits, hit_bytes}, {counts, c->motif_counts.p, cnt_bytes}});
 }
 
 int tps_batch_variant_census(tps_ctx* c, int32_t slot, uint64_t unit, int32_t m, const uint8_t* tails, const int32_t* begin, const int32_t* end,
                              int64_t n_reads, int32_t bin, int32_t n_bins, uint32_t* counts, int64_t counts_len, int64_t* profile, int64_t profile_len) {
     int rc;
-    if ((rc = bind(c))) return rc;
-    Slot* sl = get_slot(c, slot);
-    if (!sl) return TPS_E_ARG;
-    if (sl->n < 0) return fail(TPS_E_STATE, "no batch uploaded in this slot");
-    if (m < 2 || m > tps::VARIANT_MAX_UNIT) return fail(TPS_E_ARG, "the unit must have 2..%d letters", tps::VARIANT_MAX_UNIT);
-    if (m < 32 && (unit >> (2 * m)) != 0) return fail(TPS_E_ARG, "the unit has codes behind its %d letters", m);
-    for (int d = 1; d < m; ++d) {
-        if (m % d) continue;
-        const uint64_t rot = (unit >> (2 * d)) | (unit << (2 * (m - d)));       // the unit rotated left by d letters
-        if (((rot ^ unit) & (~0ull >> (64 - 2 * m))) == 0) return fail(TPS_E_ARG, "the unit is a power of its first %d letters: pass the primitive root", d);
-    }
-    if (bin < tps::VARIANT_MIN_BIN || bin > tps::VARIANT_MAX_BIN) return fail(TPS_E_CAPACITY, "bin must be %d..%d positions", tps::VARIANT_MIN_BIN, tps::VARIANT_MAX_BIN);
-    if (n_bins < 1 || n_bins > tps::VARIANT_MAX_BINS) return fail(TPS_E_CAPACITY, "n_bins must be 1..%d", tps::VARIANT_MAX_BINS);
+    Slot* sl;
+    tps::Why why;
+    if ((rc = need_batch(c, slot, &sl))) return rc;
     const int64_t n = sl->n;
-    const int cols = 2 + 4 * m;
-    if (n_reads != n) return fail(TPS_E_ARG, "tails, begin and end must hold %lld reads", (long long)n);
-    if (n > 0 && (!tails || !begin || !end)) return fail(TPS_E_ARG, "null tails / begin / end");
-    if ((!counts && n > 0) || counts_len != n * cols) return fail(TPS_E_ARG, "counts must hold %lld counters", (long long)(n * cols));
-    if (profile && profile_len != (int64_t)n_bins * cols) return fail(TPS_E_ARG, "profile must hold %lld counters", (long long)n_bins * cols);
-    for (int64_t i = 0; i < n; ++i) {
-        if (tails[i] > 1) return fail(TPS_E_ARG, "read %lld: tail must be 0 or 1", (long long)i);
-        if (begin[i] < 0 || end[i] < 0 || begin[i] > end[i]) return fail(TPS_E_ARG, "read %lld: need 0 <= begin <= end", (long long)i);
-    }
+    if ((rc = tps::variant_census_check(n, unit, m, tails, begin, end, n_reads, bin, n_bins, counts, counts_len, profile, profile_len, &why)))
+        return fail(rc, "%s", why.msg);
     if (profile) memset(profile, 0, (size_t)profile_len * 8);
     if (n == 0) return TPS_OK;
     // (the table, the slot's tails, its scan outputs and its plan are not touched: a scan before and after the census gives the same results)
+    const int cols = 2 + 4 * m;
     const size_t cnt_bytes = (size_t)n * cols * 4, part_len = (size_t)n_bins * cols, prof_bytes = tps::VARIANT_PARTS * part_len * 8;
-    const size_t off_begin = (((size_t)n + 15) & ~(size_t)15), off_end = off_begin + (size_t)n * 4;
-    if ((rc = c->variant_in.ensure(off_end + (size_t)n * 4))) return rc;
+    tps::Layout in;
+    const tps::RegionAt reg = tps::region_layout(in, n);
+    if ((rc = c->variant_in.ensure(in.total))) return rc;
     if ((rc = c->variant_counts.ensure(cnt_bytes))) return rc;
     TPS_POISON(c->variant_counts);
-    HIP_TRY(hipMemcpyAsync(c->variant_in.p, tails, (size_t)n, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync((char*)c->variant_in.p + off_begin, begin, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync((char*)c->variant_in.p + off_end, end, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    tps::VariantArgs a{};
+    set_batch(a, *sl);
+    if ((rc = upload_region(c, c->variant_in, reg, tails, begin, end, n, a))) return rc;
     HIP_TRY(hipMemsetAsync(c->variant_counts.p, 0, cnt_bytes, c->stream));
     if (profile) {
         if ((rc = c->variant_prof.ensure(prof_bytes))) return rc;
         TPS_POISON(c->variant_prof);
         HIP_TRY(hipMemsetAsync(c->variant_prof.p, 0, prof_bytes, c->stream));
+        c->h_variant_prof.resize(tps::VARIANT_PARTS * part_len);
     }
-    tps::VariantArgs a{};
-    a.seq2 = (const uint32_t*)sl->seq2.p;
-    a.inv = (const uint16_t*)sl->inv.p;
-    a.desc = (const tps_read_desc*)sl->desc.p;
-    a.tails = (const uint8_t*)c->variant_in.p;
-    a.begin = (const int32_t*)((const char*)c->variant_in.p + off_begin);
-    a.end = (const int32_t*)((const char*)c->variant_in.p + off_end);
     a.counts = (uint32_t*)c->variant_counts.p;
     a.prof = profile ? (unsigned long long*)c->variant_prof.p : nullptr;
     a.n_reads = n;
     a.unit = unit; a.m = m; a.bin = bin; a.n_bins = n_bins;
-    hipLaunchKernelGGL(tps::variant_census_kernel, dim3((unsigned)((n + tps::WPG - 1) / tps::WPG)), dim3(tps::NT * tps::WPG), 0, c->stream, a);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(counts, c->variant_counts.p, cnt_bytes, hipMemcpyDeviceToHost, c->stream));
-    if (profile) {
-        c->h_variant_prof.resize(tps::VARIANT_PARTS * part_len);
-        HIP_TRY(hipMemcpyAsync(c->h_variant_prof.data(), c->variant_prof.p, prof_bytes, hipMemcpyDeviceToHost, c->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    if ((rc = launch_waves(c, tps::variant_census_kernel, n, tps::WPG, a))) return rc;
+    if ((rc = download(c, {{counts, a.counts, cnt_bytes}, {profile ? c->h_variant_prof.data() : nullptr, c->variant_prof.p, prof_bytes}}))) return rc;
     if (profile)
         for (int p = 0; p < tps::VARIANT_PARTS; ++p)
             for (size_t i = 0; i < part_len; ++i) profile[i] += (int64_t)c->h_variant_prof[p * part_len + i];
@@ -1539,223 +1550,159 @@ int tps_batch_variant_census(tps_ctx* c, int32_t slot, uint64_t unit, int32_t m,
 
 int tps_batch_tract_map(tps_ctx* c, int32_t slot, uint64_t unit, int32_t m, int32_t block, int32_t min_hits, int32_t gap, int32_t min_blocks,
                         int32_t max_tracts, tps_tract* tracts, int64_t tracts_len, int32_t* found, int64_t found_len, uint32_t* totals, int64_t totals_len) {
-    int rc;
-    if ((rc = bind(c))) return rc;
-    Slot* sl = get_slot(c, slot);
-    if (!sl) return TPS_E_ARG;
-    if (sl->n < 0) return fail(TPS_E_STATE, "no batch uploaded in this slot");
-    const char* why = "";
-    if ((rc = tps::tract_check(unit, m, block, min_hits, gap, min_blocks, max_tracts, &why))) return fail(rc, "%s", why);
+    int rc, w;
+    Slot* sl;
+    tps::Why why;
+    if ((rc = need_batch(c, slot, &sl))) return rc;
     const int64_t n = sl->n;
-    if (tracts_len != n * 2 * max_tracts) return fail(TPS_E_ARG, "tracts must hold %lld records", (long long)(n * 2 * max_tracts));
-    if (found_len != n * 2) return fail(TPS_E_ARG, "found must hold %lld counters", (long long)(n * 2));
-    if (totals_len != n * 4) return fail(TPS_E_ARG, "totals must hold %lld counters", (long long)(n * 4));
+    if ((rc = tps::tract_map_check(n, unit, m, block, min_hits, gap, min_blocks, max_tracts, tracts, tracts_len, found, found_len, totals, totals_len, &why)))
+        return fail(rc, "%s", why.msg);
     if (n == 0) return TPS_OK;
-    if (!tracts || !found || !totals) return fail(TPS_E_ARG, "null tracts / found / totals");
     // (the pattern table, the slot's tails, its scan outputs and its plan are not touched: a scan before and after the map gives the same results)
-    const int w = m < tps::TRACT_MAX_WORD ? m : tps::TRACT_MAX_WORD;
-    std::vector<uint32_t> table((size_t)tps::tract_table_dw(w));
-    tps::tract_hit_table(unit, m, table.data());
-    const size_t tab_bytes = table.size() * 4, tr_bytes = (size_t)n * 2 * max_tracts * sizeof(tps_tract), fo_bytes = (size_t)n * 2 * 4, to_bytes = (size_t)n * 4 * 4;
-    if ((rc = c->tract_table.ensure(tab_bytes))) return rc;
-    if ((rc = c->tract_out.ensure(tr_bytes + fo_bytes + to_bytes))) return rc;
+    tps::Layout out;
+    const size_t tr_bytes = (size_t)n * 2 * max_tracts * sizeof(tps_tract), fo_bytes = (size_t)n * 2 * 4, to_bytes = (size_t)n * 4 * 4;
+    const size_t off_tr = out.add(tr_bytes), off_fo = out.add(fo_bytes), off_to = out.add(to_bytes);
+    if ((rc = c->tract_out.ensure(out.total))) return rc;
     TPS_POISON(c->tract_out);
-    HIP_TRY(hipMemcpyAsync(c->tract_table.p, table.data(), tab_bytes, hipMemcpyHostToDevice, c->stream));      // (pageable: the copy has left `table` when the call returns)
-    HIP_TRY(hipMemsetAsync(c->tract_out.p, 0, tr_bytes + fo_bytes + to_bytes, c->stream));
+    std::vector<uint32_t> table;
+    if ((rc = upload_hit_table(c, unit, m, table, &w))) return rc;
+    HIP_TRY(hipMemsetAsync(c->tract_out.p, 0, out.total, c->stream));
     tps::TractArgs a{};
-    a.seq2 = (const uint32_t*)sl->seq2.p;
-    a.inv = (const uint16_t*)sl->inv.p;
-    a.desc = (const tps_read_desc*)sl->desc.p;
+    set_batch(a, *sl);
     a.table = (const uint32_t*)c->tract_table.p;
-    a.tracts = (tps_tract*)c->tract_out.p;
-    a.found = (int32_t*)((char*)c->tract_out.p + tr_bytes);
-    a.totals = (uint32_t*)((char*)c->tract_out.p + tr_bytes + fo_bytes);
+    a.tracts = at<tps_tract>(c->tract_out, off_tr);
+    a.found = at<int32_t>(c->tract_out, off_fo);
+    a.totals = at<uint32_t>(c->tract_out, off_to);
     a.n_reads = n;
     a.w = w; a.block = block; a.min_hits = min_hits; a.gap = gap; a.min_blocks = min_blocks; a.max_tracts = max_tracts;
-    hipLaunchKernelGGL(tps::tract_map_kernel, dim3((unsigned)((n + tps::TRACT_WPG - 1) / tps::TRACT_WPG)), dim3(tps::NT * tps::TRACT_WPG), 0, c->stream, a);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(tracts, a.tracts, tr_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(found, a.found, fo_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(totals, a.totals, to_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return TPS_OK;
+    if ((rc = launch_waves(c, tps::tract_map_kernel, n, tps::TRACT_WPG, a))) return rc;
+    return download(c, {{tracts, a.tracts, tr_bytes}, {found, a.found, fo_bytes}, {totals, a.totals, to_bytes}});
 }
 
 int tps_batch_end_sketch(tps_ctx* c, int32_t slot, uint64_t unit, int32_t m, int32_t k, int32_t buckets, const uint8_t* tails, const int32_t* begin,
                          const int32_t* end, int64_t n_reads, uint32_t* sketch, int64_t sketch_len, uint32_t* kept, int64_t kept_len) {
-    int rc;
-    if ((rc = bind(c))) return rc;
-    Slot* sl = get_slot(c, slot);
-    if (!sl) return TPS_E_ARG;
-    if (sl->n < 0) return fail(TPS_E_STATE, "no batch uploaded in this slot");
-    const char* why = "";
-    if ((rc = tps::ends_check(unit, m, k, buckets, &why))) return fail(rc, "%s", why);
+    int rc, w;
+    Slot* sl;
+    tps::Why why;
+    if ((rc = need_batch(c, slot, &sl))) return rc;
     const int64_t n = sl->n;
-    if (n_reads != n) return fail(TPS_E_ARG, "tails, begin and end must hold %lld reads", (long long)n);
-    if (sketch_len != n * buckets) return fail(TPS_E_ARG, "sketch must hold %lld hashes", (long long)(n * buckets));
-    if (kept_len != n) return fail(TPS_E_ARG, "kept must hold %lld counters", (long long)n);
+    if ((rc = tps::end_sketch_check(n, unit, m, k, buckets, tails, begin, end, n_reads, sketch, sketch_len, kept, kept_len, &why))) return fail(rc, "%s", why.msg);
     if (n == 0) return TPS_OK;
-    if (!tails || !begin || !end || !sketch || !kept) return fail(TPS_E_ARG, "null tails / begin / end / sketch / kept");
-    int64_t at = 0;
-    if ((rc = tps::ends_check_reads(tails, begin, end, n, &why, &at))) return fail(rc, "read %lld: %s", (long long)at, why);
     // (the pattern table, the slot's tails, its scan outputs and its plan are not touched: a scan before and after the sketch gives the same results)
-    const int w = m < tps::TRACT_MAX_WORD ? m : tps::TRACT_MAX_WORD;
-    std::vector<uint32_t> table((size_t)tps::tract_table_dw(w));
-    tps::tract_hit_table(unit, m, table.data());
-    const size_t tab_bytes = table.size() * 4, sk_bytes = (size_t)n * buckets * 4, kp_bytes = (size_t)n * 4;
-    const size_t off_begin = (((size_t)n + 15) & ~(size_t)15), off_end = off_begin + (size_t)n * 4;
-    if ((rc = c->tract_table.ensure(tab_bytes))) return rc;
-    if ((rc = c->ends_in.ensure(off_end + (size_t)n * 4))) return rc;
-    if ((rc = c->ends_out.ensure(sk_bytes + kp_bytes))) return rc;
+    tps::Layout in, out;
+    const tps::RegionAt reg = tps::region_layout(in, n);
+    const size_t sk_bytes = (size_t)n * buckets * 4, kp_bytes = (size_t)n * 4;
+    const size_t off_sk = out.add(sk_bytes), off_kp = out.add(kp_bytes);
+    if ((rc = c->ends_in.ensure(in.total))) return rc;
+    if ((rc = c->ends_out.ensure(out.total))) return rc;
     TPS_POISON(c->ends_out);
-    HIP_TRY(hipMemcpyAsync(c->tract_table.p, table.data(), tab_bytes, hipMemcpyHostToDevice, c->stream));      // (pageable: the copy has left `table` when the call returns)
-    HIP_TRY(hipMemcpyAsync(c->ends_in.p, tails, (size_t)n, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync((char*)c->ends_in.p + off_begin, begin, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync((char*)c->ends_in.p + off_end, end, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    std::vector<uint32_t> table;
+    if ((rc = upload_hit_table(c, unit, m, table, &w))) return rc;
     tps::EndSketchArgs a{};
-    a.seq2 = (const uint32_t*)sl->seq2.p;
-    a.inv = (const uint16_t*)sl->inv.p;
-    a.desc = (const tps_read_desc*)sl->desc.p;
+    set_batch(a, *sl);
+    if ((rc = upload_region(c, c->ends_in, reg, tails, begin, end, n, a))) return rc;
     a.table = (const uint32_t*)c->tract_table.p;
-    a.tails = (const uint8_t*)c->ends_in.p;
-    a.begin = (const int32_t*)((const char*)c->ends_in.p + off_begin);
-    a.end = (const int32_t*)((const char*)c->ends_in.p + off_end);
-    a.sketch = (uint32_t*)c->ends_out.p;
-    a.kept = (uint32_t*)((char*)c->ends_out.p + sk_bytes);
+    a.sketch = at<uint32_t>(c->ends_out, off_sk);
+    a.kept = at<uint32_t>(c->ends_out, off_kp);
     a.n_reads = n;
     a.w = w; a.k = k; a.buckets = buckets; a.shift = 32 - tps::ends_log2(buckets);
-    hipLaunchKernelGGL(tps::end_sketch_kernel, dim3((unsigned)((n + tps::ENDS_WPG - 1) / tps::ENDS_WPG)), dim3(tps::NT * tps::ENDS_WPG), 0, c->stream, a);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(sketch, a.sketch, sk_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(kept, a.kept, kp_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return TPS_OK;
+    if ((rc = launch_waves(c, tps::end_sketch_kernel, n, tps::ENDS_WPG, a))) return rc;
+    return download(c, {{sketch, a.sketch, sk_bytes}, {kept, a.kept, kp_bytes}});
 }
 
 int tps_sketch_links(tps_ctx* c, const uint32_t* sketch, int64_t n, int32_t buckets, int64_t sketch_len, int32_t min_match, int32_t max_links,
                      int32_t* degree, int64_t degree_len, int32_t* links, int64_t links_len, int32_t* matches, int64_t matches_len) {
     int rc;
+    tps::Why why;
     if ((rc = bind(c))) return rc;
-    const char* why = "";
-    if ((rc = tps::links_check(n, buckets, sketch_len, min_match, max_links, degree_len, links_len, matches_len, &why))) return fail(rc, "%s", why);
+    if ((rc = tps::sketch_links_check(sketch, n, buckets, sketch_len, min_match, max_links, degree, degree_len, links, links_len, matches, matches_len, &why)))
+        return fail(rc, "%s", why.msg);
     if (n == 0) return TPS_OK;
-    if (!sketch || !degree || !links || !matches) return fail(TPS_E_ARG, "null sketch / degree / links / matches");
     std::vector<uint32_t> t((size_t)n * buckets);
     tps::links_transpose(sketch, n, buckets, t.data());
+    tps::Layout out;
     const size_t t_bytes = t.size() * 4, dg_bytes = (size_t)n * 4, ln_bytes = (size_t)n * max_links * 4;
+    const size_t off_dg = out.add(dg_bytes), off_ln = out.add(ln_bytes), off_ma = out.add(ln_bytes);
     if ((rc = c->links_t.ensure(t_bytes))) return rc;
-    if ((rc = c->links_out.ensure(dg_bytes + 2 * ln_bytes))) return rc;
+    if ((rc = c->links_out.ensure(out.total))) return rc;
     TPS_POISON(c->links_out);
     HIP_TRY(hipMemcpyAsync(c->links_t.p, t.data(), t_bytes, hipMemcpyHostToDevice, c->stream));      // (pageable: the copy has left `t` when the call returns)
     tps::LinkArgs a{};
     a.t = (const uint32_t*)c->links_t.p;
-    a.degree = (int32_t*)c->links_out.p;
-    a.links = (int32_t*)((char*)c->links_out.p + dg_bytes);
-    a.matches = (int32_t*)((char*)c->links_out.p + dg_bytes + ln_bytes);
+    a.degree = at<int32_t>(c->links_out, off_dg);
+    a.links = at<int32_t>(c->links_out, off_ln);
+    a.matches = at<int32_t>(c->links_out, off_ma);
     a.n = n;
     a.buckets = buckets; a.min_match = min_match; a.max_links = max_links;
     HIP_TRY(hipMemsetAsync(a.links, 0xFF, ln_bytes, c->stream));               // -1: no link
     HIP_TRY(hipMemsetAsync(a.matches, 0, ln_bytes, c->stream));
-    hipLaunchKernelGGL(tps::sketch_links_kernel, dim3((unsigned)((n + tps::LINKS_WPG - 1) / tps::LINKS_WPG)), dim3(tps::NT * tps::LINKS_WPG), 0, c->stream, a);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(degree, a.degree, dg_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(links, a.links, ln_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(matches, a.matches, ln_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return TPS_OK;
+    if ((rc = launch_waves(c, tps::sketch_links_kernel, n, tps::LINKS_WPG, a))) return rc;
+    return download(c, {{degree, a.degree, dg_bytes}, {links, a.links, ln_bytes}, {matches, a.matches, ln_bytes}});
 }
 
 int tps_batch_end_window(tps_ctx* c, int32_t slot, uint64_t unit, int32_t m, int32_t k, const uint8_t* tails, const int32_t* begin, const int32_t* end,
                          int64_t n_reads, int32_t span, uint32_t* codes, int64_t codes_len, uint32_t* keep, int64_t keep_len) {
-    int rc;
-    if ((rc = bind(c))) return rc;
-    Slot* sl = get_slot(c, slot);
-    if (!sl) return TPS_E_ARG;
-    if (sl->n < 0) return fail(TPS_E_STATE, "no batch uploaded in this slot");
-    const char* why = "";
-    if ((rc = tps::ends_check(unit, m, k, tps::ENDS_MIN_BUCKETS, &why))) return fail(rc, "%s", why);
-    if ((rc = tps::window_check_span(span, k, &why))) return fail(rc, "%s", why);
+    int rc, w;
+    Slot* sl;
+    tps::Why why;
+    if ((rc = need_batch(c, slot, &sl))) return rc;
     const int64_t n = sl->n;
-    const int cdw = (span + 15) / 16, kdw = (span + 31) / 32;
-    if (n_reads != n) return fail(TPS_E_ARG, "tails, begin and end must hold %lld reads", (long long)n);
-    if (codes_len != n * cdw) return fail(TPS_E_ARG, "codes must hold %lld dwords", (long long)(n * cdw));
-    if (keep_len != n * kdw) return fail(TPS_E_ARG, "keep must hold %lld dwords", (long long)(n * kdw));
+    if ((rc = tps::end_window_check(n, unit, m, k, tails, begin, end, n_reads, span, codes, codes_len, keep, keep_len, &why))) return fail(rc, "%s", why.msg);
     if (n == 0) return TPS_OK;
-    if (!tails || !begin || !end || !codes || !keep) return fail(TPS_E_ARG, "null tails / begin / end / codes / keep");
-    int64_t at = 0;
-    if ((rc = tps::ends_check_reads(tails, begin, end, n, &why, &at))) return fail(rc, "read %lld: %s", (long long)at, why);
-    if ((rc = tps::window_check_reads(begin, end, n, span, &why, &at))) return fail(rc, "read %lld: %s", (long long)at, why);
     // (like the sketch: the pattern table, the slot's tails, its scan outputs and its plan are not touched)
-    const int w = m < tps::TRACT_MAX_WORD ? m : tps::TRACT_MAX_WORD;
-    std::vector<uint32_t> table((size_t)tps::tract_table_dw(w));
-    tps::tract_hit_table(unit, m, table.data());
-    const size_t tab_bytes = table.size() * 4, co_bytes = (size_t)n * cdw * 4, kp_bytes = (size_t)n * kdw * 4;
-    const size_t off_begin = (((size_t)n + 15) & ~(size_t)15), off_end = off_begin + (size_t)n * 4;
-    if ((rc = c->tract_table.ensure(tab_bytes))) return rc;
-    if ((rc = c->ends_in.ensure(off_end + (size_t)n * 4))) return rc;
-    if ((rc = c->window_out.ensure(co_bytes + kp_bytes))) return rc;
+    const int cdw = (span + 15) / 16, kdw = (span + 31) / 32;
+    tps::Layout in, out;
+    const tps::RegionAt reg = tps::region_layout(in, n);
+    const size_t co_bytes = (size_t)n * cdw * 4, kp_bytes = (size_t)n * kdw * 4;
+    const size_t off_co = out.add(co_bytes), off_kp = out.add(kp_bytes);
+    if ((rc = c->ends_in.ensure(in.total))) return rc;
+    if ((rc = c->window_out.ensure(out.total))) return rc;
     TPS_POISON(c->window_out);
-    HIP_TRY(hipMemcpyAsync(c->tract_table.p, table.data(), tab_bytes, hipMemcpyHostToDevice, c->stream));      // (pageable: the copy has left `table` when the call returns)
-    HIP_TRY(hipMemcpyAsync(c->ends_in.p, tails, (size_t)n, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync((char*)c->ends_in.p + off_begin, begin, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync((char*)c->ends_in.p + off_end, end, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    std::vector<uint32_t> table;
+    if ((rc = upload_hit_table(c, unit, m, table, &w))) return rc;
     tps::EndWindowArgs a{};
-    a.seq2 = (const uint32_t*)sl->seq2.p;
-    a.inv = (const uint16_t*)sl->inv.p;
-    a.desc = (const tps_read_desc*)sl->desc.p;
+    set_batch(a, *sl);
+    if ((rc = upload_region(c, c->ends_in, reg, tails, begin, end, n, a))) return rc;
     a.table = (const uint32_t*)c->tract_table.p;
-    a.tails = (const uint8_t*)c->ends_in.p;
-    a.begin = (const int32_t*)((const char*)c->ends_in.p + off_begin);
-    a.end = (const int32_t*)((const char*)c->ends_in.p + off_end);
-    a.codes = (uint32_t*)c->window_out.p;
-    a.keep = (uint32_t*)((char*)c->window_out.p + co_bytes);
+    a.codes = at<uint32_t>(c->window_out, off_co);
+    a.keep = at<uint32_t>(c->window_out, off_kp);
     a.n_reads = n;
     a.w = w; a.k = k; a.cdw = cdw; a.kdw = kdw;
-    hipLaunchKernelGGL(tps::end_window_kernel, dim3((unsigned)((n + tps::ENDS_WPG - 1) / tps::ENDS_WPG)), dim3(tps::NT * tps::ENDS_WPG), 0, c->stream, a);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(codes, a.codes, co_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(keep, a.keep, kp_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return TPS_OK;
+    if ((rc = launch_waves(c, tps::end_window_kernel, n, tps::ENDS_WPG, a))) return rc;
+    return download(c, {{codes, a.codes, co_bytes}, {keep, a.keep, kp_bytes}});
 }
 
 int tps_window_offsets(tps_ctx* c, const uint32_t* codes, const uint32_t* keep, const int32_t* length, const int32_t* ref, int64_t n, int32_t span,
                        int32_t k, int32_t* offset, int32_t* votes, int32_t* second, int64_t out_len) {
     int rc;
+    tps::Why why;
     if ((rc = bind(c))) return rc;
-    const char* why = "";
-    if ((rc = tps::offsets_check(n, span, k, out_len, &why))) return fail(rc, "%s", why);
+    if ((rc = tps::window_offsets_check(codes, keep, length, ref, n, span, k, offset, votes, second, out_len, &why))) return fail(rc, "%s", why.msg);
     if (n == 0) return TPS_OK;
-    if (!codes || !keep || !length || !ref || !offset || !votes || !second) return fail(TPS_E_ARG, "null codes / keep / length / ref / offset / votes / second");
-    int64_t at = 0;
-    if ((rc = tps::offsets_check_rows(length, ref, n, span, &why, &at))) return fail(rc, "row %lld: %s", (long long)at, why);
     const int cdw = (span + 15) / 16, kdw = (span + 31) / 32;
+    tps::Layout in, out;
     const size_t co_bytes = (size_t)n * cdw * 4, kp_bytes = (size_t)n * kdw * 4, n_bytes = (size_t)n * 4;
-    if ((rc = c->offsets_in.ensure(co_bytes + kp_bytes + 2 * n_bytes))) return rc;
-    if ((rc = c->offsets_out.ensure(3 * n_bytes))) return rc;
+    const size_t in_co = in.add(co_bytes), in_kp = in.add(kp_bytes), in_len = in.add(n_bytes), in_ref = in.add(n_bytes);
+    const size_t off_of = out.add(n_bytes), off_vo = out.add(n_bytes), off_se = out.add(n_bytes);
+    if ((rc = c->offsets_in.ensure(in.total))) return rc;
+    if ((rc = c->offsets_out.ensure(out.total))) return rc;
     TPS_POISON(c->offsets_out);
-    char* in = (char*)c->offsets_in.p;
-    HIP_TRY(hipMemcpyAsync(in, codes, co_bytes, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(in + co_bytes, keep, kp_bytes, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(in + co_bytes + kp_bytes, length, n_bytes, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(in + co_bytes + kp_bytes + n_bytes, ref, n_bytes, hipMemcpyHostToDevice, c->stream));
     tps::OffsetArgs a{};
-    a.codes = (const uint32_t*)in;
-    a.keep = (const uint32_t*)(in + co_bytes);
-    a.length = (const int32_t*)(in + co_bytes + kp_bytes);
-    a.ref = (const int32_t*)(in + co_bytes + kp_bytes + n_bytes);
-    a.offset = (int32_t*)c->offsets_out.p;
-    a.votes = (int32_t*)((char*)c->offsets_out.p + n_bytes);
-    a.second = (int32_t*)((char*)c->offsets_out.p + 2 * n_bytes);
+    a.codes = at<const uint32_t>(c->offsets_in, in_co);
+    a.keep = at<const uint32_t>(c->offsets_in, in_kp);
+    a.length = at<const int32_t>(c->offsets_in, in_len);
+    a.ref = at<const int32_t>(c->offsets_in, in_ref);
+    HIP_TRY(hipMemcpyAsync((void*)a.codes, codes, co_bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync((void*)a.keep, keep, kp_bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync((void*)a.length, length, n_bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync((void*)a.ref, ref, n_bytes, hipMemcpyHostToDevice, c->stream));
+    a.offset = at<int32_t>(c->offsets_out, off_of);
+    a.votes = at<int32_t>(c->offsets_out, off_vo);
+    a.second = at<int32_t>(c->offsets_out, off_se);
     a.n = n;
     a.k = k; a.cdw = cdw; a.kdw = kdw;
-    hipLaunchKernelGGL(tps::window_offsets_kernel, dim3((unsigned)((n + tps::OFFSETS_WPG - 1) / tps::OFFSETS_WPG)), dim3(tps::NT * tps::OFFSETS_WPG), 0, c->stream, a);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(offset, a.offset, n_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(votes, a.votes, n_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(second, a.second, n_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return TPS_OK;
+    if ((rc = launch_waves(c, tps::window_offsets_kernel, n, tps::OFFSETS_WPG, a))) return rc;
+    return download(c, {{offset, a.offset, n_bytes}, {votes, a.votes, n_bytes}, {second, a.second, n_bytes}});
 }
 
 int tps_window_place(tps_ctx* c, const uint32_t* codes, int64_t codes_len, const uint32_t* keep, int64_t keep_len, const int32_t* length, int64_t n,
@@ -1763,102 +1710,80 @@ int tps_window_place(tps_ctx* c, const uint32_t* codes, int64_t codes_len, const
                      int32_t n_ref, int32_t span, int32_t k, int32_t max_occ, int32_t* ref, int32_t* total, int32_t* runner_ref, int32_t* runner,
                      int32_t* offset, int32_t* votes, int32_t* second, int64_t out_len) {
     int rc;
+    tps::Why why;
     if ((rc = bind(c))) return rc;
-    const char* why = "";
-    if ((rc = tps::place_check(n, n_ref, span, k, max_occ, codes_len, keep_len, ref_codes_len, ref_keep_len, out_len, &why))) return fail(rc, "%s", why);
-    if (!ref_codes || !ref_keep || !ref_length) return fail(TPS_E_ARG, "null ref_codes / ref_keep / ref_length");
-    int64_t at = 0;
-    if ((rc = tps::place_check_rows(ref_length, n_ref, span, &why, &at))) return fail(rc, "reference row %lld: %s", (long long)at, why);
+    const bool have_outs = ref && total && runner_ref && runner && offset && votes && second;
+    if ((rc = tps::window_place_check(codes, codes_len, keep, keep_len, length, n, ref_codes, ref_codes_len, ref_keep, ref_keep_len, ref_length, n_ref, span, k,
+                                      max_occ, have_outs, out_len, &why)))
+        return fail(rc, "%s", why.msg);
     if (n == 0) return TPS_OK;
-    if (!codes || !keep || !length || !ref || !total || !runner_ref || !runner || !offset || !votes || !second)
-        return fail(TPS_E_ARG, "null codes / keep / length / ref / total / runner_ref / runner / offset / votes / second");
-    if ((rc = tps::place_check_rows(length, n, span, &why, &at))) return fail(rc, "row %lld: %s", (long long)at, why);
     const int cdw = (span + 15) / 16, kdw = (span + 31) / 32;
     tps::PlaceIndex ix;
     tps::place_index_build(ref_codes, ref_keep, ref_length, n_ref, cdw, kdw, k, max_occ, ix);
+    tps::Layout in, idx;
     const size_t co_bytes = (size_t)n * cdw * 4, kp_bytes = (size_t)n * kdw * 4, n_bytes = (size_t)n * 4;
     const size_t dir_bytes = ix.dir.size() * 4, key_bytes = ix.keys.size() * 4, ent_bytes = ix.ent.size() * 4;
-    if ((rc = c->place_in.ensure(co_bytes + kp_bytes + n_bytes))) return rc;
-    if ((rc = c->place_idx.ensure(dir_bytes + key_bytes + ent_bytes))) return rc;
+    const size_t in_co = in.add(co_bytes), in_kp = in.add(kp_bytes), in_len = in.add(n_bytes);
+    const size_t off_dir = idx.add(dir_bytes), off_key = idx.add(key_bytes), off_ent = idx.add(ent_bytes);
+    if ((rc = c->place_in.ensure(in.total))) return rc;
+    if ((rc = c->place_idx.ensure(idx.total))) return rc;
     if ((rc = c->place_out.ensure(tps::PLACE_OUTS * n_bytes))) return rc;
     TPS_POISON(c->place_in);
     TPS_POISON(c->place_idx);
     TPS_POISON(c->place_out);
-    char* in = (char*)c->place_in.p;
-    char* idx = (char*)c->place_idx.p;
-    HIP_TRY(hipMemcpyAsync(in, codes, co_bytes, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(in + co_bytes, keep, kp_bytes, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(in + co_bytes + kp_bytes, length, n_bytes, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(idx, ix.dir.data(), dir_bytes, hipMemcpyHostToDevice, c->stream));
-    if (key_bytes) HIP_TRY(hipMemcpyAsync(idx + dir_bytes, ix.keys.data(), key_bytes, hipMemcpyHostToDevice, c->stream));
-    if (ent_bytes) HIP_TRY(hipMemcpyAsync(idx + dir_bytes + key_bytes, ix.ent.data(), ent_bytes, hipMemcpyHostToDevice, c->stream));
     tps::PlaceArgs a{};
-    a.codes = (const uint32_t*)in;
-    a.keep = (const uint32_t*)(in + co_bytes);
-    a.length = (const int32_t*)(in + co_bytes + kp_bytes);
-    a.dir = (const uint32_t*)idx;
-    a.keys = (const uint32_t*)(idx + dir_bytes);
-    a.ent = (const uint32_t*)(idx + dir_bytes + key_bytes);
+    a.codes = at<const uint32_t>(c->place_in, in_co);
+    a.keep = at<const uint32_t>(c->place_in, in_kp);
+    a.length = at<const int32_t>(c->place_in, in_len);
+    a.dir = at<const uint32_t>(c->place_idx, off_dir);
+    a.keys = at<const uint32_t>(c->place_idx, off_key);
+    a.ent = at<const uint32_t>(c->place_idx, off_ent);
+    HIP_TRY(hipMemcpyAsync((void*)a.codes, codes, co_bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync((void*)a.keep, keep, kp_bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync((void*)a.length, length, n_bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync((void*)a.dir, ix.dir.data(), dir_bytes, hipMemcpyHostToDevice, c->stream));
+    if (key_bytes) HIP_TRY(hipMemcpyAsync((void*)a.keys, ix.keys.data(), key_bytes, hipMemcpyHostToDevice, c->stream));
+    if (ent_bytes) HIP_TRY(hipMemcpyAsync((void*)a.ent, ix.ent.data(), ent_bytes, hipMemcpyHostToDevice, c->stream));
     a.out = (int32_t*)c->place_out.p;
     a.n = n;
     a.R = n_ref; a.k = k; a.cdw = cdw; a.kdw = kdw; a.shift = 32 - ix.bits;
-    hipLaunchKernelGGL(tps::window_place_kernel, dim3((unsigned)((n + tps::PLACE_WPG - 1) / tps::PLACE_WPG)), dim3(tps::NT * tps::PLACE_WPG), 0, c->stream, a);
-    HIP_TRY(hipGetLastError());
-    int32_t* outs[tps::PLACE_OUTS] = {ref, total, runner_ref, runner, offset, votes, second};
-    for (int j = 0; j < tps::PLACE_OUTS; ++j) HIP_TRY(hipMemcpyAsync(outs[j], (char*)c->place_out.p + j * n_bytes, n_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return TPS_OK;
+    if ((rc = launch_waves(c, tps::window_place_kernel, n, tps::PLACE_WPG, a))) return rc;
+    static_assert(tps::PLACE_OUTS == 7, "the seven outputs behind one another, n entries each");
+    return download(c, {{ref, a.out, n_bytes}, {total, a.out + n, n_bytes}, {runner_ref, a.out + 2 * n, n_bytes}, {runner, a.out + 3 * n, n_bytes},
+                        {offset, a.out + 4 * n, n_bytes}, {votes, a.out + 5 * n, n_bytes}, {second, a.out + 6 * n, n_bytes}});
 }
 
 int tps_batch_adapter_find(tps_ctx* c, int32_t slot, const uint64_t* patterns, const int32_t* pat_len, int32_t n_pat, const uint8_t* tails,
                            const int32_t* begin, const int32_t* end, int64_t n_reads, uint16_t* hits, int64_t hits_len) {
     int rc;
-    if ((rc = bind(c))) return rc;
-    Slot* sl = get_slot(c, slot);
-    if (!sl) return TPS_E_ARG;
-    if (sl->n < 0) return fail(TPS_E_STATE, "no batch uploaded in this slot");
-    const char* why = "";
-    int pat_at = 0;
-    if ((rc = tps::adapter_check(patterns, pat_len, n_pat, &why, &pat_at))) return fail(rc, "pattern %d: %s", pat_at, why);
+    Slot* sl;
+    tps::Why why;
+    if ((rc = need_batch(c, slot, &sl))) return rc;
     const int64_t n = sl->n;
-    if (n_reads != n) return fail(TPS_E_ARG, "tails, begin and end must hold %lld reads", (long long)n);
-    if (hits_len != n * n_pat * 2) return fail(TPS_E_ARG, "hits must hold %lld values", (long long)(n * n_pat * 2));
+    if ((rc = tps::adapter_find_check(n, patterns, pat_len, n_pat, tails, begin, end, n_reads, hits, hits_len, &why))) return fail(rc, "%s", why.msg);
     if (n == 0) return TPS_OK;
-    if (!tails || !begin || !end || !hits) return fail(TPS_E_ARG, "null tails / begin / end / hits");
-    int64_t at = 0;
-    if ((rc = tps::adapter_check_reads(tails, begin, end, n, &why, &at))) return fail(rc, "read %lld: %s", (long long)at, why);
     // (no pattern table; the slot's tails, its scan outputs and its plan are not touched: a scan before and after the call gives the same results)
     uint64_t peq[4 * tps::ADAPTER_MAX_PATTERNS];
     tps::adapter_build_peq(patterns, pat_len, n_pat, peq);
+    tps::Layout in;
     const size_t peq_bytes = (size_t)n_pat * 32, len_bytes = (size_t)n_pat * 4, out_bytes = (size_t)n * n_pat * 4;
-    const size_t off_len = peq_bytes, off_tails = (off_len + len_bytes + 15) & ~(size_t)15, off_begin = (off_tails + (size_t)n + 15) & ~(size_t)15,
-                 off_end = off_begin + (size_t)n * 4;
-    if ((rc = c->adapter_in.ensure(off_end + (size_t)n * 4))) return rc;
+    const size_t off_peq = in.add(peq_bytes), off_len = in.add(len_bytes);
+    const tps::RegionAt reg = tps::region_layout(in, n);
+    if ((rc = c->adapter_in.ensure(in.total))) return rc;
     if ((rc = c->adapter_out.ensure(out_bytes))) return rc;
     TPS_POISON(c->adapter_out);
-    char* in = (char*)c->adapter_in.p;
-    HIP_TRY(hipMemcpyAsync(in, peq, peq_bytes, hipMemcpyHostToDevice, c->stream));      // (pageable: the copy has left `peq` when the call returns)
-    HIP_TRY(hipMemcpyAsync(in + off_len, pat_len, len_bytes, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(in + off_tails, tails, (size_t)n, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(in + off_begin, begin, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(in + off_end, end, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
     tps::AdapterArgs a{};
-    a.seq2 = (const uint32_t*)sl->seq2.p;
-    a.inv = (const uint16_t*)sl->inv.p;
-    a.desc = (const tps_read_desc*)sl->desc.p;
-    a.peq = (const uint64_t*)in;
-    a.pat_len = (const int32_t*)(in + off_len);
-    a.tails = (const uint8_t*)(in + off_tails);
-    a.begin = (const int32_t*)(in + off_begin);
-    a.end = (const int32_t*)(in + off_end);
+    set_batch(a, *sl);
+    a.peq = at<const uint64_t>(c->adapter_in, off_peq);
+    a.pat_len = at<const int32_t>(c->adapter_in, off_len);
+    HIP_TRY(hipMemcpyAsync((void*)a.peq, peq, peq_bytes, hipMemcpyHostToDevice, c->stream));      // (pageable: the copy has left `peq` when the call returns)
+    HIP_TRY(hipMemcpyAsync((void*)a.pat_len, pat_len, len_bytes, hipMemcpyHostToDevice, c->stream));
+    if ((rc = upload_region(c, c->adapter_in, reg, tails, begin, end, n, a))) return rc;
     a.hits = (uint32_t*)c->adapter_out.p;
     a.n_reads = n;
     a.n_pat = n_pat;
-    hipLaunchKernelGGL(tps::adapter_find_kernel, dim3((unsigned)((n + tps::ADAPTER_WPG - 1) / tps::ADAPTER_WPG)), dim3(tps::NT * tps::ADAPTER_WPG), 0, c->stream, a);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(hits, a.hits, out_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return TPS_OK;
+    if ((rc = launch_waves(c, tps::adapter_find_kernel, n, tps::ADAPTER_WPG, a))) return rc;
+    return download(c, {{hits, a.hits, out_bytes}});
 }
 
 int tps_batch_set_tails(tps_ctx* c, int32_t slot, const uint8_t* tails) {

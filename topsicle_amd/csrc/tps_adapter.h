@@ -83,6 +83,21 @@ static inline int adapter_check_reads(const uint8_t* tails, const int32_t* begin
     }
     return TPS_OK;
 }
+// Every refusal of tps_batch_adapter_find that needs no context, in the library's order, the message in *why (host code; the library
+// and the emulation call it).  n = the reads of the batch; an empty batch needs no per-read arrays.
+static inline int adapter_find_check(int64_t n, const uint64_t* patterns, const int32_t* pat_len, int n_pat, const uint8_t* tails, const int32_t* begin,
+                                     const int32_t* end, int64_t n_reads, const void* hits, int64_t hits_len, Why* why) {
+    const char* s = "";
+    int pat_at = 0;
+    int64_t at = 0;
+    if (const int rc = adapter_check(patterns, pat_len, n_pat, &s, &pat_at)) return refuse(why, rc, "pattern %d: %s", pat_at, s);
+    if (n_reads != n) return refuse(why, TPS_E_ARG, "tails, begin and end must hold %lld reads", (long long)n);
+    if (hits_len != n * n_pat * 2) return refuse(why, TPS_E_ARG, "hits must hold %lld values", (long long)(n * n_pat * 2));
+    if (n == 0) return TPS_OK;
+    if (!tails || !begin || !end || !hits) return refuse(why, TPS_E_ARG, "null tails / begin / end / hits");
+    if (const int rc = adapter_check_reads(tails, begin, end, n, &s, &at)) return refuse(why, rc, "read %lld: %s", (long long)at, s);
+    return TPS_OK;
+}
 // peq[j][c]: bit i set exactly where letter i of pattern j has code c (patterns as adapter_check takes them)
 static inline void adapter_build_peq(const uint64_t* patterns, const int32_t* pat_len, int n_pat, uint64_t* peq) {
     for (int j = 0; j < n_pat; ++j) {

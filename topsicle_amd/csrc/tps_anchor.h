@@ -101,6 +101,35 @@ static inline int offsets_check_rows(const int32_t* length, const int32_t* ref, 
     return TPS_OK;
 }
 
+// Every refusal of tps_batch_end_window and of tps_window_offsets that needs no context, in the library's order, the message in *why
+// (host code; the library and the emulation call them).  n = the reads of the batch, the rows of the call; n = 0 needs no arrays.
+static inline int end_window_check(int64_t n, uint64_t unit, int m, int k, const uint8_t* tails, const int32_t* begin, const int32_t* end, int64_t n_reads,
+                                   int span, const void* codes, int64_t codes_len, const void* keep, int64_t keep_len, Why* why) {
+    const char* s = "";
+    int64_t at = 0;
+    if (const int rc = ends_check(unit, m, k, ENDS_MIN_BUCKETS, &s)) return refuse(why, rc, "%s", s);
+    if (const int rc = window_check_span(span, k, &s)) return refuse(why, rc, "%s", s);
+    const int cdw = (span + 15) / 16, kdw = (span + 31) / 32;
+    if (n_reads != n) return refuse(why, TPS_E_ARG, "tails, begin and end must hold %lld reads", (long long)n);
+    if (codes_len != n * cdw) return refuse(why, TPS_E_ARG, "codes must hold %lld dwords", (long long)(n * cdw));
+    if (keep_len != n * kdw) return refuse(why, TPS_E_ARG, "keep must hold %lld dwords", (long long)(n * kdw));
+    if (n == 0) return TPS_OK;
+    if (!tails || !begin || !end || !codes || !keep) return refuse(why, TPS_E_ARG, "null tails / begin / end / codes / keep");
+    if (const int rc = ends_check_reads(tails, begin, end, n, &s, &at)) return refuse(why, rc, "read %lld: %s", (long long)at, s);
+    if (const int rc = window_check_reads(begin, end, n, span, &s, &at)) return refuse(why, rc, "read %lld: %s", (long long)at, s);
+    return TPS_OK;
+}
+static inline int window_offsets_check(const void* codes, const void* keep, const int32_t* length, const int32_t* ref, int64_t n, int span, int k,
+                                       const void* offset, const void* votes, const void* second, int64_t out_len, Why* why) {
+    const char* s = "";
+    int64_t at = 0;
+    if (const int rc = offsets_check(n, span, k, out_len, &s)) return refuse(why, rc, "%s", s);
+    if (n == 0) return TPS_OK;
+    if (!codes || !keep || !length || !ref || !offset || !votes || !second) return refuse(why, TPS_E_ARG, "null codes / keep / length / ref / offset / votes / second");
+    if (const int rc = offsets_check_rows(length, ref, n, span, &s, &at)) return refuse(why, rc, "row %lld: %s", (long long)at, s);
+    return TPS_OK;
+}
+
 // the 16 bits of x, bit j at bits 2j and 2j + 1
 TPS_DEV uint32_t anchor_pairs(uint32_t x) {
     x = (x | (x << 8)) & 0x00FF00FFu;

@@ -31,6 +31,7 @@
 #include <stdint.h>
 #include "../../include/topsicle_hip.h"
 #include "tps_wave.h"
+#include "tps_check.h"
 
 namespace tps {
 
@@ -3675,6 +3676,18 @@ constexpr int FOLLOW_MAX_SPAN = 4096;                      // hi - lo
 constexpr int FOLLOW_SEQ_DW = 4 * ((63 + FOLLOW_MAX_SPAN + 63) / 64) + 8;
 constexpr int FOLLOW_PW = FOLLOW_MAX_SPAN / 32;
 constexpr int FOLLOW_LDS_DW = FOLLOW_SEQ_DW + FOLLOW_SEQ_DW / 2 + 4 + 15 * FOLLOW_PW + 4;   // seq2, val, flag, occurrence / pick bits
+// Every refusal of tps_batch_kmer_followers that needs no context, in the library's order (host code; the library and the emulation
+// call it): TPS_OK, or the code and *why.  P = the patterns of the table, n = the reads of the batch.
+static inline int followers_check(int P, int64_t n, int n_fwd, int follow, int lo, int hi, const void* picks, int64_t picks_words, const void* hist,
+                                  int64_t hist_len, Why* why) {
+    if (n_fwd < 1 || n_fwd > 15 || 2 * n_fwd > P) return refuse(why, TPS_E_ARG, "n_fwd must be 1..15 and the table must hold the complements behind the k-mers");
+    if (follow < 0 || follow > 8) return refuse(why, TPS_E_CAPACITY, "follow must be 0..8 bases");
+    if (lo < 0 || hi <= lo || hi - lo > FOLLOW_MAX_SPAN) return refuse(why, TPS_E_CAPACITY, "the scanned range [lo, hi) must hold 1..%d bases", FOLLOW_MAX_SPAN);
+    const int64_t want = n * 2 * n_fwd * ((hi - lo + 31) / 32), bins = 2ll * n_fwd * ((1 << (2 * follow)) + 1);
+    if (!picks || picks_words != want) return refuse(why, TPS_E_ARG, "picks must hold %lld words", (long long)want);
+    if (hist && hist_len != bins) return refuse(why, TPS_E_ARG, "hist must hold %lld counters", (long long)bins);
+    return TPS_OK;
+}
 TPS_DEV void followers_read(const FollowArgs& a, int64_t r, uint32_t* lds) {
     uint32_t* seq2 = lds;
     uint16_t* val = (uint16_t*)(lds + FOLLOW_SEQ_DW);

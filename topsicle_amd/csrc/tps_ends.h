@@ -114,6 +114,29 @@ static inline int links_check(int64_t n, int buckets, int64_t sketch_len, int mi
     return TPS_OK;
 }
 
+// Every refusal of tps_batch_end_sketch and of tps_sketch_links that needs no context, in the library's order, the message in *why
+// (host code; the library and the emulation call them).  n = the reads of the batch; an empty batch needs no arrays.
+static inline int end_sketch_check(int64_t n, uint64_t unit, int m, int k, int buckets, const uint8_t* tails, const int32_t* begin, const int32_t* end,
+                                   int64_t n_reads, const void* sketch, int64_t sketch_len, const void* kept, int64_t kept_len, Why* why) {
+    const char* s = "";
+    int64_t at = 0;
+    if (const int rc = ends_check(unit, m, k, buckets, &s)) return refuse(why, rc, "%s", s);
+    if (n_reads != n) return refuse(why, TPS_E_ARG, "tails, begin and end must hold %lld reads", (long long)n);
+    if (sketch_len != n * buckets) return refuse(why, TPS_E_ARG, "sketch must hold %lld hashes", (long long)(n * buckets));
+    if (kept_len != n) return refuse(why, TPS_E_ARG, "kept must hold %lld counters", (long long)n);
+    if (n == 0) return TPS_OK;
+    if (!tails || !begin || !end || !sketch || !kept) return refuse(why, TPS_E_ARG, "null tails / begin / end / sketch / kept");
+    if (const int rc = ends_check_reads(tails, begin, end, n, &s, &at)) return refuse(why, rc, "read %lld: %s", (long long)at, s);
+    return TPS_OK;
+}
+static inline int sketch_links_check(const void* sketch, int64_t n, int buckets, int64_t sketch_len, int min_match, int max_links, const void* degree,
+                                     int64_t degree_len, const void* links, int64_t links_len, const void* matches, int64_t matches_len, Why* why) {
+    const char* s = "";
+    if (const int rc = links_check(n, buckets, sketch_len, min_match, max_links, degree_len, links_len, matches_len, &s)) return refuse(why, rc, "%s", s);
+    if (n > 0 && (!sketch || !degree || !links || !matches)) return refuse(why, TPS_E_ARG, "null sketch / degree / links / matches");
+    return TPS_OK;
+}
+
 // the sketches bucket-major: t[b][i] = sketch[i][b] (host code, in tiles of 64 rows: both sides stay in cache)
 static inline void links_transpose(const uint32_t* sketch, int64_t n, int buckets, uint32_t* t) {
     for (int64_t i0 = 0; i0 < n; i0 += 64) {

@@ -50,6 +50,18 @@ static_assert(FOLLOW_SEQ_DW % 4 == 0 && MOTIF_LDS_DW % 4 == 0, "seq and every wa
 static_assert(MOTIF_LDS_DW <= FOLLOW_LDS_DW, "no more LDS per wave than the followers kernel takes");
 static_assert(2 * NT * 32 >= FOLLOW_MAX_SPAN, "64 bits of the per bitmap per lane cover the span");
 
+// Every refusal of tps_batch_motif_census that needs no context, in the library's order (host code; the library and the emulation
+// call it): TPS_OK, or the code and *why.  n = the reads of the batch.
+static inline int motif_census_check(int64_t n, int u_min, int u_max, int lo, int hi, const void* hits, int64_t n_hits, const void* counts,
+                                     int64_t counts_len, Why* why) {
+    if (u_min < 1 || u_max < u_min || u_max > MOTIF_MAX_PERIOD) return refuse(why, TPS_E_ARG, "the periods must be 1 <= u_min <= u_max <= %d", MOTIF_MAX_PERIOD);
+    if (lo < 0 || hi <= lo || hi - lo > FOLLOW_MAX_SPAN) return refuse(why, TPS_E_CAPACITY, "the scanned range [lo, hi) must hold 1..%d bases", FOLLOW_MAX_SPAN);
+    const int nu = u_max - u_min + 1;
+    if ((!hits && n > 0) || n_hits != 2 * n) return refuse(why, TPS_E_ARG, "hits must hold %lld entries", (long long)(2 * n));
+    if (counts && counts_len != 2 * n * nu) return refuse(why, TPS_E_ARG, "counts must hold %lld counters", (long long)(2 * n * nu));
+    return TPS_OK;
+}
+
 // the even bits of x (bit 2 j -> bit j): one plane of sixteen 2-bit codes
 TPS_DEV uint32_t motif_even_bits(uint32_t x) {
     x &= 0x55555555u;

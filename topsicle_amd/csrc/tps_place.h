@@ -76,6 +76,23 @@ static inline int place_check_rows(const int32_t* length, int64_t n, int span, c
     return TPS_OK;
 }
 
+// Every refusal of tps_window_place, none of which needs the context, in the library's order, the message in *why (host code; the
+// library and the emulation call it).  The reference is checked whatever n is; n = 0 needs no query arrays and no outputs.
+static inline int window_place_check(const void* codes, int64_t codes_len, const void* keep, int64_t keep_len, const int32_t* length, int64_t n,
+                                     const void* ref_codes, int64_t ref_codes_len, const void* ref_keep, int64_t ref_keep_len, const int32_t* ref_length,
+                                     int64_t R, int span, int k, int max_occ, bool have_outs, int64_t out_len, Why* why) {
+    const char* s = "";
+    int64_t at = 0;
+    if (const int rc = place_check(n, R, span, k, max_occ, codes_len, keep_len, ref_codes_len, ref_keep_len, out_len, &s)) return refuse(why, rc, "%s", s);
+    if (!ref_codes || !ref_keep || !ref_length) return refuse(why, TPS_E_ARG, "null ref_codes / ref_keep / ref_length");
+    if (const int rc = place_check_rows(ref_length, R, span, &s, &at)) return refuse(why, rc, "reference row %lld: %s", (long long)at, s);
+    if (n == 0) return TPS_OK;
+    if (!codes || !keep || !length || !have_outs)
+        return refuse(why, TPS_E_ARG, "null codes / keep / length / ref / total / runner_ref / runner / offset / votes / second");
+    if (const int rc = place_check_rows(length, n, span, &s, &at)) return refuse(why, rc, "row %lld: %s", (long long)at, s);
+    return TPS_OK;
+}
+
 // The index of R reference rows (host code; the library and the emulation share it).
 struct PlaceIndex {
     std::vector<uint32_t> dir, keys, ent;

@@ -91,6 +91,19 @@ static inline int tract_check(uint64_t unit, int m, int block, int min_hits, int
     return TPS_OK;
 }
 
+// Every refusal of tps_batch_tract_map that needs no context, in the library's order, the message in *why (host code; the library and
+// the emulation call it).  n = the reads of the batch; an empty batch needs no arrays.
+static inline int tract_map_check(int64_t n, uint64_t unit, int m, int block, int min_hits, int gap, int min_blocks, int max_tracts, const void* tracts,
+                                  int64_t tracts_len, const void* found, int64_t found_len, const void* totals, int64_t totals_len, Why* why) {
+    const char* s = "";
+    if (const int rc = tract_check(unit, m, block, min_hits, gap, min_blocks, max_tracts, &s)) return refuse(why, rc, "%s", s);
+    if (tracts_len != n * 2 * max_tracts) return refuse(why, TPS_E_ARG, "tracts must hold %lld records", (long long)(n * 2 * max_tracts));
+    if (found_len != n * 2) return refuse(why, TPS_E_ARG, "found must hold %lld counters", (long long)(n * 2));
+    if (totals_len != n * 4) return refuse(why, TPS_E_ARG, "totals must hold %lld counters", (long long)(n * 4));
+    if (n > 0 && (!tracts || !found || !totals)) return refuse(why, TPS_E_ARG, "null tracts / found / totals");
+    return TPS_OK;
+}
+
 // one strand's run of flagged blocks (wave-uniform)
 struct TractRun {
     int32_t open, first, last, found;

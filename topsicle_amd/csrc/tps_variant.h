@@ -51,6 +51,31 @@ static_assert(FOLLOW_SEQ_DW % 4 == 0 && VARIANT_LDS_DW % 4 == 0, "seq and every 
 static_assert(VARIANT_MAX_BIN + VARIANT_MAX_UNIT - 1 < FOLLOW_MAX_SPAN, "a piece fits the staging area");
 static_assert(VARIANT_MIN_BIN >= VARIANT_MAX_UNIT, "every tract of m bases or more has a position in its first piece");
 
+// Every refusal of tps_batch_variant_census that needs no context, in the library's order (host code; the library and the emulation
+// call it): TPS_OK, or the code and *why.  n = the reads of the batch.
+static inline int variant_census_check(int64_t n, uint64_t unit, int m, const uint8_t* tails, const int32_t* begin, const int32_t* end, int64_t n_reads,
+                                       int bin, int n_bins, const void* counts, int64_t counts_len, const void* profile, int64_t profile_len, Why* why) {
+    if (m < 2 || m > VARIANT_MAX_UNIT) return refuse(why, TPS_E_ARG, "the unit must have 2..%d letters", VARIANT_MAX_UNIT);
+    if (m < 32 && (unit >> (2 * m)) != 0) return refuse(why, TPS_E_ARG, "the unit has codes behind its %d letters", m);
+    for (int d = 1; d < m; ++d) {
+        if (m % d) continue;
+        const uint64_t rot = (unit >> (2 * d)) | (unit << (2 * (m - d)));       // the unit rotated left by d letters
+        if (((rot ^ unit) & (~0ull >> (64 - 2 * m))) == 0) return refuse(why, TPS_E_ARG, "the unit is a power of its first %d letters: pass the primitive root", d);
+    }
+    if (bin < VARIANT_MIN_BIN || bin > VARIANT_MAX_BIN) return refuse(why, TPS_E_CAPACITY, "bin must be %d..%d positions", VARIANT_MIN_BIN, VARIANT_MAX_BIN);
+    if (n_bins < 1 || n_bins > VARIANT_MAX_BINS) return refuse(why, TPS_E_CAPACITY, "n_bins must be 1..%d", VARIANT_MAX_BINS);
+    const int cols = 2 + 4 * m;
+    if (n_reads != n) return refuse(why, TPS_E_ARG, "tails, begin and end must hold %lld reads", (long long)n);
+    if (n > 0 && (!tails || !begin || !end)) return refuse(why, TPS_E_ARG, "null tails / begin / end");
+    if ((!counts && n > 0) || counts_len != n * cols) return refuse(why, TPS_E_ARG, "counts must hold %lld counters", (long long)(n * cols));
+    if (profile && profile_len != (int64_t)n_bins * cols) return refuse(why, TPS_E_ARG, "profile must hold %lld counters", (long long)n_bins * cols);
+    for (int64_t i = 0; i < n; ++i) {
+        if (tails[i] > 1) return refuse(why, TPS_E_ARG, "read %lld: tail must be 0 or 1", (long long)i);
+        if (begin[i] < 0 || end[i] < 0 || begin[i] > end[i]) return refuse(why, TPS_E_ARG, "read %lld: need 0 <= begin <= end", (long long)i);
+    }
+    return TPS_OK;
+}
+
 TPS_DEV int variant_popc(uint32_t x) { return popc(x); }
 TPS_DEV int variant_popc(uint64_t x) { return popc((uint32_t)x) + popc((uint32_t)(x >> 32)); }
 TPS_DEV int variant_ctz(uint32_t x) { return __builtin_ctz(x); }

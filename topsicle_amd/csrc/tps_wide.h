@@ -400,6 +400,20 @@ constexpr int FOLLOWW_LDS_DW = (FOLLOWW_OCC_OFF + NT + MISC_DW + 3) & ~3;    // 
 static_assert(FOLLOW_SEQ_DW % 4 == 0 && FOLLOWW_PM_OFF % 4 == 0 && FOLLOWW_PM_DW % 4 == 0 && FOLLOWW_LDS_DW % 4 == 0 && WIDE_IMG_DW % 4 == 0,
               "seq, the byte map and every wave's slice start on 16-byte boundaries (lds_load16 / lds_store16)");
 TPS_HD int64_t followers_wide_wg_lds_dwords() { return WIDE_IMG_DW + (int64_t)WPG * FOLLOWW_LDS_DW; }       // (does not depend on n_fwd or the span: sized for 32 and 4096)
+// Every refusal of tps_batch_kmer_followers_wide that needs no context, in the library's order (host code; the library and the
+// emulation call it): TPS_OK, or the code and *why.  P = the patterns of the table, n = the reads of the batch.
+static inline int followers_wide_check(int P, int64_t n, int n_fwd, int follow, int lo, int hi, const void* picks, int64_t picks_words, const void* hist,
+                                       int64_t hist_len, Why* why) {
+    if (n_fwd < 1 || n_fwd > FOLLOWW_MAX_FWD || 2 * n_fwd > P)
+        return refuse(why, TPS_E_ARG, "n_fwd must be 1..%d and the table must hold the complements behind the k-mers", FOLLOWW_MAX_FWD);
+    if (follow < 0) return refuse(why, TPS_E_ARG, "follow must not be negative");
+    if (lo < 0 || hi <= lo || hi - lo > FOLLOW_MAX_SPAN) return refuse(why, TPS_E_CAPACITY, "the scanned range [lo, hi) must hold 1..%d bases", FOLLOW_MAX_SPAN);
+    if (hist && follow > 8) return refuse(why, TPS_E_CAPACITY, "the followers histogram has 4^follow bins: follow must be 0..8 bases with it (pass no hist for more)");
+    const int64_t want = n * 2 * n_fwd * ((hi - lo + 31) / 32), bins = hist ? 2ll * n_fwd * ((1 << (2 * follow)) + 1) : 0;
+    if (!picks || picks_words != want) return refuse(why, TPS_E_ARG, "picks must hold %lld words", (long long)want);
+    if (hist && hist_len != bins) return refuse(why, TPS_E_ARG, "hist must hold %lld counters", (long long)bins);
+    return TPS_OK;
+}
 
 // bit j = byte j of the 16 equals g1 (g1 >= 1: an empty position never matches)
 TPS_DEV uint32_t wide_occ16(const u32x4& v, uint32_t g1) {

@@ -256,6 +256,16 @@ def resolve_ties(engine, slot: int, res: np.ndarray, n_patterns: int, jump: int 
     return len(idx)
 
 
+def _region(tails, begin, end, call):
+    """tails / begin / end of the calls that look at one region per read, as the C ABI takes them."""
+    tails = np.ascontiguousarray(tails, dtype=np.uint8)
+    begin = np.ascontiguousarray(begin, dtype=np.int32)
+    end = np.ascontiguousarray(end, dtype=np.int32)
+    if not (len(tails) == len(begin) == len(end)):
+        raise TopsicleHipError(f"{call}: tails, begin and end must have one entry per read")
+    return tails, begin, end
+
+
 class HipScanner:
     """One context on one MI355X.  Not thread-safe; use one per host thread and device."""
 
@@ -472,11 +482,7 @@ class HipScanner:
         from . import variants
         code, m = variants.unit_code(unit)
         n = self._n[slot]
-        tails = np.ascontiguousarray(tails, dtype=np.uint8)
-        begin = np.ascontiguousarray(begin, dtype=np.int32)
-        end = np.ascontiguousarray(end, dtype=np.int32)
-        if not (len(tails) == len(begin) == len(end)):
-            raise TopsicleHipError("variant_census: tails, begin and end must have one entry per read")
+        tails, begin, end = _region(tails, begin, end, "variant_census")
         cols = 2 + 4 * m
         counts = np.zeros((n, cols), dtype=np.uint32)
         profile = np.zeros((max(n_bins, 0), cols), dtype=np.int64) if want_profile else None      # (a bad bin count is the library's to refuse)
@@ -510,11 +516,7 @@ class HipScanner:
         from . import variants
         code, m = variants.unit_code(unit)
         n = self._n[slot]
-        tails = np.ascontiguousarray(tails, dtype=np.uint8)
-        begin = np.ascontiguousarray(begin, dtype=np.int32)
-        end = np.ascontiguousarray(end, dtype=np.int32)
-        if not (len(tails) == len(begin) == len(end)):
-            raise TopsicleHipError("end_sketch: tails, begin and end must have one entry per read")
+        tails, begin, end = _region(tails, begin, end, "end_sketch")
         nb = buckets if buckets in ENDS_BUCKETS else ENDS_BUCKETS[0]          # (a bad count is the library's to refuse)
         sketch = np.zeros((n, nb), dtype=np.uint32)
         kept = np.zeros(n, dtype=np.uint32)
@@ -547,11 +549,7 @@ class HipScanner:
         from . import variants
         code, m = variants.unit_code(unit)
         n = self._n[slot]
-        tails = np.ascontiguousarray(tails, dtype=np.uint8)
-        begin = np.ascontiguousarray(begin, dtype=np.int32)
-        end = np.ascontiguousarray(end, dtype=np.int32)
-        if not (len(tails) == len(begin) == len(end)):
-            raise TopsicleHipError("end_window: tails, begin and end must have one entry per read")
+        tails, begin, end = _region(tails, begin, end, "end_window")
         sp = span if 1 <= span <= ANCHOR_MAX_SPAN else 1                       # (a bad span is the library's to refuse)
         codes = np.zeros((n, (sp + 15) // 16), dtype=np.uint32)
         keep = np.zeros((n, (sp + 31) // 32), dtype=np.uint32)
@@ -609,11 +607,7 @@ class HipScanner:
         from . import adapters
         codes, lens = adapters.pattern_codes(patterns)
         n = self._n[slot]
-        tails = np.ascontiguousarray(tails, dtype=np.uint8)
-        begin = np.ascontiguousarray(begin, dtype=np.int32)
-        end = np.ascontiguousarray(end, dtype=np.int32)
-        if not (len(tails) == len(begin) == len(end)):
-            raise TopsicleHipError("adapter_find: tails, begin and end must have one entry per read")
+        tails, begin, end = _region(tails, begin, end, "adapter_find")
         hits = np.zeros((n, len(lens), 2), dtype=np.uint16)
         self._check(self.lib.tps_batch_adapter_find(self._h, slot, _ptr(codes), _ptr(lens), len(lens), _ptr(tails), _ptr(begin), _ptr(end), len(tails),
                                                     _ptr(hits), hits.size))
