@@ -484,6 +484,35 @@ int  tps_batch_adapter_find(tps_ctx* ctx, int32_t slot, const uint64_t* patterns
                             const uint8_t* tails, const int32_t* begin, const int32_t* end, int64_t n_reads, uint16_t* hits,
                             int64_t hits_len);
 
+/* ---- the boundary at base resolution, and its support -------------------------------------------------------------------- */
+/* One change point per read on the per-position hits of the telomere repeat, by likelihood, with the evidence for it; no pattern
+ * table (the reference has nothing comparable).  unit, m: as tps_batch_tract_map takes them, 4 <= m <= 32, a primitive word;
+ * w = min(m, 8).  For read r, h = the telomere-first string of tps_batch_variant_census: the upper-cased read (tails[r] = 0) or its
+ * reverse complement (tails[r] = 1).  end[r] is clamped to L.  N = end - begin - w + 1 positions (N <= 0: none).
+ *   hit      for i in [begin, begin + N): x_i = 1 when h[i .. i + w) has only ACGT letters and is within Hamming distance 1 of a
+ *            cyclic word of U; else 0.  This is strand 0 of the tract map's rule applied to h; for tail 1 it is the read's strand-1
+ *            hit at the mirrored position.
+ *   score    s_i = x_i ? +hit : -miss.  P(begin) = 0, P(j) = the sum of s_i over begin <= i < j, for j in [begin, begin + N]: the
+ *            log-likelihood of "telomere up to j, not telomere from j on", up to a constant.  A stretch keeps extending the tract
+ *            while its hit density exceeds miss / (hit + miss).
+ *   pos      the smallest j with P(j) maximal; score = P(pos).  pos = begin when nothing scores positive.
+ *   drop     score - P(begin + N), always >= 0; 0 when the tract runs to the region's end.
+ *   at_score P(clamp(at[r], begin, begin + N)): the caller passes the boundary it has called there.
+ *   hits     hits_before = the sum of x_i over i < pos; hits_after = the rest.
+ *   runner   the maximum of P(j) over the j with |j - pos| >= sep; runner_pos = the smallest such j.  Where there is no such j:
+ *            runner = 0, runner_pos = -1.  score - runner says how much worse the best boundary at least sep away is.
+ *   empty    a read with N <= 0 gets pos = begin, runner_pos = -1, everything else 0.
+ * Every row is written whole, every time; exact integers, identical from run to run.  TPS_E_ARG: the unit rules of
+ * tps_batch_tract_map, a negative begin / end / at, begin > end, a tail other than 0 / 1, n_reads or out_len that does not match
+ * the slot, null arrays with reads in the slot.  TPS_E_CAPACITY: hit or miss outside 1..16, sep outside 1..65535,
+ * end - begin > 65536 after end is clamped to L (named with the read: "read 7: ...").  TPS_E_STATE: an empty slot.  An empty batch
+ * is TPS_OK.  One launch (one wave per read); returns when the rows are in place.  The slot's scan state (tails, results, sums, raw
+ * rows) is not touched. */
+typedef struct tps_refine { int32_t pos, score, drop, at_score, hits_before, hits_after, runner, runner_pos; } tps_refine; /* 32 bytes */
+int  tps_batch_boundary_refine(tps_ctx* ctx, int32_t slot, uint64_t unit, int32_t m, const uint8_t* tails, const int32_t* begin,
+                               const int32_t* end, const int32_t* at, int64_t n_reads, int32_t hit, int32_t miss, int32_t sep,
+                               tps_refine* out, int64_t out_len);
+
 /* ---- measurement ----------------------------------------------------------------------- */
 /* hipEvent timings of the scan kernel launches since the last reset: number of launches,
  * total and mean milliseconds (events are recorded on the stream the kernel runs on). */

@@ -42,7 +42,7 @@ class Job:
     batch = `--telophrase 4 5 6`: the batch is parsed, packed and uploaded ONCE and scanned once per k (the reference
     re-parses the input for every k, main.py:206-235)."""
 
-    def __init__(self, patterns, prm: hiplib.Params, want_sums=False, want_raw=False, raw_sink=None, variants=None, tracts=None, ends=None, adapters=None):
+    def __init__(self, patterns, prm: hiplib.Params, want_sums=False, want_raw=False, raw_sink=None, variants=None, tracts=None, ends=None, adapters=None, refine=None):
         """raw_sink (with want_raw; rawnpz.RawNpzWriter): the raw rows of the reads the sink selects are written to its file by
         the worker that scanned the batch, device -> file, and the caller gets a `RawKept` in place of the rows.
         variants (variants.VariantSpec: unit, bin, n_bins, sink): the worker that scanned the batch runs the variant census of the
@@ -54,13 +54,17 @@ class Job:
         called boundary while the batch is still resident and hands (recs, results, sketch, kept) to the spec's sink -- and, for a
         spec with `anchor` set, the windows' packed letters and keep bits behind them (recs, results, sketch, kept, codes, keep).
         adapters (adapters.AdapterSpec: sequences, search, sink): the same worker searches the sequences in the first `search` bases of
-        every read with a called boundary while the batch is still resident and hands (recs, results, dist, end) to the spec's sink."""
+        every read with a called boundary while the batch is still resident and hands (recs, results, dist, end) to the spec's sink.
+        refine (refine.RefineSpec: unit, hit, miss, sep, sink): the same worker refines the boundary of every read with a called one,
+        position by position over [trimfirst, maxlen), while the batch is still resident and hands (recs, results, rows) to the spec's
+        sink."""
         self.patterns, self.prm, self.want_sums, self.want_raw = list(patterns), prm, bool(want_sums), bool(want_raw)
         self.raw_sink = raw_sink if want_raw else None
         self.variants = variants
         self.tracts = tracts
         self.ends = ends
         self.adapters = adapters
+        self.refine = refine
 
 
 class CensusJob:
@@ -189,6 +193,26 @@ def _find_adapters(job, eng, slot, recs, res, slot_index=None):
     spec.sink(recs, res, dist, aend)
 
 
+def _refine_boundaries(job, eng, slot, recs, res, slot_index=None):
+    """The boundary at base resolution of the reads the scan has just called (Job.refine), on the engine and slot that were scanned:
+    the region [trimfirst, maxlen) of the telomere-first string of every read whose boundary the CLI would store, with that boundary
+    as `at` (refine.regions), begin = end = at = 0 -- the row of an empty region -- for every other read.  `slot_index` as in
+    _census_variants (the region ends at maxlen: it lies inside the span packed for the second pass)."""
+    from . import refine
+    spec = job.refine
+    begin, end, at = refine.regions(res, int(job.prm.trimfirst), int(job.prm.slide), int(job.prm.maxlen), spec.w)
+    tails = np.where(end > begin, res["tail"], 0).astype(np.uint8)
+    rows = np.zeros(len(res), hiplib.REFINE_DTYPE)
+    rows["runner_pos"] = -1
+    kw = dict(hit=spec.hit, miss=spec.miss, sep=spec.sep)
+    if slot_index is None:
+        if eng is not None:
+            rows = eng.boundary_refine(slot, spec.unit, tails, begin, end, at, **kw)
+    elif len(slot_index):
+        rows[slot_index] = eng.boundary_refine(slot, spec.unit, tails[slot_index], begin[slot_index], end[slot_index], at[slot_index], **kw)
+    spec.sink(recs, res, rows)
+
+
 def _map_tracts(job, eng, slot, recs):
     """The tract map of the resident batch (Job.tracts), on the engine and slot that were scanned: every read, whole."""
     spec = job.tracts
@@ -308,6 +332,8 @@ def scan_jobs_heads(engine, recs, jobs, slot: int = 0, seq=None):
                     _sketch_ends(job, eng, slot_b, recs, res, slot_index=idx)
                 if getattr(job, "adapters", None) is not None:
                     _find_adapters(job, eng, slot_b, recs, res, slot_index=idx)
+                if getattr(job, "refine", None) is not None:
+                    _refine_boundaries(job, eng, slot_b, recs, res, slot_index=idx)
                 np.cumsum(np.where(passing, res["n_win"], 0), out=win_off[1:])
                 if job.want_sums:
                     sums, wo_b = eng.window_sums(slot_b)
@@ -324,6 +350,8 @@ def scan_jobs_heads(engine, recs, jobs, slot: int = 0, seq=None):
                     _sketch_ends(job, None, slot_b, recs, res)
                 if getattr(job, "adapters", None) is not None:
                     _find_adapters(job, None, slot_b, recs, res)
+                if getattr(job, "refine", None) is not None:
+                    _refine_boundaries(job, None, slot_b, recs, res)
                 if job.want_sums:
                     sums = np.zeros(0, np.int32)
                 if job.want_raw and job.raw_sink is not None and seq is not None:
@@ -401,6 +429,8 @@ def scan_jobs(engine, recs, jobs, slot: int = 0, seq=None):
                 _sketch_ends(job, eng, slot, recs, res)
             if getattr(job, "adapters", None) is not None:
                 _find_adapters(job, eng, slot, recs, res)
+            if getattr(job, "refine", None) is not None:
+                _refine_boundaries(job, eng, slot, recs, res)
             if getattr(job, "tracts", None) is not None:
                 _map_tracts(job, eng, slot, recs)
             sums = raw = win_off = None

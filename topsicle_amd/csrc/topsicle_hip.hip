@@ -29,6 +29,7 @@
 #include "tps_anchor.h"
 #include "tps_place.h"
 #include "tps_adapter.h"
+#include "tps_refine.h"
 #include "tps_layout.h"
 #include "tps_pack.h"
 #include "tps_plan.h"
@@ -186,6 +187,19 @@ __global__ void __launch_bounds__(NT * ADAPTER_WPG) adapter_find_kernel(AdapterA
     const int64_t r = (int64_t)blockIdx.x * ADAPTER_WPG + wave;
     if (r >= a.n_reads) return;
     adapter_read(a, r, smem + wave * ADAPTER_LDS_DW);
+}
+// The boundary at base resolution (tps_batch_boundary_refine; refine_read in csrc/tps_refine.h): the tract map's hit table in LDS,
+// shared by the workgroup's waves as there, then one wave per read.  The LDS is dynamic: the call sizes every wave's slice by the
+// longest region of the batch.
+__global__ void __launch_bounds__(NT * REFINE_WPG) boundary_refine_kernel(RefineArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+    const int tab_dw = tract_table_dw(a.w);
+    for (int i = (int)threadIdx.x; i < tab_dw; i += NT * REFINE_WPG) smem[i] = a.table[i];
+    __syncthreads();
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t r = (int64_t)blockIdx.x * REFINE_WPG + wave;
+    if (r >= a.n_reads) return;
+    refine_read(a, r, smem + TRACT_TABLE_DW + wave * refine_lds_dw(a.bal_dw), smem);
 }
 }  // namespace tps
 
@@ -454,6 +468,7 @@ struct tps_ctx {
     DevBuf offsets_in, offsets_out;   // tps_window_offsets: codes, keep, length and ref; offset, votes and second behind one another
     DevBuf place_in, place_idx, place_out;   // tps_window_place: the queries' codes, keep and length; the index's dir, keys and ent; the seven outputs behind one another
     DevBuf adapter_in, adapter_out;   // tps_batch_adapter_find: Peq, lengths, tails / begin / end; the hits
+    DevBuf refine_in, refine_out;     // tps_batch_boundary_refine: tails / begin / end / at; the rows (its table is tract_table)
     DevBuf ascii, ascii_off;          // staging of tps_batch_upload: ASCII bases + offsets, packed on the device right after the copy
     DevBuf nib, nib_src;              // staging of tps_batch_upload_nib4: BAM base codes + where each read's are, expanded right after the copy
     std::set<void*> pinned;           // host buffers handed out by tps_host_alloc
@@ -473,6 +488,7 @@ struct tps_ctx {
     int poison = 0;                   // tps_ctx_debug_option "poison": 1..255 = every call fills the output and scratch buffers it is about to use with this byte (tests: a byte nobody writes shows)
     int event_stride = 1;             // time every event_stride-th launch (tps_ctx_debug_option "event_stride"): timing costs ~3.5 us per launch
     uint64_t launch_seq = 0;
+    size_t lds_set_refine = 0;       // ... of boundary_refine_kernel
     size_t lds_set_generic = 0;      // hipFuncAttributeMaxDynamicSharedMemorySize as last raised, per scan kernel
     size_t lds_set_fused[KF_COUNT][KSLIDE_MAX - KSLIDE_MIN + 1] = {};
     uint32_t* h_flag = nullptr;      // mapped host word the pack kernel raises when a read has a non-ACGT letter
@@ -1048,7 +1064,7 @@ Slot* get_slot(tps_ctx* c, int slot) {
     return &c->slots[slot];
 }
 
-// ---- the steps the read-analysis calls share (tps_batch_kmer_followers .. tps_batch_adapter_find; DESIGN.md, "How a read-analysis
+// ---- the steps the read-analysis calls share (tps_batch_kmer_followers .. tps_batch_boundary_refine; DESIGN.md, "How a read-analysis
 // call is put together").  Each call: need_batch (or bind alone, where it takes no batch), its check function from the feature's
 // header, its layouts (tps_layout.h), ensure + TPS_POISON, its clearing memsets and input copies, launch_waves, download.
 
@@ -1102,10 +1118,10 @@ int upload_hit_table(tps_ctx* c, uint64_t unit, int m, std::vector<uint32_t>& ta
     return TPS_OK;
 }
 
-// one wave per read (or row), wpg waves per workgroup
+// one wave per read (or row), wpg waves per workgroup; lds_bytes: the dynamic LDS of a kernel that has some
 template <class A>
-int launch_waves(tps_ctx* c, void (*kernel)(A), int64_t n, int wpg, const A& a) {
-    hipLaunchKernelGGL(kernel, dim3((unsigned)((n + wpg - 1) / wpg)), dim3(tps::NT * wpg), 0, c->stream, a);
+int launch_waves(tps_ctx* c, void (*kernel)(A), int64_t n, int wpg, const A& a, size_t lds_bytes = 0) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((n + wpg - 1) / wpg)), dim3(tps::NT * wpg), lds_bytes, c->stream, a);
     HIP_TRY(hipGetLastError());
     return TPS_OK;
 }
@@ -1784,6 +1800,44 @@ int tps_batch_adapter_find(tps_ctx* c, int32_t slot, const uint64_t* patterns, c
     a.n_pat = n_pat;
     if ((rc = launch_waves(c, tps::adapter_find_kernel, n, tps::ADAPTER_WPG, a))) return rc;
     return download(c, {{hits, a.hits, out_bytes}});
+}
+
+int tps_batch_boundary_refine(tps_ctx* c, int32_t slot, uint64_t unit, int32_t m, const uint8_t* tails, const int32_t* begin, const int32_t* end,
+                              const int32_t* at_in, int64_t n_reads, int32_t hit, int32_t miss, int32_t sep, tps_refine* out, int64_t out_len) {
+    int rc, w;
+    Slot* sl;
+    tps::Why why;
+    if ((rc = need_batch(c, slot, &sl))) return rc;
+    const int64_t n = sl->n;
+    if ((rc = tps::boundary_refine_check(n, sl->h_offsets.data(), unit, m, tails, begin, end, at_in, n_reads, hit, miss, sep, out, out_len, &why)))
+        return fail(rc, "%s", why.msg);
+    if (n == 0) return TPS_OK;
+    // (the pattern table, the slot's tails, its scan outputs and its plan are not touched: a scan before and after the call gives the same results)
+    tps::Layout in;
+    const tps::RegionAt reg = tps::region_layout(in, n);
+    const size_t off_at = in.add((size_t)n * 4), out_bytes = (size_t)n * sizeof(tps_refine);
+    if ((rc = c->refine_in.ensure(in.total))) return rc;
+    if ((rc = c->refine_out.ensure(out_bytes))) return rc;
+    TPS_POISON(c->refine_out);
+    std::vector<uint32_t> table;
+    if ((rc = upload_hit_table(c, unit, m, table, &w))) return rc;
+    tps::RefineArgs a{};
+    set_batch(a, *sl);
+    if ((rc = upload_region(c, c->refine_in, reg, tails, begin, end, n, a))) return rc;
+    a.at = at<const int32_t>(c->refine_in, off_at);
+    HIP_TRY(hipMemcpyAsync((void*)a.at, at_in, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    a.table = (const uint32_t*)c->tract_table.p;
+    a.out = (tps_refine*)c->refine_out.p;
+    a.n_reads = n;
+    a.w = w; a.hit = hit; a.miss = miss; a.sep = sep;
+    a.bal_dw = tps::refine_ballot_dw(n, sl->h_offsets.data(), begin, end, w);
+    const size_t lds_bytes = (size_t)(tps::TRACT_TABLE_DW + tps::REFINE_WPG * tps::refine_lds_dw(a.bal_dw)) * 4;
+    if (lds_bytes > c->lds_set_refine) {
+        HIP_TRY(hipFuncSetAttribute((const void*)tps::boundary_refine_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+        c->lds_set_refine = lds_bytes;
+    }
+    if ((rc = launch_waves(c, tps::boundary_refine_kernel, n, tps::REFINE_WPG, a, lds_bytes))) return rc;
+    return download(c, {{out, a.out, out_bytes}});
 }
 
 int tps_batch_set_tails(tps_ctx* c, int32_t slot, const uint8_t* tails) {

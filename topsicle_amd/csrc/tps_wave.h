@@ -149,6 +149,17 @@ TPS_DEV uint64_t wave_ballot(const Lane<bool>& p) {
 #else
 TPS_DEV uint64_t wave_ballot(const Lane<bool>& p) { return __builtin_amdgcn_ballot_w64(p); }
 #endif
+// inside a phase: how many of the lanes 0 .. tid have their bit set in the ballot `b` (wave-uniform).  Device: the two v_mbcnt count
+// the bits below the lane; shifted down by one they cover bits 1 .. tid, and bit 0 goes in as the scalar start value.
+#ifdef TPS_EMU
+TPS_DEV int wave_ballot_upto(uint64_t b, int tid) { return __builtin_popcountll(tid >= NT - 1 ? b : b & ((2ull << tid) - 1ull)); }
+#else
+TPS_DEV int wave_ballot_upto(uint64_t b, int tid) {
+    (void)tid;
+    const uint64_t s = b >> 1;
+    return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(s >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)s, (uint32_t)(b & 1ull)));
+}
+#endif
 // inclusive prefix sum over the lanes (device: DPP row shifts / broadcasts, six VALU adds, no LDS round trips)
 #ifdef TPS_EMU
 TPS_DEV Lane<uint32_t> wave_incl_sum(const Lane<uint32_t>& x) {

@@ -23,7 +23,7 @@ FOLLOW_MAX_FWD, FOLLOW_WIDE_MAX_FWD, FOLLOW_HIST_MAX = 15, 32, 8      # k-mers t
 EXPORTS = [
     "tps_abi_version", "tps_device_count", "tps_ctx_create", "tps_ctx_destroy", "tps_last_error",
     "tps_set_patterns", "tps_set_patterns_wide", "tps_batch_upload", "tps_batch_upload_packed", "tps_batch_upload_nib4", "tps_batch_share", "tps_host_alloc", "tps_host_free",
-    "tps_batch_download_packed", "tps_batch_kmer_followers", "tps_batch_kmer_followers_wide", "tps_batch_motif_census", "tps_batch_variant_census", "tps_batch_tract_map", "tps_batch_end_sketch", "tps_sketch_links", "tps_batch_end_window", "tps_window_offsets", "tps_window_place", "tps_batch_adapter_find", "tps_batch_set_tails", "tps_batch_scan", "tps_sync",
+    "tps_batch_download_packed", "tps_batch_kmer_followers", "tps_batch_kmer_followers_wide", "tps_batch_motif_census", "tps_batch_variant_census", "tps_batch_tract_map", "tps_batch_end_sketch", "tps_sketch_links", "tps_batch_end_window", "tps_window_offsets", "tps_window_place", "tps_batch_adapter_find", "tps_batch_boundary_refine", "tps_batch_set_tails", "tps_batch_scan", "tps_sync",
     "tps_batch_results", "tps_batch_window_offsets", "tps_batch_window_sums", "tps_batch_window_raw",
     "tps_batch_raw_to_fd", "tps_batch_trc_counts", "tps_trc_counts", "tps_window_counts", "tps_binseg_l2", "tps_binseg_l2_ties", "tps_batch_read_sums", "tps_window_count",
     "tps_kernel_time_ms", "tps_kernel_time_reset", "tps_device_info", "tps_batch_kernel_info", "tps_ctx_debug_option", "tps_debug_stamps_get",
@@ -72,6 +72,10 @@ ANCHOR_MAX_SPAN, ANCHOR_MAX_ROWS = 4096, 262144
 PLACE_MAX_REFS, PLACE_MAX_OCC = 1024, 64
 # tps_batch_adapter_find: letters of a pattern, patterns of one call, letters of a region
 ADAPTER_LEN_RANGE, ADAPTER_MAX_PATTERNS, ADAPTER_MAX_REGION = (12, 64), 64, 1024
+REFINE_DTYPE = np.dtype([(f, "<i4") for f in ("pos", "score", "drop", "at_score", "hits_before", "hits_after", "runner", "runner_pos")])      # struct tps_refine
+assert REFINE_DTYPE.itemsize == 32
+# tps_batch_boundary_refine: hit and miss, sep, end - begin (after end is clamped to the read)
+REFINE_WEIGHT_RANGE, REFINE_SEP_RANGE, REFINE_MAX_REGION = (1, 16), (1, 65535), 65536
 RES_TIE = 1            # TPS_RES_TIE: the exact tournament decided the change-point (candidates within float64 noise of each other)
 
 
@@ -123,6 +127,7 @@ def load_library(path: str | None = None) -> C.CDLL:
         "tps_window_offsets": (C.c_int, [vp, vp, vp, vp, vp, i64, i32, i32, vp, vp, vp, i64]),
         "tps_window_place": (C.c_int, [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64]),
         "tps_batch_adapter_find": (C.c_int, [vp, i32, vp, vp, i32, vp, vp, vp, i64, vp, i64]),
+        "tps_batch_boundary_refine": (C.c_int, [vp, i32, C.c_uint64, i32, vp, vp, vp, vp, i64, i32, i32, i32, vp, i64]),
         "tps_batch_set_tails": (C.c_int, [vp, i32, vp]),
         "tps_batch_scan": (C.c_int, [vp, i32, C.POINTER(Params)]),
         "tps_sync": (C.c_int, [vp]),
@@ -612,6 +617,26 @@ class HipScanner:
         self._check(self.lib.tps_batch_adapter_find(self._h, slot, _ptr(codes), _ptr(lens), len(lens), _ptr(tails), _ptr(begin), _ptr(end), len(tails),
                                                     _ptr(hits), hits.size))
         return hits[:, :, 0].copy(), hits[:, :, 1].copy()
+
+    def boundary_refine(self, slot: int, unit: str, tails, begin, end, at, hit: int = 2, miss: int = 1, sep: int = 200):
+        """The boundary of the telomere tract at base resolution in the region [begin, end) of every read of the resident batch
+        (tails: 0 = the read, 1 = its reverse complement; at most 65 536 letters), and what supports it: one change point on the
+        per-position hits of the primitive unit `unit` (a string of ACGT, 4 .. 32 letters), a hit worth +hit, any other position
+        -miss (tps_batch_boundary_refine, the rule is in include/topsicle_hip.h; classes and files: topsicle_amd.refine):
+        REFINE_DTYPE[n] -- pos and its score, the drop from there to the region's end, the score at the boundary `at` the caller has
+        called, the hits on either side, and the best boundary at least `sep` positions away.  No pattern table needed; the slot's
+        scan outputs stay as they are."""
+        from . import variants
+        code, m = variants.unit_code(unit)
+        n = self._n[slot]
+        tails, begin, end = _region(tails, begin, end, "boundary_refine")
+        at = np.ascontiguousarray(at, dtype=np.int32)
+        if len(at) != len(tails):
+            raise TopsicleHipError("boundary_refine: at must have one entry per read")
+        out = np.zeros(n, dtype=REFINE_DTYPE)
+        self._check(self.lib.tps_batch_boundary_refine(self._h, slot, code, m, _ptr(tails), _ptr(begin), _ptr(end), _ptr(at), len(tails), hit, miss, sep,
+                                                       _ptr(out), out.size))
+        return out
 
     def set_tails(self, slot: int, tails: np.ndarray):
         tails = np.ascontiguousarray(tails, dtype=np.uint8)

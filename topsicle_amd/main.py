@@ -20,7 +20,7 @@ from collections import defaultdict
 
 import numpy as np
 
-from . import adapters, allsteps, anchor, batch, endref, ends, hiplib, motif, rawnpz, seqio, tracts, variants
+from . import adapters, allsteps, anchor, batch, endref, ends, hiplib, motif, rawnpz, refine, seqio, tracts, variants
 
 version_number = "1.0.0"
 Topsicle_output_prefix = "Topsicle"
@@ -163,9 +163,12 @@ def process_file_multi(args, seq_loc, phrases, engines):
     # --adapters: the same per k; the search runs on the batch workers, the naming rule once per run (analysis_run)
     acols = getattr(args, "adapter_collectors", None) or [None] * len(phrases)
     arows = [[] for _ in phrases]
+    # --refine: the same per k; the kernel runs on the batch workers, the class rule once per run (analysis_run)
+    rcols = getattr(args, "refine_collectors", None) or [None] * len(phrases)
+    rrows = [[] for _ in phrases]
     jobs = [batch.Job(pattern, _scan_params(args, slide), want_sums, want_raw, raw_sink=sink, variants=None if col is None else col.spec,
-                      ends=None if ecol is None else ecol.spec, adapters=None if acol is None else acol.spec)
-        for (_k, pattern, slide), sink, col, ecol, acol in zip(phrases, raw_npz, vcols, ecols, acols)]
+                      ends=None if ecol is None else ecol.spec, adapters=None if acol is None else acol.spec, refine=None if rcol is None else rcol.spec)
+        for (_k, pattern, slide), sink, col, ecol, acol, rcol in zip(phrases, raw_npz, vcols, ecols, acols, rcols)]
     # --tracts: one collector for the whole run; the map runs once per batch, with the first k's job
     tcol = getattr(args, "tract_collector", None)
     if tcol is not None:
@@ -259,6 +262,7 @@ def process_file_multi(args, seq_loc, phrases, engines):
                 eout = ecols[n].take(pb) if ecols[n] is not None else None
                 ewin = ecols[n].take_windows(pb) if ecols[n] is not None else None          # (--anchor: the windows themselves)
                 aout = acols[n].take(pb) if acols[n] is not None else None
+                rout = rcols[n].take(pb) if rcols[n] is not None else None
                 if wthread is not None and len(idx) and n == writer_k:
                     write_passing(pb, idx)                                   # every passing record (main.py:83-86)
                 ids = [pb.read_id(int(i)) for i in idx]
@@ -294,6 +298,8 @@ def process_file_multi(args, seq_loc, phrases, engines):
                     a_dist, a_end = aout
                     arows[n] += [(file_name, ids[j], int(r["tail"][j]), telo_l[j], a_dist[idx[j]].copy(), a_end[idx[j]].copy())
                                  for j in np.nonzero(telolen != 0)[0]]
+                if rout is not None:                                         # one row per read with a stored boundary
+                    rrows[n] += [(file_name, ids[j], int(r["tail"][j]), telo_l[j], rout[idx[j]].copy()) for j in np.nonzero(telolen != 0)[0]]
                 if n == 0:
                     with _CSV_LOCK, open(csv_path, mode="a", newline="") as fh:
                         csv.writer(fh).writerows(zip([file_name] * len(ids), [telo_phrase] * len(ids), ["%.3f" % t for t in trc_l], ids, telo_l))
@@ -347,6 +353,9 @@ def process_file_multi(args, seq_loc, phrases, engines):
     for col, ar in zip(acols, arows):
         if col is not None:
             col.add_file_rows(seq_loc, ar)
+    for col, rr in zip(rcols, rrows):
+        if col is not None:
+            col.add_file_rows(seq_loc, rr)
     st = pool.stats
     if st.get("shards", 0) > 1:
         tprint(f"{base_name}: read as {st['shards']} byte ranges, one reader team each")
@@ -409,6 +418,14 @@ def analysis_run(args, engines=None, engine_factory=None, wait_plots=True):
         why = adapters.check(adapter_pats, args.adaptersearch, args.adaptererr, args.adaptermargin, args.maxlengthtelo)
         if why is not None:
             tprint(f"--adapters needs {why}")
+            sys.exit(2)
+    if getattr(args, "refine", False):
+        # (before any input file is read or written; the root of a motif that --pattern auto has yet to find is checked below)
+        root = "ACGT" if args.pattern.strip().lower() == "auto" else variants.primitive_root(args.pattern.upper())
+        why = refine.check(root, args.refinehit, args.refinemiss, args.refinesep, args.refineminscore, args.refinemindrop, args.refineminmargin,
+                           args.trimfirst, args.maxlengthtelo)
+        if why is not None:
+            tprint(f"--refine needs {why}")
             sys.exit(2)
     if args.pattern.strip().lower() == "auto":
         # the motif comes from the reads (motif.py); from here on the run is the one `--pattern <that motif>` would have been
@@ -506,6 +523,19 @@ def analysis_run(args, engines=None, engine_factory=None, wait_plots=True):
     if adapter_pats is not None:
         args.adapter_collectors = [adapters.Collector(adapter_pats, args.adaptersearch, args.adaptererr, args.adaptermargin) for _ in phrases]
 
+    args.refine_collectors = None
+    if getattr(args, "refine", False):
+        unit = variants.primitive_root(args.pattern.upper())
+        why = refine.check(unit, args.refinehit, args.refinemiss, args.refinesep, args.refineminscore, args.refinemindrop, args.refineminmargin,
+                           args.trimfirst, args.maxlengthtelo)
+        if why is not None:
+            tprint(f"--refine needs {why}")
+            sys.exit(2)
+        if unit != args.pattern.upper():
+            tprint(f"--refine: {args.pattern} is a power of {unit}; the hits are words of {unit}")
+        args.refine_collectors = [refine.Collector(unit, args.refinehit, args.refinemiss, args.refinesep, args.refineminscore, args.refinemindrop,
+                                                   args.refineminmargin, args.trimfirst) for _ in phrases]
+
     args.tract_collector = None
     if getattr(args, "tracts", False):
         unit = variants.primitive_root(args.pattern.upper())
@@ -595,6 +625,14 @@ def analysis_run(args, engines=None, engine_factory=None, wait_plots=True):
         adapters.write_csv(f"{args.outputDir}/adapter_summary_{telo_phrase}.csv", adapters.SUMMARY_HEADER, a_summary)
         tprint(f"adapters (k = {telo_phrase}): {args.outputDir}/adapters_{telo_phrase}.csv, {args.outputDir}/adapter_summary_{telo_phrase}.csv")
         for line in adapters.summary(col, a_stats):
+            tprint(line)
+
+    for (telo_phrase, _pattern, _slide), col in zip(phrases, args.refine_collectors or []):
+        r_reads, r_summary, r_stats = col.finish(filenames)
+        refine.write_csv(f"{args.outputDir}/refined_{telo_phrase}.csv", refine.READ_HEADER, r_reads)
+        refine.write_csv(f"{args.outputDir}/refine_summary_{telo_phrase}.csv", refine.SUMMARY_HEADER, r_summary)
+        tprint(f"refined boundaries (k = {telo_phrase}): {args.outputDir}/refined_{telo_phrase}.csv, {args.outputDir}/refine_summary_{telo_phrase}.csv")
+        for line in refine.summary(col, r_stats):
             tprint(line)
 
     if args.tract_collector is not None:
@@ -779,6 +817,17 @@ def build_parser():
                              "literal sequences (adapter1 ...), 12..64 letters of ACGT each, 64 at most, given as they stand in front of the --pattern repeats; one row "
                              "per read (adapters_{k}.csv: adapter, edit distance, where it ends, the length measured from there) and one per sequence "
                              "(adapter_summary_{k}.csv)")
+    parser.add_argument("--refine", action="store_true",
+                        help="MI355X build: the boundary of every read with a called one again at base resolution, with what supports it -- one change point on "
+                             "the per-position hits of the --pattern repeat over [trimfirst, maxlengthtelo); one row per read (refined_{k}.csv: refined length, "
+                             "shift against telo_length, score, drop, margin, the called boundary's deficit, hit densities, class) and one per class "
+                             "(refine_summary_{k}.csv); no other output changes")
+    parser.add_argument("--refinehit", metavar="INT", type=int, default=refine.DEFAULT_HIT, help="--refine: what a position whose word is within one substitution of the repeat adds (1..16)")
+    parser.add_argument("--refinemiss", metavar="INT", type=int, default=refine.DEFAULT_MISS, help="--refine: what any other position costs (1..16)")
+    parser.add_argument("--refinesep", metavar="INT", type=int, default=refine.DEFAULT_SEP, help="--refine: positions the runner-up boundary must be away from the best (1..65535)")
+    parser.add_argument("--refineminscore", metavar="INT", type=int, default=refine.DEFAULT_MIN_SCORE, help="--refine: a read whose best score is below this is classed no_telomere")
+    parser.add_argument("--refinemindrop", metavar="INT", type=int, default=refine.DEFAULT_MIN_DROP, help="--refine: a read whose score falls by less than this up to the end of the region is classed open")
+    parser.add_argument("--refineminmargin", metavar="INT", type=int, default=refine.DEFAULT_MIN_MARGIN, help="--refine: a read whose runner-up boundary scores within this of the best is classed ambiguous")
     parser.add_argument("--adaptersearch", metavar="INT", type=int, default=adapters.DEFAULT_SEARCH, help="--adapters: bases at the telomere end that are searched (16..1024; never beyond maxlengthtelo)")
     parser.add_argument("--adaptererr", metavar="FLOAT", type=float, default=adapters.DEFAULT_ERR, help="--adapters: edits allowed per letter of a sequence (a sequence of m letters: floor(err m) edits)")
     parser.add_argument("--adaptermargin", metavar="INT", type=int, default=adapters.DEFAULT_MARGIN, help="--adapters: edits by which the best sequence must beat every other to name the read")
