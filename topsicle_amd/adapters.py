@@ -17,11 +17,13 @@ telomere is at its start.  The same list is searched on reads whose telomere is 
 """
 from __future__ import annotations
 
-import csv
 import math
 import os
 
 import numpy as np
+
+from . import analyses
+from .analyses import median_cell, write_csv  # noqa: F401  (write_csv stays importable from here)
 
 LETTERS = "ACTG"                  # the packed batch's 2-bit codes
 MIN_LEN, MAX_LEN, MAX_PATTERNS, MAX_REGION = 12, 64, 64, 1024
@@ -29,13 +31,24 @@ SEARCH_RANGE = (16, MAX_REGION)
 DEFAULT_SEARCH, DEFAULT_ERR, DEFAULT_MARGIN = 256, 0.2, 2
 
 
-class AdapterSpec:
+class AdapterSpec(analyses.BoundaryAnalysis):
     """What batch.Job(adapters=...) carries: the sequences, the letters of the region [0, search) and `sink(recs, res, dist, end)`,
-    called by the worker that scanned a batch while that batch is still resident."""
+    called by the worker that scanned a batch while that batch is still resident.  search <= maxlen: the region lies inside the
+    span packed for the second pass of the two-pass route."""
 
     def __init__(self, seqs, search: int = DEFAULT_SEARCH, sink=None):
         self.seqs, self.search, self.sink = [s.upper() for s in seqs], int(search), sink
         self.lens = np.array([len(s) for s in self.seqs], np.int32)
+
+    def regions(self, res, prm):
+        return search_regions(res, *self.scan_geometry(prm), self.search)
+
+    def empty(self, n):
+        """(m_j, 0): the answer of an empty region"""
+        return np.tile(self.lens.astype(np.uint16), (n, 1)), np.zeros((n, len(self.lens)), np.uint16)
+
+    def launch(self, eng, slot, tails, begin, end):
+        return eng.adapter_find(slot, self.seqs, tails, begin, end)
 
 
 def pattern_codes(patterns):
@@ -124,40 +137,21 @@ def search_regions(res, trimfirst: int, slide: int, maxlen: int, search: int):
     return np.zeros(len(res), np.int32), np.where(e > 0, search, 0).astype(np.int32)
 
 
-class Collector:
-    """The sink of one k of a run, like variants.Collector: the workers hand it every batch's hits (in whatever order they finish),
-    the run's consumer, which sees the batches in file order, asks for them with take(recs)."""
+class Collector(analyses.Collector):
+    """The sink of one k of a run: (dist, end) per batch.  A row: (file, readID, tail, telo_length, dist row, end row)."""
 
     def __init__(self, pats, search: int = DEFAULT_SEARCH, err: float = DEFAULT_ERR, margin: int = DEFAULT_MARGIN):
-        import threading
+        super().__init__()
         self.names = [name for name, _ in pats]
         self.spec = AdapterSpec([seq for _, seq in pats], search, self)
         self.err, self.margin = float(err), int(margin)
-        self._pending = {}
-        self._file_rows = {}
-        self._lock = threading.Lock()
 
-    def __call__(self, recs, res, dist, end):
-        with self._lock:
-            self._pending[id(recs)] = (dist, end)
-
-    def take(self, recs):
-        """(dist, end) of a batch the consumer has in hand."""
-        with self._lock:
-            return self._pending.pop(id(recs))
-
-    def add_file_rows(self, path, rows):
-        """The rows of one input file, in read order: (file, readID, tail, telo_length, dist row, end row) each."""
-        with self._lock:
-            self._file_rows.setdefault(path, []).extend(rows)
-
-    def rows_in_order(self, paths):
-        for p in paths:
-            yield from self._file_rows.get(p, [])
+    def keep_row(self, out, i, file, rid, tail, telo, length):
+        return file, rid, tail, telo, out[0][i].copy(), out[1][i].copy()
 
     def finish(self, paths):
         """(read rows, summary rows, stats) of the run: the naming rule on every read's hits."""
-        rows = list(self.rows_in_order(paths))
+        rows = self.rows_in_order(paths)
         lens = self.spec.lens
         P = len(lens)
         dist = np.array([r[4] for r in rows], np.int64).reshape(len(rows), P)
@@ -175,30 +169,15 @@ class Collector:
         for j in range(P + 1):
             got, is_pat = per[j], j < P
             summary_rows.append([self.names[j] if is_pat else "none", int(lens[j]) if is_pat else "", len(got), sum(1 for g in got if g[0] == 0),
-                                 sum(1 for g in got if g[0] != 0), _median([g[1] for g in got]) if is_pat else "", _median([g[2] for g in got]) if is_pat else "",
-                                 _median([g[3] for g in got]), _median([g[4] for g in got if g[4] != ""]) if is_pat else ""])
+                                 sum(1 for g in got if g[0] != 0), median_cell([g[1] for g in got]) if is_pat else "", median_cell([g[2] for g in got]) if is_pat else "",
+                                 median_cell([g[3] for g in got]), median_cell([g[4] for g in got if g[4] != ""]) if is_pat else ""])
         stats = {"reads": len(rows), "named": int(named.sum()), "per_pattern": [len(per[j]) for j in range(P)],
-                 "end_median": _median([int(end[i, best[i]]) for i in np.nonzero(named)[0]])}
+                 "end_median": median_cell([int(end[i, best[i]]) for i in np.nonzero(named)[0]])}
         return read_rows, summary_rows, stats
-
-
-def _median(xs):
-    """The median as a CSV cell: empty without values, a whole number where it is one."""
-    if not len(xs):
-        return ""
-    m = float(np.median(np.asarray(xs, np.float64)))
-    return int(m) if m == int(m) else m
 
 
 READ_HEADER = ["file", "readID", "tail", "telo_length", "adapter", "dist", "adapter_end", "runner", "runner_dist", "length_from_adapter"]
 SUMMARY_HEADER = ["name", "length", "reads", "tail0", "tail1", "dist_median", "adapter_end_median", "telo_median", "from_adapter_median"]
-
-
-def write_csv(path, header, rows):
-    with open(path, "w", newline="") as f:
-        w = csv.writer(f)
-        w.writerow(header)
-        w.writerows(rows)
 
 
 def summary(col: Collector, stats) -> list[str]:
@@ -209,3 +188,24 @@ def summary(col: Collector, stats) -> list[str]:
             f"{stats['reads']} reads (err {col.err:g}, margin {col.margin})",
             f"  named: {stats['named']} reads ({counts}); not named: {stats['reads'] - stats['named']}",
             f"  median adapter end of the named reads: {stats['end_median'] if stats['end_median'] != '' else 'n/a'}"]
+
+
+# ---- the CLI's side (main.ANALYSES)
+FLAG = "adapters"
+POWER_NOTE = None                 # (the sequences are searched as given: the motif's root plays no part)
+
+
+def cli_check(args, root: str):
+    """(the sequences come from the command line or from their own small file)"""
+    return check(load_patterns(args.adapters), args.adaptersearch, args.adaptererr, args.adaptermargin, args.maxlengthtelo)
+
+
+def cli_collector(args, unit: str, slide: int):
+    return Collector(load_patterns(args.adapters), args.adaptersearch, args.adaptererr, args.adaptermargin)
+
+
+def finish_and_write(args, k, col, filenames, engines):
+    """The naming rule once per run and k; writes the two files, yields the log lines."""
+    read_rows, summary_rows, stats = col.finish(filenames)
+    yield analyses.write_tables(args.outputDir, k, "adapters", [("adapters", READ_HEADER, read_rows), ("adapter_summary", SUMMARY_HEADER, summary_rows)])
+    yield from summary(col, stats)

@@ -33,6 +33,13 @@ def check(with_ends: bool, span: int, min_votes: int = DEFAULT_MIN_VOTES, ratio:
     return None
 
 
+FLAG = "anchor"                   # (main.EARLY_CHECKS; the rest of its CLI side is inside ends.finish_and_write)
+
+
+def cli_check(args, root: str):
+    return check(getattr(args, "ends", False), args.endspan, args.anchorminvotes, args.anchorratio)
+
+
 def references(end, links):
     """ref int32[n]: for a read of group end[i] > 0 the member of its group with the most links, the first of them in run order; -1
     for a read without a group."""

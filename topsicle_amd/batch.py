@@ -45,26 +45,20 @@ class Job:
     def __init__(self, patterns, prm: hiplib.Params, want_sums=False, want_raw=False, raw_sink=None, variants=None, tracts=None, ends=None, adapters=None, refine=None):
         """raw_sink (with want_raw; rawnpz.RawNpzWriter): the raw rows of the reads the sink selects are written to its file by
         the worker that scanned the batch, device -> file, and the caller gets a `RawKept` in place of the rows.
-        variants (variants.VariantSpec: unit, bin, n_bins, sink): the worker that scanned the batch runs the variant census of the
-        called tracts on it while it is still resident and hands (recs, results, counts, profile) to the spec's sink.
+        variants, ends, adapters, refine (variants.VariantSpec, ends.EndSpec, adapters.AdapterSpec, refine.RefineSpec: each an
+        analyses.BoundaryAnalysis): the worker that scanned the batch runs the analysis on the regions behind the boundaries it has
+        just called, while the batch is still resident, and hands (recs, results, *outputs) to the spec's sink (run_analysis).
         tracts (tracts.TractSpec: unit, the rule's parameters, sink): the same worker maps the telomere-repeat tracts of EVERY read of
         the batch, passing or not, and hands (recs, tracts, found, totals) to the spec's sink.  The map needs whole reads: a batch
-        in heads mode is refused.  One job of a batch carries it (the map does not depend on the pattern table).
-        ends (ends.EndSpec: unit, k, buckets, span, sink): the worker that scanned the batch sketches the subtelomere window behind every
-        called boundary while the batch is still resident and hands (recs, results, sketch, kept) to the spec's sink -- and, for a
-        spec with `anchor` set, the windows' packed letters and keep bits behind them (recs, results, sketch, kept, codes, keep).
-        adapters (adapters.AdapterSpec: sequences, search, sink): the same worker searches the sequences in the first `search` bases of
-        every read with a called boundary while the batch is still resident and hands (recs, results, dist, end) to the spec's sink.
-        refine (refine.RefineSpec: unit, hit, miss, sep, sink): the same worker refines the boundary of every read with a called one,
-        position by position over [trimfirst, maxlen), while the batch is still resident and hands (recs, results, rows) to the spec's
-        sink."""
+        in heads mode is refused.  One job of a batch carries it (the map does not depend on the pattern table)."""
         self.patterns, self.prm, self.want_sums, self.want_raw = list(patterns), prm, bool(want_sums), bool(want_raw)
         self.raw_sink = raw_sink if want_raw else None
-        self.variants = variants
-        self.tracts = tracts
-        self.ends = ends
-        self.adapters = adapters
-        self.refine = refine
+        self.variants, self.ends, self.adapters, self.refine, self.tracts = variants, ends, adapters, refine, tracts
+
+    @property
+    def analyses(self):
+        """The boundary analyses the job carries, in the order they are launched behind its scan."""
+        return [spec for spec in (self.variants, self.ends, self.adapters, self.refine) if spec is not None]
 
 
 class CensusJob:
@@ -123,98 +117,34 @@ def _sink_rows(job, seq, eng, slot, recs, res, slot_index=None):
     return RawKept(keep)
 
 
-def _census_variants(job, eng, slot, recs, res, slot_index=None):
-    """The variant census of the tracts the scan has just called (Job.variants), on the engine and slot that were scanned: the tract
-    of a read is [trimfirst, boundary) of its telomere-first string, boundary = bkp * slide + trimfirst where the CLI would store it
-    (variants.tract_bounds); every other read gets begin = end = 0.  `slot_index`: the batch indices of the reads resident in
-    `slot` when that is not the whole batch (second pass of the two-pass route: the passing reads only -- their packed span is the
-    first / last min(L, maxlen) bases, so the coordinates are those of the whole read), None with nothing resident: no read passed."""
-    from . import variants
-    spec = job.variants
-    m = len(spec.unit)
-    begin, end = variants.tract_bounds(res, int(job.prm.trimfirst), int(job.prm.slide), int(job.prm.maxlen))
+def run_analysis(spec, prm, eng, slot, recs, res, slot_index=None):
+    """One boundary analysis (analyses.BoundaryAnalysis) of the batch the scan has just called, on the engine and slot that were
+    scanned.  The regions are in the coordinates of the telomere-first string and cover every read of the batch: begin = end = 0 --
+    and tail 0 -- for a read whose boundary the CLI would not store, which gets the answer of an empty region.  Three routes:
+      slot_index None, an engine   the whole batch is resident in `slot` (one pass): every read is submitted;
+      slot_index given             the batch indices of the reads resident in `slot` (second pass of the two-pass route: the passing
+                                   reads only -- their packed span is the first / last min(L, maxlen) bases, so the coordinates are
+                                   those of the whole read): those are submitted, their rows scattered over the empty answer;
+      slot_index None, eng None    nothing is resident (no read passed, or no window step): no launch, the empty answer.
+    Outputs that are one answer per call (spec.per_batch) are passed on as they come.  The sink gets (recs, res, *outputs)."""
+    begin, end, *extra = spec.regions(res, prm)
     tails = np.where(end > begin, res["tail"], 0).astype(np.uint8)
-    counts = np.zeros((len(res), 2 + 4 * m), np.uint32)
-    profile = np.zeros((spec.n_bins, 2 + 4 * m), np.int64)
+    out = list(spec.empty(len(res)))
     if slot_index is None:
         if eng is not None:
-            counts, profile = eng.variant_census(slot, spec.unit, tails, begin, end, spec.bin, spec.n_bins)
+            out = spec.launch(eng, slot, tails, begin, end, *extra)
     elif len(slot_index):
-        counts[slot_index], profile = eng.variant_census(slot, spec.unit, tails[slot_index], begin[slot_index], end[slot_index], spec.bin, spec.n_bins)
-    spec.sink(recs, res, counts, profile)
-
-
-def _sketch_ends(job, eng, slot, recs, res, slot_index=None):
-    """The end sketch of the windows behind the boundaries the scan has just called (Job.ends), on the engine and slot that were
-    scanned: [boundary, min(boundary + span, maxlen)) of the telomere-first string where the CLI would store the boundary
-    (ends.windows), begin = end = 0 -- an empty sketch -- for every other read.  `slot_index` as in _census_variants.  A spec with
-    `anchor` set also gets the same windows position by position (end_window: packed letters and keep bits), right behind the sketch."""
-    from . import ends
-    spec = job.ends
-    anchor = getattr(spec, "anchor", False)
-    begin, end = ends.windows(res, int(job.prm.trimfirst), int(job.prm.slide), int(job.prm.maxlen), spec.span)
-    tails = np.where(end > begin, res["tail"], 0).astype(np.uint8)
-    sketch = np.full((len(res), spec.buckets), ends.EMPTY, np.uint32)
-    kept = np.zeros(len(res), np.uint32)
-    if anchor:
-        codes = np.zeros((len(res), (spec.span + 15) // 16), np.uint32)
-        keep = np.zeros((len(res), (spec.span + 31) // 32), np.uint32)
-    if slot_index is None:
-        if eng is not None:
-            sketch, kept = eng.end_sketch(slot, spec.unit, tails, begin, end, spec.k, spec.buckets)
-            if anchor:
-                codes, keep = eng.end_window(slot, spec.unit, tails, begin, end, spec.k, spec.span)
-    elif len(slot_index):
-        sketch[slot_index], kept[slot_index] = eng.end_sketch(slot, spec.unit, tails[slot_index], begin[slot_index], end[slot_index], spec.k, spec.buckets)
-        if anchor:
-            codes[slot_index], keep[slot_index] = eng.end_window(slot, spec.unit, tails[slot_index], begin[slot_index], end[slot_index], spec.k, spec.span)
-    if anchor:
-        spec.sink(recs, res, sketch, kept, codes, keep)
-    else:
-        spec.sink(recs, res, sketch, kept)
-
-
-def _find_adapters(job, eng, slot, recs, res, slot_index=None):
-    """The adapter search at the telomere end of the reads the scan has just called (Job.adapters), on the engine and slot that were
-    scanned: the region [0, search) of the telomere-first string of every read whose boundary the CLI would store
-    (adapters.search_regions), begin = end = 0 -- the answer of an empty region, (m_j, 0) -- for every other read.  `slot_index` as in
-    _census_variants (search <= maxlen: the region lies inside the span packed for the second pass)."""
-    from . import adapters
-    spec = job.adapters
-    begin, end = adapters.search_regions(res, int(job.prm.trimfirst), int(job.prm.slide), int(job.prm.maxlen), spec.search)
-    tails = np.where(end > begin, res["tail"], 0).astype(np.uint8)
-    dist = np.tile(spec.lens.astype(np.uint16), (len(res), 1))
-    aend = np.zeros((len(res), len(spec.lens)), np.uint16)
-    if slot_index is None:
-        if eng is not None:
-            dist, aend = eng.adapter_find(slot, spec.seqs, tails, begin, end)
-    elif len(slot_index):
-        dist[slot_index], aend[slot_index] = eng.adapter_find(slot, spec.seqs, tails[slot_index], begin[slot_index], end[slot_index])
-    spec.sink(recs, res, dist, aend)
-
-
-def _refine_boundaries(job, eng, slot, recs, res, slot_index=None):
-    """The boundary at base resolution of the reads the scan has just called (Job.refine), on the engine and slot that were scanned:
-    the region [trimfirst, maxlen) of the telomere-first string of every read whose boundary the CLI would store, with that boundary
-    as `at` (refine.regions), begin = end = at = 0 -- the row of an empty region -- for every other read.  `slot_index` as in
-    _census_variants (the region ends at maxlen: it lies inside the span packed for the second pass)."""
-    from . import refine
-    spec = job.refine
-    begin, end, at = refine.regions(res, int(job.prm.trimfirst), int(job.prm.slide), int(job.prm.maxlen), spec.w)
-    tails = np.where(end > begin, res["tail"], 0).astype(np.uint8)
-    rows = np.zeros(len(res), hiplib.REFINE_DTYPE)
-    rows["runner_pos"] = -1
-    kw = dict(hit=spec.hit, miss=spec.miss, sep=spec.sep)
-    if slot_index is None:
-        if eng is not None:
-            rows = eng.boundary_refine(slot, spec.unit, tails, begin, end, at, **kw)
-    elif len(slot_index):
-        rows[slot_index] = eng.boundary_refine(slot, spec.unit, tails[slot_index], begin[slot_index], end[slot_index], at[slot_index], **kw)
-    spec.sink(recs, res, rows)
+        got = spec.launch(eng, slot, *(a[slot_index] for a in (tails, begin, end, *extra)))
+        per_read = len(out) - spec.per_batch
+        for rows, mine in zip(out[:per_read], got):
+            rows[slot_index] = mine
+        out[per_read:] = got[per_read:]
+    spec.sink(recs, res, *out)
 
 
 def _map_tracts(job, eng, slot, recs):
-    """The tract map of the resident batch (Job.tracts), on the engine and slot that were scanned: every read, whole."""
+    """The tract map of the resident batch (Job.tracts), on the engine and slot that were scanned: every read, whole -- no regions
+    and no route but the one-pass one, so it is no BoundaryAnalysis."""
     spec = job.tracts
     spec.sink(recs, *eng.tract_map(slot, spec.unit, **spec.kw()))
 
@@ -246,6 +176,33 @@ AUTO_MIN_FILE_BYTES = 1 << 30    # auto mode only probes files of at least this 
                                  # file, and what two passes save on a small file is less than that
 
 
+def _contexts(engine, jobs):
+    """(concurrent, the context of every job): job j > 0 on the engine's j-th helper context, or -- an engine without helpers,
+    SEQUENTIAL_TABLES -- every job on the one context."""
+    concurrent = len(jobs) > 1 and hasattr(engine, "helper") and not SEQUENTIAL_TABLES
+    return concurrent, [engine] + ([engine.helper(j) for j in range(len(jobs) - 1)] if concurrent else [engine] * (len(jobs) - 1))
+
+
+def _scans(engine, engines, concurrent, jobs, prms, slot):
+    """Scan the batch resident in `slot` of `engine` once per job and yield (context, job, parameters) when that job's scan has
+    completed.  Concurrent: the helper contexts borrow the batch, every job is launched, then the jobs are waited for one by one.
+    Sequential: a job's table is set and its scan launched when the caller comes back for it, after it has dealt with the one before."""
+    if concurrent:
+        for eng, job, p in zip(engines, jobs, prms):
+            if eng is not engine:
+                eng.share(slot, engine, slot)
+            if getattr(eng, "patterns", None) != job.patterns:
+                hiplib.set_table(eng, job.patterns)
+            eng.scan(slot, p)
+    for eng, job, p in zip(engines, jobs, prms):
+        if not concurrent:
+            if len(jobs) > 1 or getattr(eng, "patterns", None) != job.patterns:
+                hiplib.set_table(eng, job.patterns)
+            eng.scan(slot, p)
+        eng.sync()
+        yield eng, job, p
+
+
 def scan_jobs_heads(engine, recs, jobs, slot: int = 0, seq=None):
     """Two passes over a batch that came in HEADS mode (seqio.PackedBatch.full_len: only the first + last no_bp bases of every read
     were packed and uploaded -- all that step 1, allsteps.py:174-198, looks at):
@@ -256,9 +213,7 @@ def scan_jobs_heads(engine, recs, jobs, slot: int = 0, seq=None):
     The rows that come back are those of the one-pass scan (tests/test_two_pass.py: equal field by field); sums / raw rows are
     laid out over ALL reads of the batch with no windows for the reads that do not pass.  PCIe bytes per input base, 30 kb reads of
     which 1 % pass: 0.375 -> 0.028.  Same return value as scan_jobs."""
-    import numpy as np
-    concurrent = len(jobs) > 1 and hasattr(engine, "helper") and not SEQUENTIAL_TABLES
-    engines = [engine] + ([engine.helper(j) for j in range(len(jobs) - 1)] if concurrent else [engine] * (len(jobs) - 1))
+    concurrent, engines = _contexts(engine, jobs)
     slot_b = slot + 1
     full = np.asarray(recs.full_len, np.int64)
     out = []
@@ -270,24 +225,10 @@ def scan_jobs_heads(engine, recs, jobs, slot: int = 0, seq=None):
             p.flags = hiplib.F_STEP1
             p.min_len = 0                              # (the pseudo-reads are short: the length filter is applied to full_len below)
             prm_a.append(p)
-        res_a = []
-        if concurrent:
-            for eng, job, p in zip(engines, jobs, prm_a):
-                if eng is not engine:
-                    eng.share(slot, engine, slot)
-                if getattr(eng, "patterns", None) != job.patterns:
-                    hiplib.set_table(eng, job.patterns)
-                eng.scan(slot, p)
-        for n, (eng, job, p) in enumerate(zip(engines, jobs, prm_a)):
-            if not concurrent:
-                if len(jobs) > 1 or getattr(eng, "patterns", None) != job.patterns:
-                    hiplib.set_table(eng, job.patterns)
-                eng.scan(slot, p)
-            eng.sync()
-            res_a.append(eng.results(slot))
+        res_a = [eng.results(slot) for eng, _job, _p in _scans(engine, engines, concurrent, jobs, prm_a, slot)]
         recs.release()                                 # the heads are on the device: the staging buffers go back to the reader
         uploaded, holds = {}, {}                       # (passing reads, tails, maxlen) -> the engine that uploaded them; engine -> what its slot_b holds
-        for n, (eng, job, ra) in enumerate(zip(engines, jobs, res_a)):
+        for eng, job, ra in zip(engines, jobs, res_a):
             res = ra.copy()
             passing = (ra["pass"] != 0) & (full > job.prm.min_len)
             res["pass"] = passing
@@ -326,14 +267,8 @@ def scan_jobs_heads(engine, recs, jobs, slot: int = 0, seq=None):
                     hiplib.resolve_ties(eng, slot_b, rb, len(job.patterns), p.jump, p.min_size)
                 for f in ("n_win", "bkp", "gain", "flags"):
                     res[f][idx] = rb[f]
-                if getattr(job, "variants", None) is not None:
-                    _census_variants(job, eng, slot_b, recs, res, slot_index=idx)
-                if getattr(job, "ends", None) is not None:
-                    _sketch_ends(job, eng, slot_b, recs, res, slot_index=idx)
-                if getattr(job, "adapters", None) is not None:
-                    _find_adapters(job, eng, slot_b, recs, res, slot_index=idx)
-                if getattr(job, "refine", None) is not None:
-                    _refine_boundaries(job, eng, slot_b, recs, res, slot_index=idx)
+                for spec in job.analyses:
+                    run_analysis(spec, job.prm, eng, slot_b, recs, res, slot_index=idx)
                 np.cumsum(np.where(passing, res["n_win"], 0), out=win_off[1:])
                 if job.want_sums:
                     sums, wo_b = eng.window_sums(slot_b)
@@ -344,14 +279,8 @@ def scan_jobs_heads(engine, recs, jobs, slot: int = 0, seq=None):
                     raw, wo_b = eng.window_raw(slot_b)
                     assert int(wo_b[-1]) == int(win_off[-1])
             else:
-                if getattr(job, "variants", None) is not None:
-                    _census_variants(job, None, slot_b, recs, res)             # (no read passed: an all-zero answer)
-                if getattr(job, "ends", None) is not None:
-                    _sketch_ends(job, None, slot_b, recs, res)
-                if getattr(job, "adapters", None) is not None:
-                    _find_adapters(job, None, slot_b, recs, res)
-                if getattr(job, "refine", None) is not None:
-                    _refine_boundaries(job, None, slot_b, recs, res)
+                for spec in job.analyses:
+                    run_analysis(spec, job.prm, None, slot_b, recs, res)       # (nothing resident: the answer of empty regions)
                 if job.want_sums:
                     sums = np.zeros(0, np.int32)
                 if job.want_raw and job.raw_sink is not None and seq is not None:
@@ -390,14 +319,13 @@ def scan_jobs(engine, recs, jobs, slot: int = 0, seq=None):
     of the k passes overlap on the GPU (measured: 603 vs 785 us per 10 000 x 25 kb batch for k = 4, 5, 6).
     batch.SEQUENTIAL_TABLES scans them back to back on the one context instead (the A/B switch)."""
     if getattr(recs, "full_len", None) is not None:
-        if any(getattr(j, "tracts", None) is not None for j in jobs):
+        if any(isinstance(j, Job) and j.tracts is not None for j in jobs):
             raise ValueError("Job.tracts needs whole reads: read the file with two_pass=\"off\"")
         return scan_jobs_heads(engine, recs, jobs, slot, seq)
     if jobs and all(isinstance(j, CensusJob) for j in jobs):
         return census_jobs(engine, recs, jobs, slot)
     out = []
-    concurrent = len(jobs) > 1 and hasattr(engine, "helper") and not SEQUENTIAL_TABLES
-    engines = [engine] + ([engine.helper(j) for j in range(len(jobs) - 1)] if concurrent else [engine] * (len(jobs) - 1))
+    concurrent, engines = _contexts(engine, jobs)
     try:
         upload_batch(engine, recs, slot)
         prms = []
@@ -405,33 +333,15 @@ def scan_jobs(engine, recs, jobs, slot: int = 0, seq=None):
             p = hiplib.Params.from_buffer_copy(job.prm)
             p.flags = job.prm.flags | (hiplib.F_STORE_SUMS if job.want_sums else 0) | (hiplib.F_STORE_RAW if job.want_raw else 0)
             prms.append(p)
-        if concurrent:
-            for eng, job, p in zip(engines, jobs, prms):
-                if eng is not engine:
-                    eng.share(slot, engine, slot)
-                if getattr(eng, "patterns", None) != job.patterns:
-                    hiplib.set_table(eng, job.patterns)
-                eng.scan(slot, p)
-        for n, (eng, job, p) in enumerate(zip(engines, jobs, prms)):
-            if not concurrent:
-                if len(jobs) > 1 or getattr(eng, "patterns", None) != job.patterns:
-                    hiplib.set_table(eng, job.patterns)
-                eng.scan(slot, p)
-            eng.sync()
-            if n == 0 and hasattr(recs, "release"):
+        for eng, job, p in _scans(engine, engines, concurrent, jobs, prms, slot):
+            if not out and hasattr(recs, "release"):
                 recs.release()             # the upload has completed: the staging buffers go back to the reader
             res = eng.results(slot)
             if p.flags & hiplib.F_BINSEG:              # exact ties: ruptures' float64 answer (a handful of reads at most)
                 hiplib.resolve_ties(eng, slot, res, len(job.patterns), p.jump, p.min_size)
-            if getattr(job, "variants", None) is not None:
-                _census_variants(job, eng, slot, recs, res)
-            if getattr(job, "ends", None) is not None:
-                _sketch_ends(job, eng, slot, recs, res)
-            if getattr(job, "adapters", None) is not None:
-                _find_adapters(job, eng, slot, recs, res)
-            if getattr(job, "refine", None) is not None:
-                _refine_boundaries(job, eng, slot, recs, res)
-            if getattr(job, "tracts", None) is not None:
+            for spec in job.analyses:
+                run_analysis(spec, job.prm, eng, slot, recs, res)
+            if job.tracts is not None:
                 _map_tracts(job, eng, slot, recs)
             sums = raw = win_off = None
             if job.want_sums:

@@ -39,6 +39,13 @@ def check(with_ends: bool, span: int, max_occ: int = DEFAULT_MAX_OCC, min_votes:
     return None
 
 
+FLAG = "endref"                   # (main.EARLY_CHECKS; the rest of its CLI side is inside ends.finish_and_write)
+
+
+def cli_check(args, root: str):
+    return check(getattr(args, "ends", False), args.endspan, args.endrefmaxocc, args.endrefminvotes, args.endrefratio)
+
+
 class Piece:
     """One end of a reference record as stored; scanned like a read (`seq` is all the batch code asks of a record)."""
 

@@ -12,12 +12,10 @@ independent subtelomeres (README, "End groups").
 """
 from __future__ import annotations
 
-import csv
-import threading
-
 import numpy as np
 
-from . import variants
+from . import analyses, variants
+from .analyses import write_csv  # noqa: F401  (stays importable from here)
 
 DEFAULT_SPAN, DEFAULT_K, DEFAULT_BUCKETS, DEFAULT_MIN_MATCH, DEFAULT_MIN_KMERS, DEFAULT_MIN_READS = 2000, 12, 256, 6, 200, 3
 DEFAULT_MAX_LINKS = 64            # links kept per sketch (the smallest partners); rows with more are counted in the log
@@ -43,14 +41,30 @@ def check(unit: str, span: int = DEFAULT_SPAN, k: int = DEFAULT_K, buckets: int 
     return None
 
 
-class EndSpec:
+class EndSpec(analyses.BoundaryAnalysis):
     """What batch.Job(ends=...) carries: the primitive unit, k, the buckets, the window's span, and `sink(recs, res, sketch, kept)`,
-    called by the worker that scanned a batch while that batch is still resident.  `anchor` (anchor.py): the worker also extracts the
-    windows themselves and calls `sink(recs, res, sketch, kept, codes, keep)`."""
+    called by the worker that scanned a batch while that batch is still resident.  The window of a read is [boundary, min(boundary +
+    span, maxlen)) of its telomere-first string (windows).  `anchor` (anchor.py): the worker also extracts the windows themselves,
+    position by position and right behind the sketch, and calls `sink(recs, res, sketch, kept, codes, keep)`."""
 
     def __init__(self, unit: str, k: int = DEFAULT_K, buckets: int = DEFAULT_BUCKETS, span: int = DEFAULT_SPAN, sink=None, anchor: bool = False):
         self.unit, self.k, self.buckets, self.span, self.sink = variants.primitive_root(unit.upper()), int(k), int(buckets), int(span), sink
         self.anchor = bool(anchor)
+
+    def regions(self, res, prm):
+        return windows(res, *self.scan_geometry(prm), self.span)
+
+    def empty(self, n):
+        out = np.full((n, self.buckets), EMPTY, np.uint32), np.zeros(n, np.uint32)
+        if self.anchor:
+            out += np.zeros((n, (self.span + 15) // 16), np.uint32), np.zeros((n, (self.span + 31) // 32), np.uint32)
+        return out
+
+    def launch(self, eng, slot, tails, begin, end):
+        out = tuple(eng.end_sketch(slot, self.unit, tails, begin, end, self.k, self.buckets))
+        if self.anchor:
+            out += tuple(eng.end_window(slot, self.unit, tails, begin, end, self.k, self.span))
+        return out
 
 
 def windows(res, trimfirst: int, slide: int, maxlen: int, span: int):
@@ -115,10 +129,10 @@ def edge_stats(n: int, links, matches):
     return n_edges, best
 
 
-class Collector:
-    """The sink of one k of a run, modelled on variants.Collector.  The workers hand it every batch's sketches (in whatever order
-    they finish); the rows wait until the run's consumer, which sees the batches in file order, asks for them with take(recs) and
-    hands back the rows of the reads with a stored boundary.  finish() links and groups the whole run."""
+class Collector(analyses.Collector):
+    """The sink of one k of a run: take(recs) gives (begin, end, sketch, kept) of a batch, take_windows(recs) the windows' packed rows
+    of the same batch.  finish() links and groups the whole run.  A row: (file, readID, tail, telo_length, begin, end, kept, sketch
+    row) -- with anchor followed by (letters of the window, its codes row, its keep row), which anchor.run reads."""
 
     def __init__(self, unit: str, k: int = DEFAULT_K, buckets: int = DEFAULT_BUCKETS, span: int = DEFAULT_SPAN, min_match: int = DEFAULT_MIN_MATCH,
                  min_kmers: int = DEFAULT_MIN_KMERS, min_reads: int = DEFAULT_MIN_READS, trimfirst: int = 100, slide: int = 6, maxlen: int = 20000,
@@ -127,10 +141,9 @@ class Collector:
         self.unit = self.spec.unit
         self.min_match, self.min_kmers, self.min_reads, self.max_links = int(min_match), int(min_kmers), int(min_reads), int(max_links)
         self.trimfirst, self.slide, self.maxlen = int(trimfirst), int(slide), int(maxlen)
-        self._pending = {}
+        super().__init__()
         self._pending_windows = {}    # (with anchor: the windows' packed rows of the same batches)
-        self._file_rows = {}
-        self._lock = threading.Lock()
+        self.ref_ends = None          # (--endref: endref.scan_reference's list for this k, once the reference has been scanned)
 
     def __call__(self, recs, res, sketch, kept, codes=None, keep=None):
         begin, end = windows(res, self.trimfirst, self.slide, self.maxlen, self.spec.span)
@@ -139,24 +152,20 @@ class Collector:
             if codes is not None:
                 self._pending_windows[id(recs)] = (codes, keep)
 
-    def take(self, recs):
-        """(begin, end, sketch, kept) of a batch the consumer has in hand."""
-        with self._lock:
-            return self._pending.pop(id(recs))
-
     def take_windows(self, recs):
         """(codes, keep) of the same batch, None without anchor."""
         with self._lock:
             return self._pending_windows.pop(id(recs), None)
 
-    def add_file_rows(self, path, rows):
-        """The rows of one input file, in read order: (file, readID, tail, telo_length, begin, end, kept, sketch row) each -- with
-        anchor followed by (letters of the window, its codes row, its keep row), which anchor.run reads."""
-        with self._lock:
-            self._file_rows.setdefault(path, []).extend(rows)
+    def take_batch(self, recs):
+        return self.take(recs) + (self.take_windows(recs),)
 
-    def rows_in_order(self, paths):
-        return [r for p in paths for r in self._file_rows.get(p, [])]
+    def keep_row(self, out, i, file, rid, tail, telo, length):
+        begin, end, sketch, kept, win = out
+        row = (file, rid, tail, telo, int(begin[i]), int(end[i]), int(kept[i]), sketch[i].copy())
+        if win is not None:                        # the letters the window really has: end clamped to the read
+            row += (max(0, min(row[5], length) - row[4]), win[0][i].copy(), win[1][i].copy())
+        return row
 
     def finish(self, paths, engine):
         """Link and group the run's reads on `engine` (anything with sketch_links): (read rows for end_reads_{k}.csv, group rows for
@@ -195,13 +204,6 @@ READ_HEADER = ["file", "readID", "tail", "telo_length", "window_begin", "window_
 GROUP_HEADER = ["end", "reads", "forward", "reverse", "telo_min", "telo_median", "telo_mean", "telo_max"]
 
 
-def write_csv(path, header, rows):
-    with open(path, "w", newline="") as f:
-        w = csv.writer(f)
-        w.writerow(header)
-        w.writerows(rows)
-
-
 def summary(col: Collector, stats) -> list[str]:
     """The log lines of one k."""
     s = stats
@@ -209,3 +211,47 @@ def summary(col: Collector, stats) -> list[str]:
             f"subtelomere {col.spec.k}-mers compared",
             f"  {s['groups']} groups of at least {col.min_reads} reads: {s['assigned']} reads assigned, {s['reads'] - s['assigned']} unassigned (end 0)",
             f"  {s['cut']} reads had more than {col.max_links} partners behind them: their links were cut at {col.max_links}"]
+
+
+# ---- the CLI's side (main.ANALYSES)
+FLAG = "ends"
+POWER_NOTE = "k-mers with words of {unit} are left out of the sketches"
+
+
+def cli_check(args, root: str):
+    return check(root, args.endspan, args.endk, args.endbuckets, args.endminmatch, args.endminkmers, args.endminreads)
+
+
+def cli_collector(args, unit: str, slide: int, anchor=None):
+    """`anchor`: None = as --anchor or --endref ask (either keeps the windows)."""
+    if anchor is None:
+        anchor = bool(getattr(args, "anchor", False) or getattr(args, "endref", None))
+    return Collector(unit, args.endk, args.endbuckets, args.endspan, args.endminmatch, args.endminkmers, args.endminreads, args.trimfirst, slide,
+                     args.maxlengthtelo, anchor=anchor)
+
+
+def finish_and_write(args, k, col, filenames, engines):
+    """All pairs of the run's sketches: one call per k, on one context, after the last file; then, with --anchor, one boundary per
+    group and, with the ends of --endref's reference (col.ref_ends), one name per read.  Writes the files; yields the log lines."""
+    from . import anchor, endref
+    out = args.outputDir
+    try:
+        read_rows, group_rows, stats = col.finish(filenames, engines[0])
+    except ValueError as e:                        # more reads than one link call takes: said, not hidden; every other output stands
+        yield f"{e}; no end groups written for k = {k}"
+        return
+    yield analyses.write_tables(out, k, "end groups", [("end_reads", READ_HEADER, read_rows), ("ends", GROUP_HEADER, group_rows)])
+    yield from summary(col, stats)
+    if getattr(args, "anchor", False):
+        # every grouped read's window against its group's reference, one call per k
+        a_reads, a_groups, a_stats = anchor.run(col.rows_in_order(filenames), read_rows, engines[0], col.spec.k, col.spec.span,
+                                                args.anchorminvotes, args.anchorratio)
+        yield analyses.write_tables(out, k, "anchored lengths", [("anchored_reads", anchor.READ_HEADER, a_reads), ("anchored_ends", anchor.GROUP_HEADER, a_groups)])
+        yield from anchor.summary(a_stats, args.anchorminvotes, args.anchorratio)
+    if col.ref_ends is not None:
+        # every read's window on all the reference's ends, one call per k
+        refs, reads, groups, r_stats = endref.run(col.rows_in_order(filenames), read_rows, col.ref_ends, engines[0], col.spec.k, col.spec.span,
+                                                  args.endminkmers, args.endrefmaxocc, args.endrefminvotes, args.endrefratio)
+        yield analyses.write_tables(out, k, "named ends", [("ref_ends", endref.REF_HEADER, refs), ("named_reads", endref.READ_HEADER, reads),
+                                                          ("named_ends", endref.GROUP_HEADER, groups)])
+        yield from endref.summary(r_stats, args.endminkmers, args.endrefminvotes, args.endrefratio)

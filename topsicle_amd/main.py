@@ -28,6 +28,15 @@ CONTEXTS_PER_GPU = 2
 WRITER_THREADS = 1                # threads that write the passing records (native FASTQ writer, pwritev at offsets known up front).  Three were measured
                                   # (round 5, configs[3]'s shard: 7.5 GB of records): buffered writes into ONE file serialise on the inode, three threads
                                   # reach 1.4 - 2.0 GB/s each where one reaches 4.9 - 6.5 -- 1.68 -> 2.30 s (.gz), 1.50 -> 2.07 s (BGZF); one it is
+# The read analyses, in the order of their launches behind a scan and of their blocks in the log.  Each module has the CLI's side of
+# its analysis: FLAG (the flag that turns it on = its keyword of batch.Job), cli_check(args, root) -> None or the words after
+# "--flag needs", POWER_NOTE (what it does with a motif that is a power of its root), cli_collector(args, unit, slide),
+# Collector.keep_row (what is kept per read with a stored boundary) and finish_and_write(args, k, col, filenames, engines) -> log lines.
+PER_K_ANALYSES = (variants, ends, adapters, refine)       # one collector per k
+ANALYSES = PER_K_ANALYSES + (tracts,)                     # one for the run: the map of whole reads, with the first k's job
+# ... and what is checked before anything is read or written, in this order (--variants is only checked against the real unit;
+# --anchor and --endref hang on --ends and have nothing else to check)
+EARLY_CHECKS = (tracts, ends, anchor, endref, adapters, refine)
 LAST_TIMINGS = {}                 # seconds of the last analysis_run: reads (step 1 + 2 + outputs) / summary (fit + PNG); bench.py's e2e leg reads it
 PLOT_THREADS = []                 # quadratic-fit PNGs being rendered off the critical path (summarize); wait_for_plots() joins them
 
@@ -154,21 +163,10 @@ def process_file_multi(args, seq_loc, phrases, engines):
     npz = want_raw and getattr(args, "rawcountformat", "csv") == "npz"
     raw_npz = [rawnpz.RawNpzWriter(f"{args.outputDir}/rawcount_{telo_phrase}_{file_name}.npz", pattern, sliding_val, args.read_check or None)
                if npz else None for telo_phrase, pattern, sliding_val in phrases]
-    # --variants: one collector per k for the whole run (analysis_run made them); the census runs on the batch workers
-    vcols = getattr(args, "variant_collectors", None) or [None] * len(phrases)
-    vrows = [[] for _ in phrases]
-    # --ends: the same per k; the sketch runs on the batch workers, the links once per run (analysis_run)
-    ecols = getattr(args, "end_collectors", None) or [None] * len(phrases)
-    erows = [[] for _ in phrases]
-    # --adapters: the same per k; the search runs on the batch workers, the naming rule once per run (analysis_run)
-    acols = getattr(args, "adapter_collectors", None) or [None] * len(phrases)
-    arows = [[] for _ in phrases]
-    # --refine: the same per k; the kernel runs on the batch workers, the class rule once per run (analysis_run)
-    rcols = getattr(args, "refine_collectors", None) or [None] * len(phrases)
-    rrows = [[] for _ in phrases]
-    jobs = [batch.Job(pattern, _scan_params(args, slide), want_sums, want_raw, raw_sink=sink, variants=None if col is None else col.spec,
-                      ends=None if ecol is None else ecol.spec, adapters=None if acol is None else acol.spec, refine=None if rcol is None else rcol.spec)
-        for (_k, pattern, slide), sink, col, ecol, acol, rcol in zip(phrases, raw_npz, vcols, ecols, acols, rcols)]
+    # the read analyses: per k {flag: collector} for the whole run (analysis_run made them); the kernels run on the batch workers
+    cols = getattr(args, "analysis_collectors", None) or [{} for _ in phrases]
+    jobs = [batch.Job(pattern, _scan_params(args, slide), want_sums, want_raw, raw_sink=sink, **{flag: col.spec for flag, col in mine.items()})
+            for (_k, pattern, slide), sink, mine in zip(phrases, raw_npz, cols)]
     # --tracts: one collector for the whole run; the map runs once per batch, with the first k's job
     tcol = getattr(args, "tract_collector", None)
     if tcol is not None:
@@ -258,11 +256,7 @@ def process_file_multi(args, seq_loc, phrases, engines):
                 tcol.add_batch(seq_loc, file_name, lambda i: pb.read_id(int(i)), pb.desc["len"], t_tracts, t_found)
             for n, ((telo_phrase, pattern, sliding_val), (res, sums, raw, win_off)) in enumerate(zip(phrases, outs)):
                 idx = np.nonzero(res["pass"])[0]
-                vout = vcols[n].take(pb) if vcols[n] is not None else None
-                eout = ecols[n].take(pb) if ecols[n] is not None else None
-                ewin = ecols[n].take_windows(pb) if ecols[n] is not None else None          # (--anchor: the windows themselves)
-                aout = acols[n].take(pb) if acols[n] is not None else None
-                rout = rcols[n].take(pb) if rcols[n] is not None else None
+                taken = [(col, col.take_batch(pb)) for col in cols[n].values()]
                 if wthread is not None and len(idx) and n == writer_k:
                     write_passing(pb, idx)                                   # every passing record (main.py:83-86)
                 ids = [pb.read_id(int(i)) for i in idx]
@@ -282,24 +276,9 @@ def process_file_multi(args, seq_loc, phrases, engines):
                 for j in np.nonzero(bkp < 0)[0]:
                     tprint(f"read {ids[j]}: {int(r['n_win'][j])} windows, no admissible change point; reporting 0")
                 telo_l, trc_l = telolen.tolist(), trc.tolist()
-                if vout is not None:                                         # one row per read with a stored boundary
-                    v_begin, v_end, v_counts = vout
-                    vrows[n] += [(file_name, ids[j], int(r["tail"][j]), int(v_begin[idx[j]]), int(v_end[idx[j]]), v_counts[idx[j]])
-                                 for j in np.nonzero(telolen != 0)[0]]
-                if eout is not None:                                         # one row per read with a stored boundary
-                    e_begin, e_end, e_sketch, e_kept = eout
-                    stored = np.nonzero(telolen != 0)[0]
-                    new = [(file_name, ids[j], int(r["tail"][j]), telo_l[j], int(e_begin[idx[j]]), int(e_end[idx[j]]), int(e_kept[idx[j]]),
-                            e_sketch[idx[j]].copy()) for j in stored]
-                    if ewin is not None:                                     # the letters the window really has: end clamped to the read
-                        new = [row + (max(0, min(row[5], int(lens[j])) - row[4]), ewin[0][idx[j]].copy(), ewin[1][idx[j]].copy()) for row, j in zip(new, stored)]
-                    erows[n] += new
-                if aout is not None:                                         # one row per read with a stored boundary
-                    a_dist, a_end = aout
-                    arows[n] += [(file_name, ids[j], int(r["tail"][j]), telo_l[j], a_dist[idx[j]].copy(), a_end[idx[j]].copy())
-                                 for j in np.nonzero(telolen != 0)[0]]
-                if rout is not None:                                         # one row per read with a stored boundary
-                    rrows[n] += [(file_name, ids[j], int(r["tail"][j]), telo_l[j], rout[idx[j]].copy()) for j in np.nonzero(telolen != 0)[0]]
+                stored = np.nonzero(telolen != 0)[0]                         # one row per read with a stored boundary
+                for col, out in taken:
+                    col.add_file_rows(seq_loc, [col.keep_row(out, int(idx[j]), file_name, ids[j], int(r["tail"][j]), telo_l[j], int(lens[j])) for j in stored])
                 if n == 0:
                     with _CSV_LOCK, open(csv_path, mode="a", newline="") as fh:
                         csv.writer(fh).writerows(zip([file_name] * len(ids), [telo_phrase] * len(ids), ["%.3f" % t for t in trc_l], ids, telo_l))
@@ -344,18 +323,6 @@ def process_file_multi(args, seq_loc, phrases, engines):
             nbytes = os.path.getsize(fasta_temp)
             tprint(f"{base_name}: {wstat['records']} passing records, {nbytes} bytes written in {wstat['write_s']:.2f} thread-seconds on {len(wthreads)} writer threads "
                    f"({nbytes / wstat['write_s'] / 1e9:.2f} GB/s per thread); the scan loop waited {wstat['blocked_s']:.2f} s for them")
-    for col, vr in zip(vcols, vrows):
-        if col is not None:
-            col.add_file_rows(seq_loc, vr)
-    for col, er in zip(ecols, erows):
-        if col is not None:
-            col.add_file_rows(seq_loc, er)
-    for col, ar in zip(acols, arows):
-        if col is not None:
-            col.add_file_rows(seq_loc, ar)
-    for col, rr in zip(rcols, rrows):
-        if col is not None:
-            col.add_file_rows(seq_loc, rr)
     st = pool.stats
     if st.get("shards", 0) > 1:
         tprint(f"{base_name}: read as {st['shards']} byte ranges, one reader team each")
@@ -388,45 +355,8 @@ def analysis_run(args, engines=None, engine_factory=None, wait_plots=True):
         tprint(f"{k}: {v}")
     print("---------------------")
     tprint("Starting Topsicle analysis")
-    if getattr(args, "tracts", False):
-        # (before any file is read or written; the root of a motif that --pattern auto has yet to find is checked below)
-        root = "ACGT" if args.pattern.strip().lower() == "auto" else variants.primitive_root(args.pattern.upper())
-        why = tracts.check(root, args.tractblock, args.tractminhits, args.tractgap, args.tractminblocks, tracts.DEFAULT_MAX_TRACTS, args.tractedge)
-        if why is not None:
-            tprint(f"--tracts needs {why}")
-            sys.exit(2)
-    if getattr(args, "ends", False):
-        root = "ACGT" if args.pattern.strip().lower() == "auto" else variants.primitive_root(args.pattern.upper())
-        why = ends.check(root, args.endspan, args.endk, args.endbuckets, args.endminmatch, args.endminkmers, args.endminreads)
-        if why is not None:
-            tprint(f"--ends needs {why}")
-            sys.exit(2)
-    if getattr(args, "anchor", False):
-        why = anchor.check(getattr(args, "ends", False), args.endspan, args.anchorminvotes, args.anchorratio)
-        if why is not None:
-            tprint(f"--anchor needs {why}")
-            sys.exit(2)
-    if getattr(args, "endref", None):
-        why = endref.check(getattr(args, "ends", False), args.endspan, args.endrefmaxocc, args.endrefminvotes, args.endrefratio)
-        if why is not None:
-            tprint(f"--endref needs {why}")
-            sys.exit(2)
-    adapter_pats = None
-    if getattr(args, "adapters", None):
-        # (before any input file is read or written; the sequences come from the command line or from their own small file)
-        adapter_pats = adapters.load_patterns(args.adapters)
-        why = adapters.check(adapter_pats, args.adaptersearch, args.adaptererr, args.adaptermargin, args.maxlengthtelo)
-        if why is not None:
-            tprint(f"--adapters needs {why}")
-            sys.exit(2)
-    if getattr(args, "refine", False):
-        # (before any input file is read or written; the root of a motif that --pattern auto has yet to find is checked below)
-        root = "ACGT" if args.pattern.strip().lower() == "auto" else variants.primitive_root(args.pattern.upper())
-        why = refine.check(root, args.refinehit, args.refinemiss, args.refinesep, args.refineminscore, args.refinemindrop, args.refineminmargin,
-                           args.trimfirst, args.maxlengthtelo)
-        if why is not None:
-            tprint(f"--refine needs {why}")
-            sys.exit(2)
+    # (before any file is read or written; the root of a motif that --pattern auto has yet to find is checked below)
+    _check_flags(args, EARLY_CHECKS, "ACGT" if args.pattern.strip().lower() == "auto" else variants.primitive_root(args.pattern.upper()))
     if args.pattern.strip().lower() == "auto":
         # the motif comes from the reads (motif.py); from here on the run is the one `--pattern <that motif>` would have been
         if engines is None:
@@ -481,76 +411,27 @@ def analysis_run(args, engines=None, engine_factory=None, wait_plots=True):
         tprint("patterns to search:", pattern)
         phrases.append((telo_phrase, pattern, sliding_val))
 
-    args.variant_collectors = None
-    if getattr(args, "variants", False):
-        unit = variants.primitive_root(args.pattern.upper())
-        if unit != args.pattern.upper():
-            tprint(f"--variants: {args.pattern} is a power of {unit}; the census counts against {unit}")
-        lo, hi = hiplib.VARIANT_BIN_RANGE
-        if not (2 <= len(unit) <= hiplib.VARIANT_MAX_UNIT) or not (lo <= args.variantbin <= hi) or not (1 <= args.variantbins <= hiplib.VARIANT_MAX_BINS):
-            tprint(f"--variants needs a motif whose root has 2..{hiplib.VARIANT_MAX_UNIT} letters, --variantbin {lo}..{hi} and --variantbins 1..{hiplib.VARIANT_MAX_BINS}")
-            sys.exit(2)
-        args.variant_collectors = [variants.Collector(unit, args.variantbin, args.variantbins, args.trimfirst, slide, args.maxlengthtelo)
-                                   for _k, _pattern, slide in phrases]
-
-    args.end_collectors = None
-    if getattr(args, "ends", False):
-        unit = variants.primitive_root(args.pattern.upper())
-        why = ends.check(unit, args.endspan, args.endk, args.endbuckets, args.endminmatch, args.endminkmers, args.endminreads)
-        if why is not None:
-            tprint(f"--ends needs {why}")
-            sys.exit(2)
-        if unit != args.pattern.upper():
-            tprint(f"--ends: {args.pattern} is a power of {unit}; k-mers with words of {unit} are left out of the sketches")
-        args.end_collectors = [ends.Collector(unit, args.endk, args.endbuckets, args.endspan, args.endminmatch, args.endminkmers, args.endminreads,
-                                              args.trimfirst, slide, args.maxlengthtelo,
-                                              anchor=bool(getattr(args, "anchor", False) or getattr(args, "endref", None)))      # (either keeps the windows)
-                               for _k, _pattern, slide in phrases]
-    ref_ends = None
-    if getattr(args, "endref", None):
-        # the reference's ends: its pieces scanned like reads, every k's table at once, into collectors of their own
-        rcols = [ends.Collector(unit, args.endk, args.endbuckets, args.endspan, args.endminmatch, args.endminkmers, args.endminreads,
-                                args.trimfirst, slide, args.maxlengthtelo, anchor=True) for _k, _pattern, slide in phrases]
-        ref_ends = endref.scan_reference(args.endref, engines[0], [batch.Job(pattern, _scan_params(args, slide), ends=col.spec)
-                                                                   for (_k, pattern, slide), col in zip(phrases, rcols)],
-                                         rcols, args.maxlengthtelo, args.endminkmers)
-        for (telo_phrase, _pattern, _slide), listed in zip(phrases, ref_ends):
-            if sum(e.indexed for e in listed) > endref.MAX_REFS:
-                tprint(f"--endref: {sum(e.indexed for e in listed)} usable reference ends for k = {telo_phrase}, {endref.MAX_REFS} at most")
-                sys.exit(2)
-
-    args.adapter_collectors = None
-    if adapter_pats is not None:
-        args.adapter_collectors = [adapters.Collector(adapter_pats, args.adaptersearch, args.adaptererr, args.adaptermargin) for _ in phrases]
-
-    args.refine_collectors = None
-    if getattr(args, "refine", False):
-        unit = variants.primitive_root(args.pattern.upper())
-        why = refine.check(unit, args.refinehit, args.refinemiss, args.refinesep, args.refineminscore, args.refinemindrop, args.refineminmargin,
-                           args.trimfirst, args.maxlengthtelo)
-        if why is not None:
-            tprint(f"--refine needs {why}")
-            sys.exit(2)
-        if unit != args.pattern.upper():
-            tprint(f"--refine: {args.pattern} is a power of {unit}; the hits are words of {unit}")
-        args.refine_collectors = [refine.Collector(unit, args.refinehit, args.refinemiss, args.refinesep, args.refineminscore, args.refinemindrop,
-                                                   args.refineminmargin, args.trimfirst) for _ in phrases]
-
-    args.tract_collector = None
-    if getattr(args, "tracts", False):
-        unit = variants.primitive_root(args.pattern.upper())
-        why = tracts.check(unit, args.tractblock, args.tractminhits, args.tractgap, args.tractminblocks, tracts.DEFAULT_MAX_TRACTS, args.tractedge)
-        if why is not None:
-            tprint(f"--tracts needs {why}")
-            sys.exit(2)
-        if unit != args.pattern.upper():
-            tprint(f"--tracts: {args.pattern} is a power of {unit}; the map looks for {unit}")
-        # the map needs whole reads on the device: no heads-only batches
-        if getattr(args, "twopass", None) == "on":
-            tprint("--tracts maps whole reads: --twopass on ignored")
-        tprint("--tracts: every file is scanned as whole reads (--twopass off)")
-        args.twopass = "off"
-        args.tract_collector = tracts.Collector(unit, args.tractblock, args.tractminhits, args.tractgap, args.tractminblocks, tracts.DEFAULT_MAX_TRACTS, args.tractedge)
+    # one collector per analysis and k (tracts: one for the run) for the whole run; process_file_multi hangs them on its jobs
+    unit = variants.primitive_root(args.pattern.upper())
+    args.analysis_collectors, args.tract_collector = [{} for _ in phrases], None
+    for mod in ANALYSES:
+        if not getattr(args, mod.FLAG, None):
+            continue
+        _check_flags(args, (mod,), unit)
+        if mod.POWER_NOTE and unit != args.pattern.upper():
+            tprint(f"--{mod.FLAG}: {args.pattern} is a power of {unit}; " + mod.POWER_NOTE.format(unit=unit))
+        if mod is tracts:
+            # the map needs whole reads on the device: no heads-only batches
+            if getattr(args, "twopass", None) == "on":
+                tprint("--tracts maps whole reads: --twopass on ignored")
+            tprint("--tracts: every file is scanned as whole reads (--twopass off)")
+            args.twopass = "off"
+            args.tract_collector = tracts.cli_collector(args, unit)
+            continue
+        for mine, (_k, _pattern, slide) in zip(args.analysis_collectors, phrases):
+            mine[mod.FLAG] = mod.cli_collector(args, unit, slide)
+        if mod is ends and getattr(args, "endref", None):
+            _scan_endref(args, unit, phrases, engines[0])
 
     filenames = []
     if os.path.isdir(args.inputDir):
@@ -580,68 +461,13 @@ def analysis_run(args, engines=None, engine_factory=None, wait_plots=True):
             with _CSV_LOCK, open(output_csv, mode="a", newline="") as fh:
                 csv.writer(fh).writerows(late)
 
-    for (telo_phrase, _pattern, _slide), col in zip(phrases, args.variant_collectors or []):
-        variants.write_reads_csv(f"{args.outputDir}/variants_{telo_phrase}.csv", col.unit, col.rows_in_order(filenames))
-        variants.write_profile_csv(f"{args.outputDir}/variant_profile_{telo_phrase}.csv", col.unit, col.profile, col.spec.bin)
-        tprint(f"variant repeats (k = {telo_phrase}): {args.outputDir}/variants_{telo_phrase}.csv, {args.outputDir}/variant_profile_{telo_phrase}.csv")
-        for line in variants.summary(col.unit, col.total, col.n_tracts):
-            tprint(line)
-
-    for n, ((telo_phrase, _pattern, _slide), col) in enumerate(zip(phrases, args.end_collectors or [])):
-        # all pairs of the run's sketches: one call per k, on one context, after the last file
-        try:
-            read_rows, group_rows, stats = col.finish(filenames, engines[0])
-        except ValueError as e:                    # more reads than one link call takes: said, not hidden; every other output stands
-            tprint(f"{e}; no end groups written for k = {telo_phrase}")
-            continue
-        ends.write_csv(f"{args.outputDir}/end_reads_{telo_phrase}.csv", ends.READ_HEADER, read_rows)
-        ends.write_csv(f"{args.outputDir}/ends_{telo_phrase}.csv", ends.GROUP_HEADER, group_rows)
-        tprint(f"end groups (k = {telo_phrase}): {args.outputDir}/end_reads_{telo_phrase}.csv, {args.outputDir}/ends_{telo_phrase}.csv")
-        for line in ends.summary(col, stats):
-            tprint(line)
-        if getattr(args, "anchor", False):
-            # one boundary per group: every grouped read's window against its group's reference, one call per k
-            a_reads, a_groups, a_stats = anchor.run(col.rows_in_order(filenames), read_rows, engines[0], col.spec.k, col.spec.span,
-                                                    args.anchorminvotes, args.anchorratio)
-            ends.write_csv(f"{args.outputDir}/anchored_reads_{telo_phrase}.csv", anchor.READ_HEADER, a_reads)
-            ends.write_csv(f"{args.outputDir}/anchored_ends_{telo_phrase}.csv", anchor.GROUP_HEADER, a_groups)
-            tprint(f"anchored lengths (k = {telo_phrase}): {args.outputDir}/anchored_reads_{telo_phrase}.csv, {args.outputDir}/anchored_ends_{telo_phrase}.csv")
-            for line in anchor.summary(a_stats, args.anchorminvotes, args.anchorratio):
-                tprint(line)
-        if ref_ends is not None:
-            # one name per read: every read's window on all the reference's ends, one call per k
-            r_refs, r_reads, r_groups, r_stats = endref.run(col.rows_in_order(filenames), read_rows, ref_ends[n], engines[0], col.spec.k, col.spec.span,
-                                                            args.endminkmers, args.endrefmaxocc, args.endrefminvotes, args.endrefratio)
-            names = [f"{args.outputDir}/{stem}_{telo_phrase}.csv" for stem in ("ref_ends", "named_reads", "named_ends")]
-            for path, header, out_rows in zip(names, (endref.REF_HEADER, endref.READ_HEADER, endref.GROUP_HEADER), (r_refs, r_reads, r_groups)):
-                ends.write_csv(path, header, out_rows)
-            tprint(f"named ends (k = {telo_phrase}): " + ", ".join(names))
-            for line in endref.summary(r_stats, args.endminkmers, args.endrefminvotes, args.endrefratio):
-                tprint(line)
-
-    for (telo_phrase, _pattern, _slide), col in zip(phrases, args.adapter_collectors or []):
-        a_reads, a_summary, a_stats = col.finish(filenames)
-        adapters.write_csv(f"{args.outputDir}/adapters_{telo_phrase}.csv", adapters.READ_HEADER, a_reads)
-        adapters.write_csv(f"{args.outputDir}/adapter_summary_{telo_phrase}.csv", adapters.SUMMARY_HEADER, a_summary)
-        tprint(f"adapters (k = {telo_phrase}): {args.outputDir}/adapters_{telo_phrase}.csv, {args.outputDir}/adapter_summary_{telo_phrase}.csv")
-        for line in adapters.summary(col, a_stats):
-            tprint(line)
-
-    for (telo_phrase, _pattern, _slide), col in zip(phrases, args.refine_collectors or []):
-        r_reads, r_summary, r_stats = col.finish(filenames)
-        refine.write_csv(f"{args.outputDir}/refined_{telo_phrase}.csv", refine.READ_HEADER, r_reads)
-        refine.write_csv(f"{args.outputDir}/refine_summary_{telo_phrase}.csv", refine.SUMMARY_HEADER, r_summary)
-        tprint(f"refined boundaries (k = {telo_phrase}): {args.outputDir}/refined_{telo_phrase}.csv, {args.outputDir}/refine_summary_{telo_phrase}.csv")
-        for line in refine.summary(col, r_stats):
-            tprint(line)
-
+    for mod in PER_K_ANALYSES:
+        for (telo_phrase, _pattern, _slide), mine in zip(phrases, args.analysis_collectors):
+            if mod.FLAG in mine:
+                for line in mod.finish_and_write(args, telo_phrase, mine[mod.FLAG], filenames, engines):
+                    tprint(line)
     if args.tract_collector is not None:
-        tcol = args.tract_collector
-        tract_rows, read_rows = tcol.rows_in_order(filenames)
-        tracts.write_tracts_csv(f"{args.outputDir}/tracts.csv", tract_rows)
-        tracts.write_reads_csv(f"{args.outputDir}/tract_reads.csv", read_rows)
-        tprint(f"tract map: {args.outputDir}/tracts.csv, {args.outputDir}/tract_reads.csv")
-        for line in tracts.summary(tcol.unit, tcol.classes):
+        for line in tracts.finish_and_write(args, None, args.tract_collector, filenames, engines):
             tprint(line)
 
     t_sum = time.perf_counter()
@@ -650,6 +476,30 @@ def analysis_run(args, engines=None, engine_factory=None, wait_plots=True):
     tprint("All telomere found, have a nice day.")
     if wait_plots:
         wait_for_plots()
+
+
+def _check_flags(args, mods, root):
+    """The flags of the analyses that are switched on against `root`, the motif's primitive root: the run ends with one message at
+    the first that does not hold."""
+    for mod in mods:
+        why = mod.cli_check(args, root) if getattr(args, mod.FLAG, None) else None
+        if why is not None:
+            tprint(f"--{mod.FLAG} needs {why}")
+            sys.exit(2)
+
+
+def _scan_endref(args, unit, phrases, engine):
+    """--endref: the reference's ends -- its pieces scanned like reads, every k's table at once, into end collectors of their own that
+    keep the windows -- left with the run's end collectors (ends.finish_and_write names the reads against them)."""
+    own = [ends.cli_collector(args, unit, slide, anchor=True) for _k, _pattern, slide in phrases]
+    ref_ends = endref.scan_reference(args.endref, engine, [batch.Job(pattern, _scan_params(args, slide), ends=col.spec)
+                                                           for (_k, pattern, slide), col in zip(phrases, own)],
+                                     own, args.maxlengthtelo, args.endminkmers)
+    for (telo_phrase, _pattern, _slide), listed, mine in zip(phrases, ref_ends, args.analysis_collectors):
+        if sum(e.indexed for e in listed) > endref.MAX_REFS:
+            tprint(f"--endref: {sum(e.indexed for e in listed)} usable reference ends for k = {telo_phrase}, {endref.MAX_REFS} at most")
+            sys.exit(2)
+        mine["ends"].ref_ends = listed
 
 
 def _open_engines(args, engine_factory):

@@ -15,9 +15,10 @@ synthetic reads.
 """
 from __future__ import annotations
 
-import csv
-
 import numpy as np
+
+from . import analyses
+from .analyses import median_cell, write_csv  # noqa: F401  (write_csv stays importable from here)
 
 DEFAULT_HIT, DEFAULT_MISS, DEFAULT_SEP = 2, 1, 200
 DEFAULT_MIN_SCORE, DEFAULT_MIN_DROP, DEFAULT_MIN_MARGIN = 100, 100, 50
@@ -31,13 +32,27 @@ def word_len(unit: str) -> int:
     return min(len(unit), 8)
 
 
-class RefineSpec:
+class RefineSpec(analyses.BoundaryAnalysis):
     """What batch.Job(refine=...) carries: the primitive unit, the rule's weights and `sink(recs, res, rows)`, called by the worker
-    that scanned a batch while that batch is still resident."""
+    that scanned a batch while that batch is still resident.  The region ends at maxlen: it lies inside the span packed for the
+    second pass of the two-pass route."""
 
     def __init__(self, unit: str, hit: int = DEFAULT_HIT, miss: int = DEFAULT_MISS, sep: int = DEFAULT_SEP, sink=None):
         self.unit, self.hit, self.miss, self.sep, self.sink = unit.upper(), int(hit), int(miss), int(sep), sink
         self.w = word_len(self.unit)
+
+    def regions(self, res, prm):
+        return regions(res, *self.scan_geometry(prm), self.w)
+
+    def empty(self, n):
+        """the row of an empty region"""
+        from . import hiplib
+        rows = np.zeros(n, hiplib.REFINE_DTYPE)
+        rows["runner_pos"] = -1
+        return rows,
+
+    def launch(self, eng, slot, tails, begin, end, at):
+        return eng.boundary_refine(slot, self.unit, tails, begin, end, at, hit=self.hit, miss=self.miss, sep=self.sep),
 
 
 def check(unit: str, hit: int, miss: int, sep: int, minscore: int, mindrop: int, minmargin: int, trimfirst: int, maxlen: int):
@@ -85,36 +100,17 @@ def classify(score: int, drop: int, margin, minscore: int = DEFAULT_MIN_SCORE, m
     return "clean"
 
 
-class Collector:
-    """The sink of one k of a run, like adapters.Collector: the workers hand it every batch's rows (in whatever order they finish),
-    the run's consumer, which sees the batches in file order, asks for them with take(recs)."""
+class Collector(analyses.Collector):
+    """The sink of one k of a run: the kernel's rows per batch.  A row: (file, readID, tail, telo_length, the read's row)."""
 
     def __init__(self, unit: str, hit: int = DEFAULT_HIT, miss: int = DEFAULT_MISS, sep: int = DEFAULT_SEP, minscore: int = DEFAULT_MIN_SCORE,
                  mindrop: int = DEFAULT_MIN_DROP, minmargin: int = DEFAULT_MIN_MARGIN, trimfirst: int = 100):
-        import threading
+        super().__init__()
         self.spec = RefineSpec(unit, hit, miss, sep, self)
         self.minscore, self.mindrop, self.minmargin, self.trimfirst = int(minscore), int(mindrop), int(minmargin), int(trimfirst)
-        self._pending = {}
-        self._file_rows = {}
-        self._lock = threading.Lock()
 
-    def __call__(self, recs, res, rows):
-        with self._lock:
-            self._pending[id(recs)] = rows
-
-    def take(self, recs):
-        """The rows of a batch the consumer has in hand."""
-        with self._lock:
-            return self._pending.pop(id(recs))
-
-    def add_file_rows(self, path, rows):
-        """The rows of one input file, in read order: (file, readID, tail, telo_length, row) each."""
-        with self._lock:
-            self._file_rows.setdefault(path, []).extend(rows)
-
-    def rows_in_order(self, paths):
-        for p in paths:
-            yield from self._file_rows.get(p, [])
+    def keep_row(self, out, i, file, rid, tail, telo, length):
+        return file, rid, tail, telo, out[0][i].copy()
 
     def read_row(self, file, rid, tail, telo, row):
         """One line of refined_{k}.csv and its class."""
@@ -132,8 +128,8 @@ class Collector:
         """(read rows, summary rows, stats) of the run."""
         read_rows = [self.read_row(*r) for r in self.rows_in_order(paths)]
         per = {c: [r for r in read_rows if r[-1] == c] for c in CLASSES}
-        summary_rows = [[c, len(per[c]), _median([r[3] for r in per[c]]), _median([r[4] for r in per[c]]), _median([abs(r[5]) for r in per[c]])] for c in CLASSES]
-        stats = {"reads": len(read_rows), "counts": {c: len(per[c]) for c in CLASSES}, "clean_shift_median": _median([abs(r[5]) for r in per["clean"]])}
+        summary_rows = [[c, len(per[c]), median_cell([r[3] for r in per[c]]), median_cell([r[4] for r in per[c]]), median_cell([abs(r[5]) for r in per[c]])] for c in CLASSES]
+        stats = {"reads": len(read_rows), "counts": {c: len(per[c]) for c in CLASSES}, "clean_shift_median": median_cell([abs(r[5]) for r in per["clean"]])}
         return read_rows, summary_rows, stats
 
 
@@ -147,24 +143,9 @@ def _density(hits: int, positions: int) -> str:
     return "" if positions <= 0 else "%.3f" % (hits / positions)
 
 
-def _median(xs):
-    """The median as a CSV cell: empty without values, a whole number where it is one."""
-    if not len(xs):
-        return ""
-    m = float(np.median(np.asarray(xs, np.float64)))
-    return int(m) if m == int(m) else m
-
-
 READ_HEADER = ["file", "readID", "tail", "telo_length", "refined_length", "shift", "score", "drop", "margin", "called_deficit", "density_before", "density_after",
                "class"]
 SUMMARY_HEADER = ["class", "reads", "telo_median", "refined_median", "abs_shift_median"]
-
-
-def write_csv(path, header, rows):
-    with open(path, "w", newline="") as f:
-        w = csv.writer(f)
-        w.writerow(header)
-        w.writerows(rows)
 
 
 def summary(col: Collector, stats) -> list[str]:
@@ -176,3 +157,24 @@ def summary(col: Collector, stats) -> list[str]:
             f"minscore {col.minscore}, mindrop {col.mindrop}, minmargin {col.minmargin})",
             f"  {counts}",
             f"  median |refined_length - telo_length| of the clean reads: {med if med != '' else 'n/a'}"]
+
+
+# ---- the CLI's side (main.ANALYSES)
+FLAG = "refine"
+POWER_NOTE = "the hits are words of {unit}"
+
+
+def cli_check(args, root: str):
+    return check(root, args.refinehit, args.refinemiss, args.refinesep, args.refineminscore, args.refinemindrop, args.refineminmargin,
+                 args.trimfirst, args.maxlengthtelo)
+
+
+def cli_collector(args, unit: str, slide: int):
+    return Collector(unit, args.refinehit, args.refinemiss, args.refinesep, args.refineminscore, args.refinemindrop, args.refineminmargin, args.trimfirst)
+
+
+def finish_and_write(args, k, col, filenames, engines):
+    """The class rule once per run and k; writes the two files, yields the log lines."""
+    read_rows, summary_rows, stats = col.finish(filenames)
+    yield analyses.write_tables(args.outputDir, k, "refined boundaries", [("refined", READ_HEADER, read_rows), ("refine_summary", SUMMARY_HEADER, summary_rows)])
+    yield from summary(col, stats)

@@ -9,13 +9,12 @@ tracts, the two CSV files and the summary for the log.  The map only reports: wh
 """
 from __future__ import annotations
 
-import csv
 import logging
-import threading
 
 import numpy as np
 
-from . import variants
+from . import analyses, variants
+from .analyses import write_csv
 
 DEFAULT_BLOCK, DEFAULT_MIN_HITS, DEFAULT_GAP, DEFAULT_MIN_BLOCKS, DEFAULT_MAX_TRACTS, DEFAULT_EDGE = 64, 20, 1, 2, 8, 256
 MIN_UNIT, MAX_UNIT = 4, 32
@@ -87,27 +86,19 @@ def classify(L: int, tracts_C, tracts_G, edge: int = DEFAULT_EDGE, slack: int = 
     return "none"
 
 
-class Collector:
-    """The sink of a run.  The workers hand it every batch's map (in whatever order they finish); the rows wait until the run's
-    consumer, which sees the batches in file order, asks for them with take(recs)."""
+class Collector(analyses.Collector):
+    """The sink of a run: (tracts, found, totals) per batch; the consumer hands every batch back as rows with add_batch."""
 
     def __init__(self, unit: str, block: int = DEFAULT_BLOCK, min_hits: int = DEFAULT_MIN_HITS, gap: int = DEFAULT_GAP,
                  min_blocks: int = DEFAULT_MIN_BLOCKS, max_tracts: int = DEFAULT_MAX_TRACTS, edge: int = DEFAULT_EDGE):
+        super().__init__()                # (_file_rows: input path -> (tract rows, read rows), each file's in read order)
         self.spec = TractSpec(unit, block, min_hits, gap, min_blocks, max_tracts, self)
         self.unit, self.edge = self.spec.unit, int(edge)
         self.classes = dict.fromkeys(CLASSES, 0)
-        self._file_rows = {}              # input path -> (tract rows, read rows), each file's in read order
-        self._pending = {}
-        self._lock = threading.Lock()
 
-    def __call__(self, recs, tracts, found, totals):
+    def __call__(self, recs, tracts, found, totals):       # (no scan results in front: the map does not hang on them)
         with self._lock:
             self._pending[id(recs)] = (tracts, found, totals)
-
-    def take(self, recs):
-        """(tracts, found, totals) of a batch the consumer has in hand."""
-        with self._lock:
-            return self._pending.pop(id(recs))
 
     def add_batch(self, path, file_name: str, ids, lens, tracts, found):
         """The rows of one batch of input file `path`, in read order (the file's consumer calls it: its batches arrive in file order;
@@ -147,19 +138,13 @@ READ_HEADER = ["file", "readID", "length", "n_C", "n_G", "class", "truncated"]
 def write_tracts_csv(path, rows):
     """tracts.csv: one row per tract; strand C = the motif as given, G = its reverse complement; [begin, end) in bases of the read as
     stored.  Of a read with more tracts on a strand than the map keeps, the first ones."""
-    with open(path, "w", newline="") as f:
-        w = csv.writer(f)
-        w.writerow(TRACT_HEADER)
-        w.writerows(rows)
+    write_csv(path, TRACT_HEADER, rows)
 
 
 def write_reads_csv(path, rows):
     """tract_reads.csv: one row per read with at least one tract; n_C / n_G are the true numbers of tracts, truncated = 1 where a
     strand has more of them than tracts.csv lists."""
-    with open(path, "w", newline="") as f:
-        w = csv.writer(f)
-        w.writerow(READ_HEADER)
-        w.writerows(rows)
+    write_csv(path, READ_HEADER, rows)
 
 
 def summary(unit: str, classes: dict) -> list[str]:
@@ -170,3 +155,24 @@ def summary(unit: str, classes: dict) -> list[str]:
 def log_summary(unit: str, classes: dict):
     for line in summary(unit, classes):
         logging.info("%s", line)
+
+
+# ---- the CLI's side (main.ANALYSES): one collector for the whole run, the map with the first k's job
+FLAG = "tracts"
+POWER_NOTE = "the map looks for {unit}"
+
+
+def cli_check(args, root: str):
+    return check(root, args.tractblock, args.tractminhits, args.tractgap, args.tractminblocks, DEFAULT_MAX_TRACTS, args.tractedge)
+
+
+def cli_collector(args, unit: str, slide=None):
+    return Collector(unit, args.tractblock, args.tractminhits, args.tractgap, args.tractminblocks, DEFAULT_MAX_TRACTS, args.tractedge)
+
+
+def finish_and_write(args, k, col, filenames, engines):
+    tract_rows, read_rows = col.rows_in_order(filenames)
+    write_tracts_csv(f"{args.outputDir}/tracts.csv", tract_rows)
+    write_reads_csv(f"{args.outputDir}/tract_reads.csv", read_rows)
+    yield f"tract map: {args.outputDir}/tracts.csv, {args.outputDir}/tract_reads.csv"
+    yield from summary(col.unit, col.classes)

@@ -16,17 +16,33 @@ import logging
 
 import numpy as np
 
+from . import analyses
+from .analyses import BoundaryAnalysis
+
 LETTERS = "ACTG"                  # the packed batch's 2-bit codes
 MAX_UNIT = 32
 DEFAULT_BIN, DEFAULT_BINS = 500, 40
 
 
-class VariantSpec:
+class VariantSpec(BoundaryAnalysis):
     """What batch.Job(variants=...) carries: the primitive unit, the bin width and count of the profile, and `sink(recs, res,
-    counts, profile)`, called by the worker that scanned a batch while that batch is still resident."""
+    counts, profile)`, called by the worker that scanned a batch while that batch is still resident.  The tract of a read is
+    [trimfirst, boundary) of its telomere-first string (tract_bounds); the profile is one answer per call."""
+
+    per_batch = 1
 
     def __init__(self, unit: str, bin: int = DEFAULT_BIN, n_bins: int = DEFAULT_BINS, sink=None):
         self.unit, self.bin, self.n_bins, self.sink = primitive_root(unit.upper()), int(bin), int(n_bins), sink
+
+    def regions(self, res, prm):
+        return tract_bounds(res, *self.scan_geometry(prm))
+
+    def empty(self, n):
+        cols = 2 + 4 * len(self.unit)
+        return np.zeros((n, cols), np.uint32), np.zeros((self.n_bins, cols), np.int64)
+
+    def launch(self, eng, slot, tails, begin, end):
+        return eng.variant_census(slot, self.unit, tails, begin, end, self.bin, self.n_bins)
 
 
 def unit_code(unit: str) -> tuple[int, int]:
@@ -80,13 +96,12 @@ def tract_bounds(res, trimfirst: int, slide: int, maxlen: int):
     return begin, end
 
 
-class Collector:
+class Collector(analyses.Collector):
     """The sink of one k of a run.  The workers hand it every batch's census (in whatever order they finish): the profile is added
-    up at once -- exact integers, the order does not matter -- and the rows wait until the run's consumer, which sees the batches
-    in file order, asks for them with take(recs)."""
+    up at once -- exact integers, the order does not matter -- and the rows, (begin, end, counts), wait for the run's consumer."""
 
     def __init__(self, unit: str, bin: int = DEFAULT_BIN, n_bins: int = DEFAULT_BINS, trimfirst: int = 100, slide: int = 6, maxlen: int = 20000):
-        import threading
+        super().__init__()
         self.spec = VariantSpec(unit, bin, n_bins, self)
         self.unit = self.spec.unit
         self.trimfirst, self.slide, self.maxlen = int(trimfirst), int(slide), int(maxlen)
@@ -94,9 +109,6 @@ class Collector:
         self.profile = np.zeros((self.spec.n_bins, cols), np.int64)
         self.total = np.zeros(cols, np.int64)
         self.n_tracts = 0
-        self._pending = {}
-        self._file_rows = {}
-        self._lock = threading.Lock()
 
     def __call__(self, recs, res, counts, profile):
         begin, end = tract_bounds(res, self.trimfirst, self.slide, self.maxlen)
@@ -106,19 +118,9 @@ class Collector:
             self.n_tracts += int((end > 0).sum())
             self._pending[id(recs)] = (begin, end, counts)
 
-    def add_file_rows(self, path, rows):
-        """The rows of one input file, in read order: (file, readID, tail, begin, end, counts row) each."""
-        with self._lock:
-            self._file_rows.setdefault(path, []).extend(rows)
-
-    def rows_in_order(self, paths):
-        for p in paths:
-            yield from self._file_rows.get(p, [])
-
-    def take(self, recs):
-        """(begin, end, counts) of a batch the consumer has in hand."""
-        with self._lock:
-            return self._pending.pop(id(recs))
+    def keep_row(self, out, i, file, rid, tail, telo, length):
+        begin, end, counts = out
+        return file, rid, tail, int(begin[i]), int(end[i]), counts[i]
 
 
 def read_row(unit: str, filename: str, read_id: str, tail: int, begin: int, end: int, row):
@@ -162,6 +164,32 @@ def summary(unit: str, total, n_reads: int, top: int = 5) -> list[str]:
             f"  variant (one substituted letter): {sum(cls)} positions, {share(sum(cls)):.2f}%",
             f"  top classes: {tops}",
             f"  other (indels, several changes, not ACGT): {other} positions, {share(other):.2f}%"]
+
+
+# ---- the CLI's side (main.ANALYSES)
+FLAG = "variants"
+POWER_NOTE = "the census counts against {unit}"
+
+
+def cli_check(args, root: str):
+    from . import hiplib
+    lo, hi = hiplib.VARIANT_BIN_RANGE
+    if not (2 <= len(root) <= hiplib.VARIANT_MAX_UNIT) or not (lo <= args.variantbin <= hi) or not (1 <= args.variantbins <= hiplib.VARIANT_MAX_BINS):
+        return f"a motif whose root has 2..{hiplib.VARIANT_MAX_UNIT} letters, --variantbin {lo}..{hi} and --variantbins 1..{hiplib.VARIANT_MAX_BINS}"
+    return None
+
+
+def cli_collector(args, unit: str, slide: int):
+    return Collector(unit, args.variantbin, args.variantbins, args.trimfirst, slide, args.maxlengthtelo)
+
+
+def finish_and_write(args, k, col, filenames, engines):
+    """The two files of one k; yields the log lines."""
+    names = f"{args.outputDir}/variants_{k}.csv", f"{args.outputDir}/variant_profile_{k}.csv"
+    write_reads_csv(names[0], col.unit, col.rows_in_order(filenames))
+    write_profile_csv(names[1], col.unit, col.profile, col.spec.bin)
+    yield f"variant repeats (k = {k}): {names[0]}, {names[1]}"
+    yield from summary(col.unit, col.total, col.n_tracts)
 
 
 def log_summary(unit: str, total, n_reads: int):
