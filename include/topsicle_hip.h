@@ -520,7 +520,8 @@ int  tps_kernel_time_ms(tps_ctx* ctx, int32_t* n_launches, double* total_ms, dou
 int  tps_kernel_time_reset(tps_ctx* ctx);
 /* Diagnostics and tests only (ABI 4).  The library reads NO environment variables: what experiments and tests need to steer is
  * set per context through this call -- "event_stride" (time every n-th launch; default 1), "no_events", "force_generic" (the
- * generic kernel instead of the fused tiles), "spans_per_tile", "force_pair", "so_order", "wpg" (csrc/tps_plan.h: PlanKnobs), "stamps"
+ * generic kernel instead of the fused tiles), "spans_per_tile", "force_pair", "so_order", "wpg" (csrc/tps_plan.h: PlanKnobs), "lc_lds"
+ * (0 = the default kernels write their change-point candidate sums off-chip like every other kernel; on by default: PlanKnobs::lc_lds), "stamps"
  * (per-read phase clocks; only a -DTPS_STAMPS build writes them), "file_order" (wave slot i takes read i: switches
  * tps::plan_dispatch_order off, which otherwise starts the longest reads of a batch first), "no_stride" (a slide that is a multiple of a
  * fused kernel's slide keeps the generic kernel instead of running that kernel and keeping every m-th window: tps::stride_base), "no_inline_rows" (such a scan at twice the base

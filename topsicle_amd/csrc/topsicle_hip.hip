@@ -479,7 +479,7 @@ struct tps_ctx {
     std::vector<EventPair> ev_pool;
     size_t ev_used = 0;      // next free event pair (never rewound: re-recording old events was measured slow)
     size_t ev_base = 0;      // first pair of the current measurement window
-    tps::PlanKnobs knobs{};           // tps_ctx_debug_option: tests / diagnostics only; the library reads no environment
+    tps::PlanKnobs knobs = tps::product_knobs();     // tps_ctx_debug_option: tests / diagnostics only; the library reads no environment
     int want_stamps = 0;
     int no_events = 0;
     int no_inline_rows = 0;           // tps_ctx_debug_option "no_inline_rows": strided scans at twice the base slide copy their raw rows like the others (A/B of ScanArgs::raw_m)
@@ -2195,6 +2195,7 @@ int tps_ctx_debug_option(tps_ctx* c, const char* key, int64_t value) {
     else if (k == "force_pair") c->knobs.force_pair = value != 0;
     else if (k == "so_order") c->knobs.so_order = (int)value;
     else if (k == "wpg") c->knobs.wpg = (int)value;
+    else if (k == "lc_lds") c->knobs.lc_lds = value != 0;       // 0: the default kernels' candidate sums off-chip, as every other kernel's (A/B, tests)
     else if (k == "stamps") c->want_stamps = value != 0;
     else if (k == "file_order") c->file_order = value != 0;
     else if (k == "no_stride") c->no_stride = value != 0;
@@ -2203,7 +2204,7 @@ int tps_ctx_debug_option(tps_ctx* c, const char* key, int64_t value) {
         if (value < 0 || value > 255) return fail(TPS_E_ARG, "poison must be 0 (off) or a fill byte 1..255");
         c->poison = (int)value;
     }
-    else return fail(TPS_E_ARG, "unknown debug option '%s' (event_stride, no_events, force_generic, spans_per_tile, force_pair, so_order, wpg, stamps, file_order, no_stride, no_inline_rows, poison)", key);
+    else return fail(TPS_E_ARG, "unknown debug option '%s' (event_stride, no_events, force_generic, spans_per_tile, force_pair, so_order, wpg, lc_lds, stamps, file_order, no_stride, no_inline_rows, poison)", key);
     drop_plans(c);
     return TPS_OK;
 }

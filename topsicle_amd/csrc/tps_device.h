@@ -130,6 +130,8 @@ struct ScanArgs {
     int32_t xt_own;              // xt_alias kernels whose fallback tile may run (non-ACGT letters in the batch, TPS_NO_SO_FAST): XT gets its own words
     int32_t pair16;              // k = 5 tables without self-overlap, sums only (kernels _s*q): BOTH tables as 16-bit pattern masks -- the pair table of
                                  // 4^6 (k+1)-mers is 8 KB instead of 16, shared by the 8 waves of a workgroup (lut16 is set as well)
+    int32_t lc_lds;              // default kernels, jump >= 4: the candidate sums stay in the wave's LDS slice as 16-bit entries (Lds::lcl, carve_fused);
+                                 // lc_global is 0 then and the host allocates no lc_scratch (plan_geometry_core decides; PlanKnobs::lc_lds)
 };
 
 struct BinsegArgs {
@@ -170,6 +172,7 @@ struct Lds {
     uint32_t* Tot;     // per span: matches in the span, then exclusive prefix over spans
     uint32_t* row;     // WIN_U * NT dwords: one group of window sums, scanned in place
     uint32_t* misc;
+    uint16_t* lcl;     // ScanArgs::lc_lds: the read's candidate sums, low 16 bits each (lc_lds_entries(slide) of them); nullptr otherwise
 };
 constexpr int XLANES = NT + 16;                  // most lanes an exchange row can hold: NT + halo lanes read past the tile end
 TPS_HD int64_t xchg_dw(const ScanArgs& a) {      // fused path: XPC (9 words per lane), XF, XT (xt_alias 2: both live elsewhere)
@@ -201,6 +204,7 @@ TPS_DEV Lds carve(uint32_t* base, uint32_t* lut, const ScanArgs& a) {
     l.Tot = p;  p += a.tot_dw;
     l.row = p;  p += row_dw(a);
     l.misc = p;
+    l.lcl = nullptr;
     l.G = l.blk;
     l.Gp = l.G + a.nblk_cap;
     l.C0 = (uint16_t*)(l.Gp + a.nblk_cap);
@@ -1171,6 +1175,9 @@ struct TileGeo {
     static constexpr int SEQ = SEQ_TILE < 144 ? 144 : SEQ_TILE;       // ... and never less than step 1's two heads of 1000 bases need (slide 3: 112 for the tile)
 };
 constexpr bool tile_full_default(int s) { return s >= 1; }
+// 16-bit candidate sums a default kernel can keep per wave (ScanArgs::lc_lds): what a tile's staged bases (seq_dw dwords) leave of the
+// old row[] (carve_fused: 9 NT dwords).  The plan calls it with fused_seq_dw(slide), carve_fused checks it against its own SEQ.
+constexpr int lc_lds_entries(int seq_dw) { return 2 * (9 * NT - seq_dw); }
 
 // LDS slice of a wave in the fused kernels: everything whose size is known at compile time comes first, at
 // compile-time offsets from the slice base (one SGPR for all of it, offsets folded into the DS instructions);
@@ -1178,7 +1185,7 @@ constexpr bool tile_full_default(int s) { return s >= 1; }
 // The exchange region holds no XF / XT arrays (ScanArgs::xt_alias == 2, every fused kernel): tile_lc_s and tile_pp_s keep the
 // lanes' totals in the pad words of their 9-word rows; the fallback tile (tile_fused_s) gets both behind everything else whenever it
 // can run (ScanArgs::xt_own).
-template <int S, bool FULL>
+template <int S, bool FULL, bool LCF = false>
 TPS_DEV Lds carve_fused(uint32_t* base, uint32_t* lut, const ScanArgs& a) {
     constexpr int BLK = 9 * NT, ROW = NT * Geo<S>::B + NT, SEQ = TileGeo<S, FULL>::SEQ;
     const int VAL = a.val_on ? ((SEQ + 4 + 3) / 4) * 2 : 0;
@@ -1200,7 +1207,27 @@ TPS_DEV Lds carve_fused(uint32_t* base, uint32_t* lut, const ScanArgs& a) {
     l.misc = l.row + ROW;
     l.Tot = l.misc + MISC_DW;
     uint32_t* p = l.Tot + 4;                   // 16-byte aligned: BLK, ROW, MISC_DW are multiples of 4 dwords
-    if (a.seq_alias) {
+    l.lcl = nullptr;
+    bool lc_lds = false;
+    if constexpr (LCF) lc_lds = a.lc_lds != 0;     // (LCF: the default family -- the plan sets the flag for no other kernel)
+    if (lc_lds) {
+        // The default kernels with resident candidate sums: [ XPC = row[] : BLK ][ seq2 : SEQ ][ Lc : ROW - SEQ ][ misc ][ Tot ] -- the
+        // slice's size as before.  Every tile of these kernels is a tile_lc_s<.., CD = 0>: its first phase writes XPC and the pad words
+        // of XPC's rows and keeps XS in registers, its window phase reads all it needs of XPC into registers at its start, and only
+        // then are row[] and its pad words written and read back (the lane's own row, the tile total); the next tile's first phase
+        // comes behind that read and a TPS_SYNC().  A wave's LDS operations execute in program order (the emulation runs the phases
+        // one after the other), so row[] lives on XPC's words, the staged bases get words nothing else writes, and what is left of
+        // the old row[] holds the read's candidate sums.  What else uses the region in front of the bases still fits BLK dwords:
+        static_assert(ROW == BLK, "row[] takes XPC's words");
+        static_assert(HIST_DW <= BLK && OCC_BASE_DW + 2 * OCC_SLOTS * 32 <= BLK && XS_DW <= BLK && 4 * NT <= BLK,
+                      "step 1's histograms and occurrence slots and the exact tournament's scratch in front of the staged bases");
+        static_assert(SEQ < ROW, "room for the candidate sums behind the staged bases");
+        static_assert(lc_lds_entries(SEQ) == 2 * (ROW - SEQ) && lc_lds_entries(SEQ) <= 16 * NT,
+                      "the entries the plan admits are the room the carve has; never more candidates than the prefilter takes (16 slots per lane)");
+        l.row = base;
+        l.seq2 = base + BLK;
+        l.lcl = (uint16_t*)(base + BLK + SEQ);
+    } else if (a.seq_alias) {
         l.seq2 = base + (BLK + ROW - SEQ);
     } else {
         l.seq2 = p;
@@ -2074,11 +2101,19 @@ TPS_DEV void tile_lc_s(const ScanArgs& a, const TileConst& tc, const Lds& l, int
             // on, which the descriptor drops, and reads its row at a clamped index.  No exec-masked region: both row reads are
             // issued before either store.  (Two bodies behind a uniform branch: as one, the compiler turns the jump > 8 case into
             // five selects that every jump pays.)
-            auto own_candidates = [&](auto bigj_) {
+            // Resident sums (ScanArgs::lc_lds): the same two values as 16-bit LDS entries, the low half of each (binseg_from_lc
+            // unwraps them).  No hardware bound stands behind an LDS store, so the lane's candidate index is cut at c_hi first: a
+            // candidate that is not the tile's goes to entry c_hi or c_hi + 1.  Those two receive garbage from any number of lanes;
+            // the next tile rewrites what it needs of them after this one (its first candidate is this tile's c_hi; a wave's LDS
+            // operations execute in order), behind the read's last tile and behind lc_cap nothing reads them -- the region holds
+            // lc_cap + 2 entries (plan_geometry_core).
+            auto own_candidates = [&](auto bigj_, auto lds_) {
+                constexpr bool LCL = decltype(lds_)::value != 0;
                 const uint32_t carry = (uint32_t)s_total + TPS_AT(lexc);
                 const uint32_t wa = (uint32_t)w0 + (uint32_t)(lane * B);
-                const uint32_t c = mulhi32(wa + tc.jump - 1u, tc.jump_magic);     // (div_jump without its jump = 1 case)
+                uint32_t c = mulhi32(wa + tc.jump - 1u, tc.jump_magic);     // (div_jump without its jump = 1 case)
                 const uint32_t f = c * tc.jump - wa, f2 = f + tc.jump;
+                if constexpr (LCL) c = c < c_hi ? c : c_hi;
                 uint32_t i1 = c, r1 = f;
                 if constexpr (decltype(bigj_)::value != 0) {
                     i1 = f < (uint32_t)B ? c : c_hi;
@@ -2087,11 +2122,20 @@ TPS_DEV void tile_lc_s(const ScanArgs& a, const TileConst& tc, const Lds& l, int
                 const uint32_t i2 = (f2 < (uint32_t)B ? c : c_hi) + 1u;
                 const uint32_t r2 = f2 < (uint32_t)B ? f2 : (uint32_t)(B - 1);
                 const uint32_t v1 = pr[r1], v2 = pr[r2];
-                g32_store_clamped(tc.lc_g, c_hi, i1, carry + v1);
-                g32_store_clamped(tc.lc_g, c_hi, i2, carry + v2);
+                if constexpr (LCL) {
+                    if (tid == 0) TPS_EMU_COUNT(15);
+                    lds16_store(l.lcl, i1, carry + v1);
+                    lds16_store(l.lcl, i2, carry + v2);
+                } else {
+                    g32_store_clamped(tc.lc_g, c_hi, i1, carry + v1);
+                    g32_store_clamped(tc.lc_g, c_hi, i2, carry + v2);
+                }
             };
-            if (tc.jump > (uint32_t)B) own_candidates(IntC<1>());       // (uniform)
-            else own_candidates(IntC<0>());
+            if (a.lc_lds) {                                                           // (uniform; CD == 0 && !M16: a default kernel)
+                if (tc.jump > (uint32_t)B) own_candidates(IntC<1>(), IntC<1>());
+                else own_candidates(IntC<0>(), IntC<1>());
+            } else if (tc.jump > (uint32_t)B) own_candidates(IntC<1>(), IntC<0>());   // (uniform)
+            else own_candidates(IntC<0>(), IntC<0>());
         }
     }
     TPS_SYNC();
@@ -2886,9 +2930,17 @@ TPS_DEV void binseg_wg(const ST* S, int n, int jump, int min_size, int n_pattern
 // Fused Binseg from the candidate left sums Lc[c] = sum_{w < c*jump} S_w (c = 1 .. (n-1)/jump) and
 // the total T: float64 scores, wave arg-max; if more than one candidate lies within float noise of
 // the best score the exact integer tournament re-reads S_w from HBM (rare).
-template <typename ST>
+// LCL (the default family) with ScanArgs::lc_lds: the sums are 16-bit entries of the wave's LDS slice, the low half of each (l.lcl).
+// A lane rebuilds its own 32-bit sums by unwrapping along its slots, lc_j = lc_(j-1) + ((h_j - lc_(j-1)) & 0xFFFF) from lc_(-1) = 0:
+// exact because the lane's first sum and the increase between two of its slots, 64 jump windows, stay below 2^16 -- the plan
+// sets the flag only where (c_min + 64) jump max S_w < 65 536 (plan_geometry_core).  Lane t reads entries c0 + 64 j: consecutive
+// lanes consecutive halves, conflict-free.  Nothing the wave stored off-chip is read back then, so the fence in front of the
+// wave's own S_w stands here, before the exact tournament, and not in scan_read.
+template <typename ST, bool LCL = false>
 TPS_DEV void binseg_from_lc(const ScanArgs& a, const Lds& l, uint64_t lc_g, const ST* S_global, int n, uint64_t tot, int jump,
                             int min_size, int n_patterns, uint32_t* misc, uint32_t* xs, int& bkp, double& gain, bool& tie) {
+    bool lc_lds = false;
+    if constexpr (LCL) lc_lds = a.lc_lds != 0;         // (uniform)
     const int ncand = (n - 1) / jump;              // candidates b = c*jump, 1 <= c <= ncand  (b < n)
     // Per lane: the best candidate as a FRACTION (num = D^2, den = b (n - b)); candidates are compared by
     // cross-multiplication, so the f64 division happens once per lane instead of once per candidate.
@@ -2939,9 +2991,11 @@ TPS_DEV void binseg_from_lc(const ScanArgs& a, const Lds& l, uint64_t lc_g, cons
     if (prefilter) {
         // (one phase per route, each with its own laundered lane id: written as two branches of one phase the slots' shared index
         // arithmetic is hoisted in front of the branch, used or not)
-        auto prefilter_phase = [&](auto intd_) {
+        auto prefilter_phase = [&](auto intd_, auto lds_) {
         TPS_PHASE {
             constexpr bool INTD = decltype(intd_)::value != 0;
+            constexpr bool LDSC = decltype(lds_)::value != 0;     // the sums are the resident 16-bit entries
+            uint32_t lcp = 0;                             // LDSC: the lane's sum of the slot before (unwrapping)
             float &p_s1 = TPS_AT(p_s1_), &p_s2 = TPS_AT(p_s2_);
             uint32_t& p_lc = TPS_AT(p_lc_);
             p_s1 = -1.0f; p_s2 = -1.0f; p_lc = 0;
@@ -2976,6 +3030,21 @@ TPS_DEV void binseg_from_lc(const ScanArgs& a, const Lds& l, uint64_t lc_g, cons
             auto group = [&](int g, auto checked_) {
                 constexpr bool CHECKED = decltype(checked_)::value != 0;
                 uint32_t lcv[4];
+                if constexpr (LDSC) {
+                    // (a lane past c_max reads entry c_max: in bounds, its score is replaced below and none of its later slots counts)
+                    TPS_UNROLL
+                    for (int i = 0; i < 4; ++i) {
+                        const uint32_t ci = (uint32_t)c0 + NT * (uint32_t)(4 * g + i);
+                        if constexpr (CHECKED) lcv[i] = lds16_load(l.lcl, ci < (uint32_t)c_max ? ci : (uint32_t)c_max);
+                        else lcv[i] = lds16_load(l.lcl + NT * (4 * g + i), (uint32_t)c0);       // (the slot's constant goes into the instruction's offset)
+                    }
+                    TPS_UNROLL
+                    for (int i = 0; i < 4; ++i) {
+                        lcp += (lcv[i] - lcp) & 0xFFFFu;
+                        slot(4 * g + i, lcp, checked_);
+                    }
+                    return;
+                }
                 TPS_UNROLL
                 for (int i = 0; i < 4; ++i) {
                     const uint32_t joff = 4u * NT * (uint32_t)(4 * g + i);
@@ -2999,11 +3068,16 @@ TPS_DEV void binseg_from_lc(const ScanArgs& a, const Lds& l, uint64_t lc_g, cons
             TPS_AT(p_c_) = p_j >= 0 ? c0 + p_j * NT : -1;
         }
         };
-        if (int_d) {
-            prefilter_phase(IntC<1>());
+        if (!int_d) TPS_EMU_COUNT(11);
+        if (lc_lds) {                              // (false at compile time unless LCL)
+            if constexpr (LCL) {
+                if (int_d) prefilter_phase(IntC<1>(), IntC<1>());
+                else prefilter_phase(IntC<0>(), IntC<1>());
+            }
+        } else if (int_d) {
+            prefilter_phase(IntC<1>(), IntC<0>());
         } else {
-            TPS_EMU_COUNT(11);
-            prefilter_phase(IntC<0>());
+            prefilter_phase(IntC<0>(), IntC<0>());
         }
         float m32;
         {
@@ -3074,6 +3148,7 @@ TPS_DEV void binseg_from_lc(const ScanArgs& a, const Lds& l, uint64_t lc_g, cons
                 if (TPS_AT(p_c_) >= 0 && TPS_AT(p_s1_) >= thr32) offer(TPS_AT(p_c_), TPS_AT(p_lc_));
             } else {
                 // (no prefilter: more than 1 024 candidates, or products of D past 2^53)
+                // (resident sums never come here: the plan sets lc_lds only where the prefilter runs, plan_geometry_core)
                 TPS_NOVEC
                 for (int c = c_min + tid; c <= c_max; c += NT) offer(c, g32_load(lc_g, (uint32_t)c));
             }
@@ -3113,6 +3188,7 @@ TPS_DEV void binseg_from_lc(const ScanArgs& a, const Lds& l, uint64_t lc_g, cons
     tie = ntie > 1u;
     if (ntie > 1u) {                               // float noise cannot separate them: exact integers decide
         TPS_EMU_COUNT(4);
+        if (lc_lds) TPS_FENCE_WG();                // this wave's S_w stores before its own loads (off-chip sums: scan_read's fence)
         Cand ex = binseg_exact_wg(S_global, n, jump, min_size, xs);
         bkp = ex.b;
         gain = ex.b < 0 ? 0.0 : gain_from((int64_t)ex.d, ex.den, n, n_patterns);
@@ -3136,7 +3212,8 @@ TPS_DEV void scan_read(const ScanArgs& a, int64_t r, uint32_t* lds_base, uint32_
     constexpr bool M16K = SV != 0 && SO && !RAW;       // sums-only kernels of self-overlap tables: 16-bit table, XT aliased (lut16 / xt_alias)
     constexpr bool F16K = SV != 0 && SO && RAW && DCLASS == 3;     // raw rows of a big self-overlap table: 16-bit field-index table (_s*sorh)
     constexpr bool P16K = SV != 0 && !SO && !RAW && PAIR && DCLASS == 4;      // pair-table kernels of k = 5 tables: 16-bit pair + single table (_s*q)
-    Lds l_ = SV ? carve_fused<SV ? SV : 5, FULL>(lds_base, lut, a) : carve(lds_base, lut, a);
+    constexpr bool LCF = SV != 0 && !SO && !RAW && !P16K;      // the default family: the candidate sums may be resident (ScanArgs::lc_lds)
+    Lds l_ = SV ? carve_fused<SV ? SV : 5, FULL, LCF>(lds_base, lut, a) : carve(lds_base, lut, a);
     if constexpr (P16K) l_.lshift = LUT_M16;
     const Lds l = l_;
     const PatInfo& pat = a.pat;
@@ -3531,10 +3608,14 @@ TPS_DEV void scan_read(const ScanArgs& a, int64_t r, uint32_t* lds_base, uint32_
         int bkp;
         double gain;
         bool tie = false;
-        TPS_FENCE_WG();                            // this wave's S_w / off-chip candidate-sum stores before its own loads
+        // this wave's S_w / off-chip candidate-sum stores before its own loads -- with resident sums nothing in the common finish
+        // reads what the wave stored: the fence moves to the exact tournament, the one consumer of the wave's own S_w (binseg_from_lc)
+        bool lc_lds = false;
+        if constexpr (LCF) lc_lds = a.lc_lds != 0;
+        if (!lc_lds) TPS_FENCE_WG();
         const uint64_t lc_g = a.lc_global ? (uint64_t)(uintptr_t)(a.lc_scratch + r * (int64_t)a.lc_stride) : 0ull;
         if constexpr (SV != 0)
-            binseg_from_lc(a, l, lc_g, (const uint16_t*)(a.sums16 + (a.win_off16 ? a.win_off16[r] : 0)), n_win, s_total, prm.jump, prm.min_size, pat.P,
+            binseg_from_lc<uint16_t, LCF>(a, l, lc_g, (const uint16_t*)(a.sums16 + (a.win_off16 ? a.win_off16[r] : 0)), n_win, s_total, prm.jump, prm.min_size, pat.P,
                            l.misc, l.blk, bkp, gain, tie);
         else
             binseg_from_lc(a, l, lc_g, (const int32_t*)(a.sums + (a.win_off ? a.win_off[r] : 0)), n_win, s_total, prm.jump, prm.min_size, pat.P,

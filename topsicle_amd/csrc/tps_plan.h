@@ -210,7 +210,7 @@ inline std::string build_patterns(const char* pats, int P, int k, std::vector<ui
 }
 
 // = TileGeo<S, true>::SEQ (tps_device.h): LDS words of a fused tile's packed bases
-inline int fused_seq_dw(int slide) {
+constexpr int fused_seq_dw(int slide) {
     const int bases = NT * 8 * slide + 13 + 15;
     const int nq = (63 + bases + 63) / 64;
     const int seq = SEQ_LEAD + 4 * nq + 4;
@@ -257,7 +257,20 @@ struct PlanKnobs {
     int force_pair = 0;       // keep the pair table where it costs a resident workgroup (the emulation's slices are bigger than the device's)
     int so_order = 0;         // 2: the raw-row kernels of self-overlap tables try the chain-free tile first for EVERY tile (round 3's order)
     int wpg = 0;              // 4 or 8: waves per workgroup whatever plan_wpg would pick (A/B of the workgroup shapes)
+    int lc_lds = 0;           // 1: the default kernels keep the candidate sums in LDS where plan_geometry_core can (ScanArgs::lc_lds).  The one knob
+                              // the product library turns ON (product_knobs; its debug option "lc_lds" = 0 gives the off-chip layout back)
 };
+// the knobs of the library's contexts
+inline PlanKnobs product_knobs() {
+    PlanKnobs kn;
+    kn.lc_lds = 1;
+    return kn;
+}
+// fused_seq_dw is what the kernels carve by: the resident candidate sums (lc_lds_entries, tps_device.h) have no hardware bound behind them
+template <int S> constexpr bool fused_seq_dw_is_tilegeo() { return fused_seq_dw(S) == TileGeo<S, true>::SEQ; }
+static_assert(fused_seq_dw_is_tilegeo<3>() && fused_seq_dw_is_tilegeo<4>() && fused_seq_dw_is_tilegeo<5>() && fused_seq_dw_is_tilegeo<6>() &&
+              fused_seq_dw_is_tilegeo<7>() && fused_seq_dw_is_tilegeo<8>() && fused_seq_dw_is_tilegeo<9>() && fused_seq_dw_is_tilegeo<10>() &&
+              fused_seq_dw_is_tilegeo<11>() && fused_seq_dw_is_tilegeo<12>(), "fused_seq_dw(slide) == TileGeo<slide, true>::SEQ for every fused slide");
 
 // Geometry of one scan: fills variant, lut_n, lw/q/r, span_dw, blk_log2, spans_per_tile, nblk_cap,
 // rec_rs, seq_dw, head_dw, tot_dw, blk_dw, lc_cap, jump_magic.  budget_dw = LDS dwords one workgroup (WPG waves +
@@ -335,7 +348,7 @@ inline std::string plan_geometry_core(ScanArgs& a, const tps_params& prm, int k,
                        (P <= 15 || p16_ok) && a.q >= 8 && sw16_ok &&
                        a.q / 8 + 2 < (XLANES - NT) && max_period <= std::min(prm.slide, 6) &&
                        2 * a.head_dw <= fused_seq_dw(prm.slide);   // the two step-1 heads fit the tile buffer (TileGeo::SEQ)
-    a.tw = 0; a.pair_n = 0; a.lc_global = 0; a.lc_stride = 0; a.pp_d = -1; a.so_fast = 0; a.seq_alias = 0; a.lut_fields = 0; a.tile_full = 0;
+    a.tw = 0; a.pair_n = 0; a.lc_global = 0; a.lc_lds = 0; a.lc_stride = 0; a.pp_d = -1; a.so_fast = 0; a.seq_alias = 0; a.lut_fields = 0; a.tile_full = 0;
     a.lut16 = 0; a.xt_alias = 0; a.xt_own = 0; a.pair16 = 0;
     if (fused) {
         // per-pattern tiles (tile_pp_s): one-hot 2-bit fields per pattern need distinct k-mers, raw rows of at most 14 bytes
@@ -393,8 +406,9 @@ inline std::string plan_geometry_core(ScanArgs& a, const tps_params& prm, int k,
         // The candidates' left sums live off-chip (L2-resident scratch, written once and read once by the same wave) as
         // absolute 32-bit sums: 4 bytes per candidate instead of the 2 of the tile-relative 16-bit form, but the
         // change-point step then needs no per-candidate tile lookup (mul, mulhi, LDS read, add) and no Tc array in LDS.
-        // (The tile-relative 16-bit and the in-LDS layouts of rounds 1 - 2 are gone, switches and code: this is the one layout
-        // every kernel, the generic one included, writes and the change-point step reads.)
+        // (The tile-relative 16-bit and the in-LDS layouts of rounds 1 - 2 are gone, switches and code: this is the layout every
+        // kernel, the generic one included, can write and the change-point step read -- and since round 23 the default kernels
+        // have a resident one beside it, ScanArgs::lc_lds, decided further down.)
         // Round 4, the 40 MB this round trip adds to a config-2 launch's 128 MB at the memory side -- three ways around it, measured
         // (A/B on one box each, us per launch) and dropped:  (i) the block indexed by the HARDWARE WAVE SLOT (s_getreg HW_ID / XCC_ID:
         // 12 MB rewritten in place launch after launch instead of 20 MB per batch): 55.3 -> 54.4, config 4's sample 67.7 -> 66.7 -- but
@@ -443,13 +457,35 @@ inline std::string plan_geometry_core(ScanArgs& a, const tps_params& prm, int k,
             if (keep16) { a.lut16 = 0; a.pair16 = 0; }        // (without: the 32-bit single table)
             if (with_pair >= 5 * WPG || waves_per_cu(WPG) <= with_pair) { a.pair_n = keep; if (keep16) { a.pair16 = 1; a.lut16 = 1; } }
         }
+        // The default kernels, round 23: the sums stay ON-CHIP after all -- not in LDS of their own (round 2: that cost the sixth
+        // workgroup per CU) but in the words of the wave's slice that the lane-contiguous tile left idle: row[] and XPC are never
+        // live at the same time there, so row[] lies on XPC, the staged bases take the head of the old row[] and its other
+        // ROW - SEQ dwords hold the sums as 16-bit entries, the low half of each (carve_fused; the change-point step unwraps them
+        // along a lane's slots, binseg_from_lc).  lds_dwords() does not change by a byte, and no lc_scratch is allocated.  Only where
+        //  * the scan is one of the default kernels (no self-overlap, sums only, not the 16-bit pair-table kernels _s*q),
+        //  * every lane stores its own candidates (tile_lc_s: jump >= 4),
+        //  * lc_cap + 2 entries fit (a tile's lanes that hold no candidate of it write to the two entries behind its last) -- at most 864
+        //    entries at any slide, below the 1 024 candidates the change point's prefilter takes, and n < 2^21: the prefilter always runs
+        //    for such a scan and is the only reader of the resident entries (binseg_from_lc),
+        //  * and unwrapping is exact: a lane's first sum covers at most (c_min + 63) jump windows, the step between two of its slots
+        //    64 jump; with distinct k-mers every start position matches at most one pattern, so S_w <= lw + P (sw_max above allows
+        //    for duplicates and is too loose for this), hence (c_min + 64) jump (lw + P) < 2^16.
+        // Everything else keeps the off-chip layout.
+        if (kn.lc_lds && a.pat.so_mask == 0 && !(prm.flags & TPS_F_STORE_RAW) && !a.pair16 && jump >= 4 && a.pat.dup_mask == 0) {
+            const int64_t c_min = std::max<int64_t>(((int64_t)std::max(prm.min_size, 1) + jump - 1) / jump, 1);
+            if ((int64_t)a.lc_cap + 2 <= lc_lds_entries(fused_seq_dw(prm.slide)) && (c_min + 64) * (int64_t)jump * ((int64_t)a.lw + P) < 65536) {
+                a.lc_lds = 1;
+                a.lc_global = 0;
+                a.lc_stride = 0;
+            }
+        }
         if (wg_lds_dwords(a) <= budget_dw) return "";
         // does not fit.  maxlengthtelo cannot bring a scan here: the fused plan's LDS is the lookup tables and the tile buffers
         // of compile-time size (the step-1 heads share the tile buffer, see `fused` above), and the candidate sums live off-chip
         // (lc_scratch) -- variant, tw and the LDS bytes are the same from 3 301 to 500 000 windows per read
         // (tests/test_long_series.py).  What is left is the budget itself: a caller or a device that offers less LDS per
         // workgroup than these fixed sizes add up to.  Then the generic kernel, whose tile size adapts, takes over
-        a.tw = 0; a.pair_n = 0; a.lc_global = 0; a.lc_stride = 0; a.pp_d = -1; a.so_fast = 0; a.seq_alias = 0; a.lut_fields = 0;
+        a.tw = 0; a.pair_n = 0; a.lc_global = 0; a.lc_lds = 0; a.lc_stride = 0; a.pp_d = -1; a.so_fast = 0; a.seq_alias = 0; a.lut_fields = 0;
         a.lut16 = 0; a.xt_alias = 0; a.xt_own = 0; a.pair16 = 0;
     }
     a.variant = 0;

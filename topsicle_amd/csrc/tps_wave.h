@@ -109,7 +109,8 @@ constexpr int NT = 64;                            // lanes that cooperate on one
 // finished by the one lane whose candidate passed the prefilter, 9 = ... by the float64 stage of every lane and the wave reduction,
 // 10 = prefilters that found a lane with two candidates inside the margin (crowded), 11 = prefilters run on the float64 D route,
 // the route a read's step 1 took: 12 = trc_decide_pairs, 13 = the packed counts (trc_count_packed; the device's
-// trc_decide_packed among them), 14 = the histograms (trc_count_thread)
+// trc_decide_packed among them), 14 = the histograms (trc_count_thread); 15 = sums tiles that keep their candidates in LDS
+// (ScanArgs::lc_lds: a subset of 7)
 #ifdef TPS_EMU
 constexpr int EMU_COUNTERS = 16;
 inline int& emu_counter(int i) { static int c[EMU_COUNTERS] = {0}; return c[i]; }
@@ -465,6 +466,10 @@ TPS_DEV u32x4 lds_load16(const uint32_t* p) { return *(const u32x4*)p; }
 TPS_DEV void lds_store16(uint32_t* p, const u32x4& v) { *(u32x4*)p = v; }
 TPS_DEV void lds_store8(uint32_t* p, const u32x2& v) { *(u32x2*)p = v; }
 #endif
+// 16-bit LDS entries (ds_write_b16 of the low half / ds_read_u16, zero-extended): the resident candidate sums of the default kernels.
+// No hardware bound stands behind these: the caller keeps i inside the region.
+TPS_DEV void lds16_store(uint16_t* base, uint32_t i, uint32_t v) { base[i] = (uint16_t)v; }
+TPS_DEV uint32_t lds16_load(const uint16_t* base, uint32_t i) { return base[i]; }
 
 // Cache policy of the kernels' big output streams (S_w, raw rows: buffer stores): 2 = nt, non-temporal (gfx940+), 0 = default.
 // Nothing on the device reads these bytes again (the exact change-point tournament aside); streamed past the caches they cost

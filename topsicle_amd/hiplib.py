@@ -293,7 +293,7 @@ class HipScanner:
 
     def debug_option(self, key: str, value: int = 1):
         """tps_ctx_debug_option: diagnostics / tests (event_stride, no_events, force_generic, spans_per_tile, force_pair, so_order,
-        stamps, file_order, no_stride, no_inline_rows, poison).  poison (tests only): 0 = off, 1 .. 255 = the byte every call fills its
+        wpg, lc_lds, stamps, file_order, no_stride, no_inline_rows, poison).  poison (tests only): 0 = off, 1 .. 255 = the byte every call fills its
         output and scratch buffers with before it runs.  Applies to this context and to the helper contexts it makes afterwards."""
         self._check(self.lib.tps_ctx_debug_option(self._h, key.encode(), int(value)))
         self._debug = getattr(self, "_debug", {})
