@@ -460,6 +460,48 @@ int  tps_window_place(tps_ctx* ctx, const uint32_t* codes, int64_t codes_len, co
                       const int32_t* ref_length, int32_t n_ref, int32_t span, int32_t k, int32_t max_occ, int32_t* ref, int32_t* total,
                       int32_t* runner_ref, int32_t* runner, int32_t* offset, int32_t* votes, int32_t* second, int64_t out_len);
 
+/* ---- windows aligned base by base (what a consensus of an end group is called from) ---------------------------------------- */
+/* n query windows, each aligned against one of n_ref reference windows inside a band of 64 diagonals, all from the host (no resident
+ * batch and no pattern table needed).  Both sets are codes rows as tps_batch_end_window writes them, (span + 15) / 16 dwords each
+ * with one span, length[i] resp. ref_length[r] letters; keep bits and k play no part.  A letter that is not ACGT arrives as code 0
+ * and is read as A.  ref[i] = the reference row of query i (< 0: none), centre[i] = the diagonal c the band sits on, with the
+ * meaning of tps_window_offsets' offset: reference position = query position + c.
+ *   band      Q = the query, n letters; R = its reference row, m letters.  Lane l, 0 <= l < 64, owns the diagonal d = c - 32 + l.
+ *             The band is the set of cells (i, j) with 0 <= i <= n, 0 <= j <= m and j - i = d for some lane; every cell outside
+ *             it is infinite.
+ *   start     D(i, j) = 0 on the band cells with i = 0 or j = 0: both leading ends are free.
+ *   step      D(i, j) = min(D(i-1, j-1) + [Q[i-1] != R[j-1]],  D(i-1, j) + 1 (lane l + 1 of the row before),
+ *             D(i, j-1) + 1 (lane l - 1 of the same row)).
+ *   end       among the band cells with i = n or j = m the smallest D; ties go to the largest i, then to the largest j.  dist = that
+ *             D.  No such finite cell (the band misses the matrix), or ref[i] < 0: flag NONE, every number 0, every column "not
+ *             covered".
+ *   path      from the end cell while i > 0 and j > 0, the first that holds: diagonal if D(i, j) = D(i-1, j-1) + s, s = 0 or 1 --
+ *             column j-1 carries the letter Q[i-1]; else up if D(i, j) = D(i-1, j) + 1 -- Q[i-1] is an inserted letter; else left --
+ *             column j-1 is deleted.  (q_begin, r_begin) = the cell where it stops, (q_end, r_end) = the end cell; the columns
+ *             r_begin <= j < r_end are covered.
+ *   inserted  letters are recorded on the column j they stand in front of, and only where r_begin < j < r_end: those in front of
+ *             the first covered column or behind the last are recorded nowhere.
+ *   EDGE      set when a cell the path stands on with i > 0 and j > 0 lies on lane 0 or lane 63.
+ * Outputs, every entry written:
+ *   stat      int32[n][6]: dist, q_begin, q_end, r_begin, r_end, flags (bit 0 NONE, bit 1 EDGE).
+ *   cols      uint16[n][span], or NULL (not asked for): bits 0-2 the state -- 0..3 the query's letter on that column, 4 deleted,
+ *             7 not covered; bits 3-4 min(inserted letters in front of the column, 3); bits 5-6 the first inserted letter; bits
+ *             7-8 the second; everything 0 where it does not apply.
+ *   pile      int32[n_pile][span][13], or NULL, with pile_row int32[n]: cleared by the call; a pair with pile_row[i] >= 0 and neither
+ *             flag set adds, per covered column, one count to its state (A C T G del = entries 0..4), per recorded insertion one
+ *             to ins1[first letter] (entries 5..8) and, with two or more inserted letters, one to ins2[second letter] (entries
+ *             9..12).
+ * Exact, identical from run to run (integer sums do not depend on order).  ref[i] pointing at a row equal to the query is an
+ * ordinary pair with dist 0.  TPS_E_CAPACITY: n over 262144, n_ref outside 1..262144, span outside 1..4096, n_pile outside 0..n_ref.
+ * TPS_E_ARG: codes_len / ref_codes_len / stat_len / cols_len / pile_len that do not match (0 for a piece that is NULL), pile with
+ * n_pile = 0, n_pile > 0 without pile_row, a length or ref_length outside 0..span, ref[i] >= n_ref, |centre[i]| > 4096,
+ * pile_row[i] >= n_pile.  One launch (one wave per pair, one lane per diagonal; dynamic LDS sized by span and by the longest query);
+ * returns when the outputs are in place. */
+int  tps_window_align(tps_ctx* ctx, const uint32_t* codes, int64_t codes_len, const int32_t* length, int64_t n, const uint32_t* ref_codes,
+                      int64_t ref_codes_len, const int32_t* ref_length, int32_t n_ref, const int32_t* ref, const int32_t* centre,
+                      int32_t span, int32_t* stat, int64_t stat_len, uint16_t* cols, int64_t cols_len, const int32_t* pile_row,
+                      int32_t* pile, int32_t n_pile, int64_t pile_len);
+
 /* ---- adapters at the telomere end (which reads start at the real chromosome end, and with which barcode) ---- */
 /* Up to 64 given sequences searched approximately in a region of every read of the resident batch; no pattern table (the
  * reference has nothing comparable).  For read r, h = the upper-cased read (tails[r] = 0) or its reverse complement

@@ -28,6 +28,7 @@
 #include "tps_ends.h"
 #include "tps_anchor.h"
 #include "tps_place.h"
+#include "tps_align.h"
 #include "tps_adapter.h"
 #include "tps_refine.h"
 #include "tps_layout.h"
@@ -178,6 +179,15 @@ __global__ void __launch_bounds__(NT * PLACE_WPG) window_place_kernel(PlaceArgs 
     const int64_t i = (int64_t)blockIdx.x * PLACE_WPG + wave;
     if (i >= a.n) return;
     window_place_row(a, i, smem + wave * PLACE_LDS_DW);
+}
+// One window aligned against another base by base (tps_window_align; window_align_row in csrc/tps_align.h): one wave per pair.  The
+// LDS is dynamic: the call sizes every wave's slice by its span and its longest query.
+__global__ void __launch_bounds__(NT * ALIGN_WPG) window_align_kernel(AlignArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t i = (int64_t)blockIdx.x * ALIGN_WPG + wave;
+    if (i >= a.n) return;
+    window_align_row(a, i, smem + wave * align_lds_dw(a.span, a.cdw, a.rows));
 }
 // The adapters at the telomere end (tps_batch_adapter_find; adapter_read in csrc/tps_adapter.h): no table, one wave per read, one lane
 // per pattern.
@@ -467,6 +477,7 @@ struct tps_ctx {
     DevBuf window_out;                // tps_batch_end_window: codes and keep behind one another (its inputs are ends_in, its table tract_table)
     DevBuf offsets_in, offsets_out;   // tps_window_offsets: codes, keep, length and ref; offset, votes and second behind one another
     DevBuf place_in, place_idx, place_out;   // tps_window_place: the queries' codes, keep and length; the index's dir, keys and ent; the seven outputs behind one another
+    DevBuf align_in, align_out, align_pile;   // tps_window_align: both sets' codes and lengths, ref, centre and pile_row; stat and cols behind one another; the pile
     DevBuf adapter_in, adapter_out;   // tps_batch_adapter_find: Peq, lengths, tails / begin / end; the hits
     DevBuf refine_in, refine_out;     // tps_batch_boundary_refine: tails / begin / end / at; the rows (its table is tract_table)
     DevBuf ascii, ascii_off;          // staging of tps_batch_upload: ASCII bases + offsets, packed on the device right after the copy
@@ -489,6 +500,7 @@ struct tps_ctx {
     int event_stride = 1;             // time every event_stride-th launch (tps_ctx_debug_option "event_stride"): timing costs ~3.5 us per launch
     uint64_t launch_seq = 0;
     size_t lds_set_refine = 0;       // ... of boundary_refine_kernel
+    size_t lds_set_align = 0;        // ... of window_align_kernel
     size_t lds_set_generic = 0;      // hipFuncAttributeMaxDynamicSharedMemorySize as last raised, per scan kernel
     size_t lds_set_fused[KF_COUNT][KSLIDE_MAX - KSLIDE_MIN + 1] = {};
     uint32_t* h_flag = nullptr;      // mapped host word the pack kernel raises when a read has a non-ACGT letter
@@ -1767,6 +1779,63 @@ int tps_window_place(tps_ctx* c, const uint32_t* codes, int64_t codes_len, const
     static_assert(tps::PLACE_OUTS == 7, "the seven outputs behind one another, n entries each");
     return download(c, {{ref, a.out, n_bytes}, {total, a.out + n, n_bytes}, {runner_ref, a.out + 2 * n, n_bytes}, {runner, a.out + 3 * n, n_bytes},
                         {offset, a.out + 4 * n, n_bytes}, {votes, a.out + 5 * n, n_bytes}, {second, a.out + 6 * n, n_bytes}});
+}
+
+int tps_window_align(tps_ctx* c, const uint32_t* codes, int64_t codes_len, const int32_t* length, int64_t n, const uint32_t* ref_codes,
+                     int64_t ref_codes_len, const int32_t* ref_length, int32_t n_ref, const int32_t* ref, const int32_t* centre, int32_t span,
+                     int32_t* stat, int64_t stat_len, uint16_t* cols, int64_t cols_len, const int32_t* pile_row, int32_t* pile, int32_t n_pile,
+                     int64_t pile_len) {
+    int rc;
+    tps::Why why;
+    if ((rc = bind(c))) return rc;
+    if ((rc = tps::window_align_check(codes, codes_len, length, n, ref_codes, ref_codes_len, ref_length, n_ref, ref, centre, span, stat, stat_len, cols, cols_len,
+                                      pile_row, pile, n_pile, pile_len, &why)))
+        return fail(rc, "%s", why.msg);
+    const size_t pile_bytes = pile ? (size_t)pile_len * 4 : 0;
+    if (n == 0) {                                  // (no pair: an empty pile is the whole answer)
+        if (pile_bytes) memset(pile, 0, pile_bytes);
+        return TPS_OK;
+    }
+    const int cdw = (span + 15) / 16;
+    tps::Layout in, out;
+    const size_t co_bytes = (size_t)n * cdw * 4, rco_bytes = (size_t)n_ref * cdw * 4, n_bytes = (size_t)n * 4, nr_bytes = (size_t)n_ref * 4;
+    const size_t st_bytes = (size_t)n * tps::ALIGN_STATS * 4, cl_bytes = cols ? (size_t)n * span * 2 : 0;
+    const size_t in_co = in.add(co_bytes), in_rco = in.add(rco_bytes), in_len = in.add(n_bytes), in_rlen = in.add(nr_bytes), in_ref = in.add(n_bytes),
+                 in_ce = in.add(n_bytes), in_pr = in.add(pile_row ? n_bytes : 0);
+    const size_t off_st = out.add(st_bytes), off_cl = out.add(cl_bytes);
+    if ((rc = c->align_in.ensure(in.total))) return rc;
+    if ((rc = c->align_out.ensure(out.total))) return rc;
+    if (pile_bytes && (rc = c->align_pile.ensure(pile_bytes))) return rc;
+    TPS_POISON(c->align_out);
+    if (pile_bytes) TPS_POISON(c->align_pile);
+    tps::AlignArgs a{};
+    a.codes = at<const uint32_t>(c->align_in, in_co);
+    a.ref_codes = at<const uint32_t>(c->align_in, in_rco);
+    a.length = at<const int32_t>(c->align_in, in_len);
+    a.ref_length = at<const int32_t>(c->align_in, in_rlen);
+    a.ref = at<const int32_t>(c->align_in, in_ref);
+    a.centre = at<const int32_t>(c->align_in, in_ce);
+    a.pile_row = pile_row ? at<const int32_t>(c->align_in, in_pr) : nullptr;
+    HIP_TRY(hipMemcpyAsync((void*)a.codes, codes, co_bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync((void*)a.ref_codes, ref_codes, rco_bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync((void*)a.length, length, n_bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync((void*)a.ref_length, ref_length, nr_bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync((void*)a.ref, ref, n_bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync((void*)a.centre, centre, n_bytes, hipMemcpyHostToDevice, c->stream));
+    if (pile_row) HIP_TRY(hipMemcpyAsync((void*)a.pile_row, pile_row, n_bytes, hipMemcpyHostToDevice, c->stream));
+    a.stat = at<int32_t>(c->align_out, off_st);
+    a.cols = cols ? at<uint16_t>(c->align_out, off_cl) : nullptr;
+    a.pile = pile_bytes ? (int32_t*)c->align_pile.p : nullptr;
+    if (pile_bytes) HIP_TRY(hipMemsetAsync(a.pile, 0, pile_bytes, c->stream));      // (the kernel adds to it)
+    a.n = n;
+    a.span = span; a.cdw = cdw; a.rows = tps::align_rows(length, ref, n);
+    const size_t lds_bytes = (size_t)tps::ALIGN_WPG * tps::align_lds_dw(span, cdw, a.rows) * 4;
+    if (lds_bytes > c->lds_set_align) {
+        HIP_TRY(hipFuncSetAttribute((const void*)tps::window_align_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+        c->lds_set_align = lds_bytes;
+    }
+    if ((rc = launch_waves(c, tps::window_align_kernel, n, tps::ALIGN_WPG, a, lds_bytes))) return rc;
+    return download(c, {{stat, a.stat, st_bytes}, {cols, a.cols, cl_bytes}, {pile, a.pile, pile_bytes}});
 }
 
 int tps_batch_adapter_find(tps_ctx* c, int32_t slot, const uint64_t* patterns, const int32_t* pat_len, int32_t n_pat, const uint8_t* tails,

@@ -208,6 +208,28 @@ TPS_DEV uint32_t wave_max_u32(const Lane<uint32_t>& x) {
     return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
 }
 #endif
+// inclusive prefix minimum over the lanes: lane l gets the smallest x of lanes 0 .. l (device: the DPP steps of wave_incl_sum; a lane
+// a shift or a broadcast does not reach takes the `old` operand, the minimum's identity)
+#ifdef TPS_EMU
+TPS_DEV Lane<uint32_t> wave_incl_min_u32(const Lane<uint32_t>& x) {
+    Lane<uint32_t> r;
+    uint32_t acc = 0xFFFFFFFFu;
+    for (int t = 0; t < NT; ++t) { acc = x.v[t] < acc ? x.v[t] : acc; r.v[t] = acc; }
+    return r;
+}
+#else
+TPS_DEV Lane<uint32_t> wave_incl_min_u32(const Lane<uint32_t>& x) {
+    uint32_t v = x;
+    auto mn = [](uint32_t a, uint32_t b) { return a < b ? a : b; };
+    v = mn(v, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x111, 0xf, 0xf, false));   // row_shr:1
+    v = mn(v, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x112, 0xf, 0xf, false));   // row_shr:2
+    v = mn(v, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x114, 0xf, 0xf, false));   // row_shr:4
+    v = mn(v, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x118, 0xf, 0xf, false));   // row_shr:8
+    v = mn(v, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x142, 0xa, 0xf, false));   // row_bcast:15 -> rows 1, 3
+    v = mn(v, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x143, 0xc, 0xf, false));   // row_bcast:31 -> rows 2, 3
+    return v;
+}
+#endif
 // the sums of a per-lane value over lanes 0 .. 31 (lo) and over lanes 32 .. 63 (hi), both wave-uniform (device: DPP row sums, the
 // rows' totals broadcast into the next row, lanes 31 and 63 read)
 #ifdef TPS_EMU
@@ -275,6 +297,7 @@ TPS_DEV void lds_max_i32(int32_t* p, int32_t v) { if (v > *p) *p = v; }
 TPS_DEV void lds_min_u32(uint32_t* p, uint32_t v) { if (v < *p) *p = v; }
 TPS_DEV void hist_add(unsigned long long* p) { *p += 1ull; }
 TPS_DEV void hist_add_n(unsigned long long* p, uint32_t v) { *p += v; }
+TPS_DEV void g_add_i32(int32_t* p, int32_t v) { *p += v; }
 struct u32x4 { uint32_t x, y, z, w; };
 struct u32x2 { uint32_t x, y; };
 TPS_DEV u32x4 load16(const uint8_t* p) { return *(const u32x4*)p; }
@@ -304,6 +327,7 @@ TPS_DEV void lds_max_i32(int32_t* p, int32_t v) { atomicMax(p, v); }
 TPS_DEV void lds_min_u32(uint32_t* p, uint32_t v) { atomicMin(p, v); }
 TPS_DEV void hist_add(unsigned long long* p) { atomicAdd(p, 1ull); }
 TPS_DEV void hist_add_n(unsigned long long* p, uint32_t v) { atomicAdd(p, (unsigned long long)v); }
+TPS_DEV void g_add_i32(int32_t* p, int32_t v) { atomicAdd(p, v); }      // a 32-bit count in global memory
 typedef uint4 u32x4;
 typedef uint2 u32x2;
 // 16-byte load that is KNOWN to hit global memory: the address was rebuilt from an integer (aligned

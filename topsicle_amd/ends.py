@@ -232,8 +232,9 @@ def cli_collector(args, unit: str, slide: int, anchor=None):
 
 def finish_and_write(args, k, col, filenames, engines):
     """All pairs of the run's sketches: one call per k, on one context, after the last file; then, with --anchor, one boundary per
-    group and, with the ends of --endref's reference (col.ref_ends), one name per read.  Writes the files; yields the log lines."""
-    from . import anchor, endref
+    group -- behind it, with --consensus, one sequence per group -- and, with the ends of --endref's reference (col.ref_ends), one
+    name per read.  Writes the files; yields the log lines."""
+    from . import anchor, consensus, endref
     out = args.outputDir
     try:
         read_rows, group_rows, stats = col.finish(filenames, engines[0])
@@ -248,6 +249,15 @@ def finish_and_write(args, k, col, filenames, engines):
                                                 args.anchorminvotes, args.anchorratio)
         yield analyses.write_tables(out, k, "anchored lengths", [("anchored_reads", anchor.READ_HEADER, a_reads), ("anchored_ends", anchor.GROUP_HEADER, a_groups)])
         yield from anchor.summary(a_stats, args.anchorminvotes, args.anchorratio)
+        if getattr(args, "consensus", False):
+            # every anchored read's window against its group's reference base by base, then against the group's consensus: two calls per k
+            records, c_groups, c_reads, references, c_stats = consensus.run(col.rows_in_order(filenames), read_rows, a_reads, a_groups, engines[0], col.unit,
+                                                                            col.spec.span, args.consensusmindepth, args.minSeqLength)
+            yield analyses.write_tables(out, k, "end consensus", [("end_consensus", consensus.GROUP_HEADER, c_groups), ("consensus_reads", consensus.READ_HEADER, c_reads)])
+            consensus.write_fasta(f"{out}/end_consensus_{k}.fa", records)
+            consensus.write_fasta(f"{out}/end_reference_{k}.fa", references)
+            yield f"end consensus (k = {k}): {out}/end_consensus_{k}.fa, {out}/end_reference_{k}.fa"
+            yield from consensus.summary(c_stats, args.consensusmindepth, args.maxlengthtelo)
     if col.ref_ends is not None:
         # every read's window on all the reference's ends, one call per k
         refs, reads, groups, r_stats = endref.run(col.rows_in_order(filenames), read_rows, col.ref_ends, engines[0], col.spec.k, col.spec.span,

@@ -23,7 +23,7 @@ FOLLOW_MAX_FWD, FOLLOW_WIDE_MAX_FWD, FOLLOW_HIST_MAX = 15, 32, 8      # k-mers t
 EXPORTS = [
     "tps_abi_version", "tps_device_count", "tps_ctx_create", "tps_ctx_destroy", "tps_last_error",
     "tps_set_patterns", "tps_set_patterns_wide", "tps_batch_upload", "tps_batch_upload_packed", "tps_batch_upload_nib4", "tps_batch_share", "tps_host_alloc", "tps_host_free",
-    "tps_batch_download_packed", "tps_batch_kmer_followers", "tps_batch_kmer_followers_wide", "tps_batch_motif_census", "tps_batch_variant_census", "tps_batch_tract_map", "tps_batch_end_sketch", "tps_sketch_links", "tps_batch_end_window", "tps_window_offsets", "tps_window_place", "tps_batch_adapter_find", "tps_batch_boundary_refine", "tps_batch_set_tails", "tps_batch_scan", "tps_sync",
+    "tps_batch_download_packed", "tps_batch_kmer_followers", "tps_batch_kmer_followers_wide", "tps_batch_motif_census", "tps_batch_variant_census", "tps_batch_tract_map", "tps_batch_end_sketch", "tps_sketch_links", "tps_batch_end_window", "tps_window_offsets", "tps_window_place", "tps_window_align", "tps_batch_adapter_find", "tps_batch_boundary_refine", "tps_batch_set_tails", "tps_batch_scan", "tps_sync",
     "tps_batch_results", "tps_batch_window_offsets", "tps_batch_window_sums", "tps_batch_window_raw",
     "tps_batch_raw_to_fd", "tps_batch_trc_counts", "tps_trc_counts", "tps_window_counts", "tps_binseg_l2", "tps_binseg_l2_ties", "tps_batch_read_sums", "tps_window_count",
     "tps_kernel_time_ms", "tps_kernel_time_reset", "tps_device_info", "tps_batch_kernel_info", "tps_ctx_debug_option", "tps_debug_stamps_get",
@@ -70,6 +70,9 @@ ENDS_EMPTY = 0xFFFFFFFF           # an empty bucket of a sketch
 ANCHOR_MAX_SPAN, ANCHOR_MAX_ROWS = 4096, 262144
 # tps_window_place: reference rows of one call, entries of a k-mer that still takes part
 PLACE_MAX_REFS, PLACE_MAX_OCC = 1024, 64
+# tps_window_align: letters of a window, rows of either set, entries of a stat row and of a pile column; the two flags; a column's states
+ALIGN_MAX_SPAN, ALIGN_MAX_ROWS, ALIGN_STATS, ALIGN_PILE = 4096, 262144, 6, 13
+ALIGN_NONE, ALIGN_EDGE, ALIGN_DELETED, ALIGN_UNCOVERED = 1, 2, 4, 7
 # tps_batch_adapter_find: letters of a pattern, patterns of one call, letters of a region
 ADAPTER_LEN_RANGE, ADAPTER_MAX_PATTERNS, ADAPTER_MAX_REGION = (12, 64), 64, 1024
 REFINE_DTYPE = np.dtype([(f, "<i4") for f in ("pos", "score", "drop", "at_score", "hits_before", "hits_after", "runner", "runner_pos")])      # struct tps_refine
@@ -126,6 +129,7 @@ def load_library(path: str | None = None) -> C.CDLL:
         "tps_batch_end_window": (C.c_int, [vp, i32, C.c_uint64, i32, i32, vp, vp, vp, i64, i32, vp, i64, vp, i64]),
         "tps_window_offsets": (C.c_int, [vp, vp, vp, vp, vp, i64, i32, i32, vp, vp, vp, i64]),
         "tps_window_place": (C.c_int, [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64]),
+        "tps_window_align": (C.c_int, [vp, vp, i64, vp, i64, vp, i64, vp, i32, vp, vp, i32, vp, i64, vp, i64, vp, vp, i32, i64]),
         "tps_batch_adapter_find": (C.c_int, [vp, i32, vp, vp, i32, vp, vp, vp, i64, vp, i64]),
         "tps_batch_boundary_refine": (C.c_int, [vp, i32, C.c_uint64, i32, vp, vp, vp, vp, i64, i32, i32, i32, vp, i64]),
         "tps_batch_set_tails": (C.c_int, [vp, i32, vp]),
@@ -601,6 +605,37 @@ class HipScanner:
         self._check(self.lib.tps_window_place(self._h, _ptr(codes), codes.size, _ptr(keep), keep.size, _ptr(length), n, _ptr(ref_codes), ref_codes.size,
                                               _ptr(ref_keep), ref_keep.size, _ptr(ref_length), n_ref, span, k, max_occ, *[_ptr(o) for o in out], n))
         return tuple(out)
+
+    def align_windows(self, codes, length, ref_codes, ref_length, ref, centre, span: int, cols: bool = True, pile_row=None, n_pile: int = 0):
+        """n query windows aligned base by base against reference windows inside a band of 64 diagonals (tps_window_align; the rule
+        is in include/topsicle_hip.h): both sets as codes rows the way end_window returns them, length[i] / ref_length[r] letters
+        each; ref[i] = the reference row of query i (< 0: none), centre[i] = the diagonal the band sits on (anchor_offsets' offset).
+        Returns (stat int32[n, 6], cols uint16[n, span] or None, pile int32[n_pile, span, 13] or None): dist, q_begin, q_end,
+        r_begin, r_end and flags (1 = no alignment, 2 = the path touched the band's edge); the state of every reference column;
+        and, with pile_row (the pile row a pair counts for, < 0: none) and n_pile > 0, the votes of the unflagged pairs per pile
+        row and column.  Needs no resident batch and no pattern table."""
+        codes = np.ascontiguousarray(codes, dtype=np.uint32)
+        length = np.ascontiguousarray(length, dtype=np.int32)
+        ref_codes = np.ascontiguousarray(ref_codes, dtype=np.uint32)
+        ref_length = np.ascontiguousarray(ref_length, dtype=np.int32)
+        ref = np.ascontiguousarray(ref, dtype=np.int32)
+        centre = np.ascontiguousarray(centre, dtype=np.int32)
+        n, n_ref = len(length), len(ref_length)
+        sp = span if 1 <= span <= ALIGN_MAX_SPAN else 1                        # (a bad span is the library's to refuse)
+        cdw = (sp + 15) // 16
+        if codes.shape != (n, cdw) or ref_codes.shape != (n_ref, cdw) or len(ref) != n or len(centre) != n:
+            raise TopsicleHipError("align_windows: codes / ref_codes must hold one row of `span` letters per window, ref and centre one entry per query")
+        if pile_row is not None:
+            pile_row = np.ascontiguousarray(pile_row, dtype=np.int32)
+            if len(pile_row) != n:
+                raise TopsicleHipError("align_windows: pile_row must hold one entry per query")
+        stat = np.zeros((n, ALIGN_STATS), dtype=np.int32)
+        out_cols = np.zeros((n, sp), dtype=np.uint16) if cols else None
+        pile = np.zeros((n_pile, sp, ALIGN_PILE), dtype=np.int32) if n_pile > 0 else None
+        self._check(self.lib.tps_window_align(self._h, _ptr(codes), codes.size, _ptr(length), n, _ptr(ref_codes), ref_codes.size, _ptr(ref_length), n_ref,
+                                              _ptr(ref), _ptr(centre), span, _ptr(stat), stat.size, _ptr(out_cols), 0 if out_cols is None else out_cols.size,
+                                              _ptr(pile_row), _ptr(pile), n_pile, 0 if pile is None else pile.size))
+        return stat, out_cols, pile
 
     def adapter_find(self, slot: int, patterns, tails, begin, end):
         """Every sequence of `patterns` (strings of ACGT, 12 .. 64 letters, at most 64 of them, telomere first like the region)

@@ -20,7 +20,7 @@ from collections import defaultdict
 
 import numpy as np
 
-from . import adapters, allsteps, anchor, batch, endref, ends, hiplib, motif, rawnpz, refine, seqio, tracts, variants
+from . import adapters, allsteps, anchor, batch, consensus, endref, ends, hiplib, motif, rawnpz, refine, seqio, tracts, variants
 
 version_number = "1.0.0"
 Topsicle_output_prefix = "Topsicle"
@@ -36,7 +36,7 @@ PER_K_ANALYSES = (variants, ends, adapters, refine)       # one collector per k
 ANALYSES = PER_K_ANALYSES + (tracts,)                     # one for the run: the map of whole reads, with the first k's job
 # ... and what is checked before anything is read or written, in this order (--variants is only checked against the real unit;
 # --anchor and --endref hang on --ends and have nothing else to check)
-EARLY_CHECKS = (tracts, ends, anchor, endref, adapters, refine)
+EARLY_CHECKS = (tracts, ends, anchor, consensus, endref, adapters, refine)
 LAST_TIMINGS = {}                 # seconds of the last analysis_run: reads (step 1 + 2 + outputs) / summary (fit + PNG); bench.py's e2e leg reads it
 PLOT_THREADS = []                 # quadratic-fit PNGs being rendered off the critical path (summarize); wait_for_plots() joins them
 
@@ -655,6 +655,10 @@ def build_parser():
                              "group and measure every read's telomere to it (anchored_reads_{k}.csv, anchored_ends_{k}.csv); needs --endspan of at most 4096")
     parser.add_argument("--anchorminvotes", metavar="INT", type=int, default=anchor.DEFAULT_MIN_VOTES, help="--anchor: k-mer votes a read needs on its best diagonals to be anchored")
     parser.add_argument("--anchorratio", metavar="INT", type=int, default=anchor.DEFAULT_RATIO, help="--anchor: ... and how many times the votes of the runner-up diagonals")
+    parser.add_argument("--consensus", action="store_true",
+                        help="MI355X build, with --ends --anchor: align the anchored reads of every end group base by base and call one consensus subtelomere per "
+                             "group (end_consensus_{k}.fa and .csv, consensus_reads_{k}.csv) and a reference --endref takes in the next run (end_reference_{k}.fa)")
+    parser.add_argument("--consensusmindepth", metavar="INT", type=int, default=consensus.DEFAULT_MIN_DEPTH, help="--consensus: reads a column needs to be called from them")
     parser.add_argument("--endref", metavar="REF", default=None,
                         help="MI355X build, with --ends: name the end groups against a reference -- a FASTA or FASTQ (plain or gzip) of chromosomes, contigs or subtelomeres; the "
                              "first and last maxlengthtelo bases of every record are scanned like reads, and every read's window is placed on the ends found "
