@@ -555,6 +555,38 @@ int  tps_batch_boundary_refine(tps_ctx* ctx, int32_t slot, uint64_t unit, int32_
                                const int32_t* end, const int32_t* at, int64_t n_reads, int32_t hit, int32_t miss, int32_t sep,
                                tps_refine* out, int64_t out_len);
 
+/* ---- base modifications against the boundary ------------------------------------------------------------------------------- */
+/* The calls of one base modification (BAM MM / ML tags, as tps_bam_mods_spans of include/topsicle_io.h lists them: skip counts among
+ * the read's C's and probability bytes) put on the resident read and binned against a boundary; no pattern table (the reference has
+ * nothing comparable).  Read r owns the entries mod_off[r] .. mod_off[r + 1] of delta[] / prob[].  end[r] is clamped to L; the
+ * region [begin, end) is in the coordinates of the telomere-first string, t = p (tails[r] = 0) or L - 1 - p (1) for the position p
+ * of the resident read -- the read as sequenced, which is what MM counts along.
+ *   C, CpG   p is a C when its base is c or C; a CpG when also p + 1 < L and the base there is g or G.  Read orientation, whatever
+ *            the tail.
+ *   ordinal  entry j has o_j = (delta_0 + 1) + ... + (delta_j + 1) - 1, carried in 64 bits, saturating: it never wraps.
+ *   landing  o_j >= c_total, the read's C's: `beyond`; one such entry sets TPS_MOD_BAD in flags and makes every bin of the read,
+ *            and cpg and called of its row, zero.  Otherwise the entry sits on the o_j-th C (from 0) at p, and is in_region when
+ *            begin <= t < end; in the region and not on a CpG: off_context; else it falls into bin floor((t - origin) / w) + nb0.
+ *   bins     nb0 bins of w bases in front of origin, nb1 behind: called = the entries, sum = the sum of their prob bytes, high =
+ *            those with prob >= hi, low = those with prob <= lo; cpg = the CpGs of the sequence whose t falls into the bin,
+ *            whatever the tags say.
+ *   row      c_total, entries (mod_off[r + 1] - mod_off[r]), beyond, in_region, off_context, cpg and called summed over the bins,
+ *            flags.
+ *   empty    a read with begin >= end after the clamp gets a row and bins of zeros.
+ * Every row and every bin record is written whole, every time; exact integers, identical from run to run.  TPS_E_CAPACITY: w outside
+ * 16..4096, nb0 + nb1 outside 1..64, end - begin > 16384 after the clamp (named with the read: "read 7: ...").  TPS_E_ARG: lo < hi
+ * within 0..255 does not hold, a negative begin / end / origin, begin > end, a tail other than 0 / 1, a region that is not empty and
+ * leaves [origin - nb0 w, origin + nb1 w), n_reads / rows_len / bins_len that do not match the slot, mod_off that does not ascend
+ * from a value >= 0 to n_mods, null arrays with reads in the slot.  TPS_E_STATE: an empty slot.  An empty batch is TPS_OK.  One launch
+ * (one wave per read); returns when rows and bins are in place.  The slot's scan state is not touched. */
+#define TPS_MOD_BAD 1u          /* tps_mod_row.flags: an entry lies beyond the read's last C (a tag that does not belong to these bases) */
+typedef struct tps_mod_row { uint32_t c_total, entries, beyond, in_region, off_context, cpg, called, flags; } tps_mod_row; /* 32 bytes */
+typedef struct tps_mod_bin { uint16_t cpg, called, high, low; uint32_t sum; } tps_mod_bin;                                /* 12 bytes */
+int  tps_batch_mod_profile(tps_ctx* ctx, int32_t slot, const uint8_t* tails, const int32_t* begin, const int32_t* end,
+                           const int32_t* origin, int64_t n_reads, const int64_t* mod_off, const uint32_t* delta, const uint8_t* prob,
+                           int64_t n_mods, int32_t w, int32_t nb0, int32_t nb1, int32_t hi, int32_t lo, tps_mod_row* rows,
+                           int64_t rows_len, tps_mod_bin* bins, int64_t bins_len);
+
 /* ---- measurement ----------------------------------------------------------------------- */
 /* hipEvent timings of the scan kernel launches since the last reset: number of launches,
  * total and mean milliseconds (events are recorded on the stream the kernel runs on). */

@@ -109,6 +109,27 @@ int64_t tps_fastq_spans_bytes(const int64_t* spans, const int32_t* lens, const i
  * qualities.  A record takes tps_fastq_spans_bytes's count.  Returns the bytes written or -1. */
 int64_t tps_write_bam_fastq_spans_at(int fd, int64_t file_off, const char* text, int64_t text_len, const int64_t* spans, const int32_t* lens,
                                      const int64_t* idx, int64_t n);
+/* The base-modification calls (SAMtags MM / ML) of the records idx[0 .. n_idx) of the last nib4 batch: text, spans, lens as
+ * tps_write_bam_fastq_spans_at takes them.  A record's aux block lies behind its qualities and runs to the end the record's
+ * block_size gives (the record starts 36 bytes in front of its name); every tag is stepped over by its SAMv1 4.2.4 size.  MM:Z is
+ * parsed by the grammar ([ACGTUN][-+]([a-z]+|[0-9]+)[.?]?(,[0-9]+)*;)* and the FIRST group on base C, strand +, whose code list holds
+ * `code` ('m' for 5mC, 'h' for 5hmC; a lower-case letter) is taken: its skip counts go to delta[], the matching ML:B:C bytes to prob[]
+ * -- ML is the concatenation over all groups in order, and inside a group of n codes the values are interleaved with stride n --
+ * and mod_off[j] .. mod_off[j + 1] are record idx[j]'s entries.  mode[j] = 1 for '?' (skipped bases unknown), 0 for '.' or no flag
+ * (skipped bases unmodified).  status[j]:
+ *   0 ok (an empty list included)
+ *   1 no MM:Z or no ML:B tag
+ *   2 no group to take.  Groups on base N (or any base but C), strand - (duplex reads) and codes given as ChEBI numbers only are out
+ *     of scope and end here
+ *   3 malformed: a tag that runs past the record or has an unknown type, an MM that does not follow the grammar, a count over
+ *     2^32 - 1, ML that is not an array of bytes or is shorter than the groups need, MN that is no integer
+ *   4 an MN:i tag that differs from l_seq (a hard-clipped record: its tags count along bases that are not there)
+ * A malformed aux block is 3 whatever else the record holds; then 1; then a malformed MM or ML; then 2; then a short ML; then 4.  A
+ * record with a status other than 0 contributes no entries.  Nothing is reversed for reverse-strand records: MM counts along the read
+ * as sequenced, which is the read tps_batch_upload_nib4 leaves resident after TPS_NIB_REVERSE.  Returns the number of entries; -2
+ * when mods_cap is too small, with nothing written; -1 on a bad span or argument (tps_io_last_error). */
+int64_t tps_bam_mods_spans(const char* text, int64_t text_len, const int64_t* spans, const int32_t* lens, const int64_t* idx, int64_t n_idx, char code,
+                           int32_t* status, uint8_t* mode, int64_t* mod_off /* n_idx + 1 */, uint32_t* delta, uint8_t* prob, int64_t mods_cap);
 /* zlib's crc32(crc, p, n) by carry-less multiplication (the checksum callback of tps_batch_raw_to_fd) and crc32_combine. */
 uint32_t tps_crc32(uint32_t crc, const uint8_t* p, int64_t n);
 uint32_t tps_crc32_combine(uint32_t crc1, uint32_t crc2, int64_t len2);

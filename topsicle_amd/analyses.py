@@ -1,4 +1,4 @@
-"""What the read analyses share (variants.py, ends.py, adapters.py, refine.py, tracts.py): the shape of an analysis that runs on the
+"""What the read analyses share (variants.py, ends.py, adapters.py, refine.py, methyl.py, tracts.py): the shape of an analysis that runs on the
 regions behind the called boundaries of a resident batch (batch.run_analysis makes the calls), the collector between the batch workers
 and the run's consumer, and the CSV helpers.  Nothing here knows a particular analysis.
 
@@ -13,10 +13,11 @@ import numpy as np
 
 
 class BoundaryAnalysis:
-    """What batch.Job(variants=, ends=, adapters=, refine=) carries.  batch.run_analysis calls, on the worker that scanned a batch and
+    """What batch.Job(variants=, ends=, adapters=, refine=, methyl=) carries.  batch.run_analysis calls, on the worker that scanned a batch and
     while that batch is still resident:
 
       regions(res, prm) -> (begin, end, *extra)   int32 arrays over the whole batch; begin = end = 0 for a read without a stored boundary
+                                                  (needs_records = True: regions(res, prm, recs), the batch's records as well)
       empty(n)          -> outputs                what n reads with empty regions get, in launch()'s order
       launch(eng, slot, tails, begin, end, *extra) -> outputs    the engine call(s) on the reads resident in `slot`
       sink(recs, res, *outputs)                   the spec's `sink` attribute
@@ -24,6 +25,7 @@ class BoundaryAnalysis:
     The last `per_batch` outputs are one answer for the whole call, not a row per read: they are never scattered over the batch."""
 
     per_batch = 0
+    needs_records = False
     sink = None
 
     @staticmethod

@@ -42,23 +42,24 @@ class Job:
     batch = `--telophrase 4 5 6`: the batch is parsed, packed and uploaded ONCE and scanned once per k (the reference
     re-parses the input for every k, main.py:206-235)."""
 
-    def __init__(self, patterns, prm: hiplib.Params, want_sums=False, want_raw=False, raw_sink=None, variants=None, tracts=None, ends=None, adapters=None, refine=None):
+    def __init__(self, patterns, prm: hiplib.Params, want_sums=False, want_raw=False, raw_sink=None, variants=None, tracts=None, ends=None, adapters=None, refine=None,
+                 methyl=None):
         """raw_sink (with want_raw; rawnpz.RawNpzWriter): the raw rows of the reads the sink selects are written to its file by
         the worker that scanned the batch, device -> file, and the caller gets a `RawKept` in place of the rows.
-        variants, ends, adapters, refine (variants.VariantSpec, ends.EndSpec, adapters.AdapterSpec, refine.RefineSpec: each an
-        analyses.BoundaryAnalysis): the worker that scanned the batch runs the analysis on the regions behind the boundaries it has
+        variants, ends, adapters, refine, methyl (variants.VariantSpec, ends.EndSpec, adapters.AdapterSpec, refine.RefineSpec,
+        methyl.MethylSpec: each an analyses.BoundaryAnalysis): the worker that scanned the batch runs the analysis on the regions behind the boundaries it has
         just called, while the batch is still resident, and hands (recs, results, *outputs) to the spec's sink (run_analysis).
         tracts (tracts.TractSpec: unit, the rule's parameters, sink): the same worker maps the telomere-repeat tracts of EVERY read of
         the batch, passing or not, and hands (recs, tracts, found, totals) to the spec's sink.  The map needs whole reads: a batch
         in heads mode is refused.  One job of a batch carries it (the map does not depend on the pattern table)."""
         self.patterns, self.prm, self.want_sums, self.want_raw = list(patterns), prm, bool(want_sums), bool(want_raw)
         self.raw_sink = raw_sink if want_raw else None
-        self.variants, self.ends, self.adapters, self.refine, self.tracts = variants, ends, adapters, refine, tracts
+        self.variants, self.ends, self.adapters, self.refine, self.methyl, self.tracts = variants, ends, adapters, refine, methyl, tracts
 
     @property
     def analyses(self):
         """The boundary analyses the job carries, in the order they are launched behind its scan."""
-        return [spec for spec in (self.variants, self.ends, self.adapters, self.refine) if spec is not None]
+        return [spec for spec in (self.variants, self.ends, self.adapters, self.refine, self.methyl) if spec is not None]
 
 
 class CensusJob:
@@ -126,8 +127,11 @@ def run_analysis(spec, prm, eng, slot, recs, res, slot_index=None):
                                    reads only -- their packed span is the first / last min(L, maxlen) bases, so the coordinates are
                                    those of the whole read): those are submitted, their rows scattered over the empty answer;
       slot_index None, eng None    nothing is resident (no read passed, or no window step): no launch, the empty answer.
-    Outputs that are one answer per call (spec.per_batch) are passed on as they come.  The sink gets (recs, res, *outputs)."""
-    begin, end, *extra = spec.regions(res, prm)
+    Outputs that are one answer per call (spec.per_batch) are passed on as they come.  The sink gets (recs, res, *outputs).
+    A spec with needs_records (methyl.MethylSpec: the tags sit in the batch's record text) gets regions(res, prm, recs).  What
+    regions() hands back behind begin and end is cut to the resident reads with [slot_index]: arrays, or one object that answers it
+    (the ragged entry lists of seqio.Mods)."""
+    begin, end, *extra = spec.regions(res, prm, recs) if getattr(spec, "needs_records", False) else spec.regions(res, prm)
     tails = np.where(end > begin, res["tail"], 0).astype(np.uint8)
     out = list(spec.empty(len(res)))
     if slot_index is None:

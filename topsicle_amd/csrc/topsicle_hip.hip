@@ -31,6 +31,7 @@
 #include "tps_align.h"
 #include "tps_adapter.h"
 #include "tps_refine.h"
+#include "tps_methyl.h"
 #include "tps_layout.h"
 #include "tps_pack.h"
 #include "tps_plan.h"
@@ -210,6 +211,14 @@ __global__ void __launch_bounds__(NT * REFINE_WPG) boundary_refine_kernel(Refine
     const int64_t r = (int64_t)blockIdx.x * REFINE_WPG + wave;
     if (r >= a.n_reads) return;
     refine_read(a, r, smem + TRACT_TABLE_DW + wave * refine_lds_dw(a.bal_dw), smem);
+}
+// Base modifications against the boundary (tps_batch_mod_profile; mod_read in csrc/tps_methyl.h): no table, one wave per read.
+__global__ void __launch_bounds__(NT * MOD_WPG) mod_profile_kernel(ModArgs a) {
+    __shared__ __attribute__((aligned(16))) uint32_t smem[MOD_WPG * MOD_LDS_DW];
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t r = (int64_t)blockIdx.x * MOD_WPG + wave;
+    if (r >= a.n_reads) return;
+    mod_read(a, r, smem + wave * MOD_LDS_DW);
 }
 }  // namespace tps
 
@@ -479,6 +488,7 @@ struct tps_ctx {
     DevBuf place_in, place_idx, place_out;   // tps_window_place: the queries' codes, keep and length; the index's dir, keys and ent; the seven outputs behind one another
     DevBuf align_in, align_out, align_pile;   // tps_window_align: both sets' codes and lengths, ref, centre and pile_row; stat and cols behind one another; the pile
     DevBuf adapter_in, adapter_out;   // tps_batch_adapter_find: Peq, lengths, tails / begin / end; the hits
+    DevBuf mod_in, mod_out;           // tps_batch_mod_profile: tails / begin / end / origin, mod_off, delta, prob; the rows and the bins behind them
     DevBuf refine_in, refine_out;     // tps_batch_boundary_refine: tails / begin / end / at; the rows (its table is tract_table)
     DevBuf ascii, ascii_off;          // staging of tps_batch_upload: ASCII bases + offsets, packed on the device right after the copy
     DevBuf nib, nib_src;              // staging of tps_batch_upload_nib4: BAM base codes + where each read's are, expanded right after the copy
@@ -1076,7 +1086,7 @@ Slot* get_slot(tps_ctx* c, int slot) {
     return &c->slots[slot];
 }
 
-// ---- the steps the read-analysis calls share (tps_batch_kmer_followers .. tps_batch_boundary_refine; DESIGN.md, "How a read-analysis
+// ---- the steps the read-analysis calls share (tps_batch_kmer_followers .. tps_batch_mod_profile; DESIGN.md, "How a read-analysis
 // call is put together").  Each call: need_batch (or bind alone, where it takes no batch), its check function from the feature's
 // header, its layouts (tps_layout.h), ensure + TPS_POISON, its clearing memsets and input copies, launch_waves, download.
 
@@ -1907,6 +1917,48 @@ int tps_batch_boundary_refine(tps_ctx* c, int32_t slot, uint64_t unit, int32_t m
     }
     if ((rc = launch_waves(c, tps::boundary_refine_kernel, n, tps::REFINE_WPG, a, lds_bytes))) return rc;
     return download(c, {{out, a.out, out_bytes}});
+}
+
+int tps_batch_mod_profile(tps_ctx* c, int32_t slot, const uint8_t* tails, const int32_t* begin, const int32_t* end, const int32_t* origin, int64_t n_reads,
+                          const int64_t* mod_off, const uint32_t* delta, const uint8_t* prob, int64_t n_mods, int32_t w, int32_t nb0, int32_t nb1, int32_t hi,
+                          int32_t lo, tps_mod_row* rows, int64_t rows_len, tps_mod_bin* bins, int64_t bins_len) {
+    int rc;
+    Slot* sl;
+    tps::Why why;
+    if ((rc = need_batch(c, slot, &sl))) return rc;
+    const int64_t n = sl->n;
+    if ((rc = tps::mod_profile_check(n, sl->h_offsets.data(), tails, begin, end, origin, n_reads, mod_off, delta, prob, n_mods, w, nb0, nb1, hi, lo, rows, rows_len,
+                                     bins, bins_len, &why)))
+        return fail(rc, "%s", why.msg);
+    if (n == 0) return TPS_OK;
+    // (no pattern table; the slot's tails, its scan outputs and its plan are not touched: a scan before and after the call gives the same results)
+    tps::Layout in, out;
+    const tps::RegionAt reg = tps::region_layout(in, n);
+    const size_t off_origin = in.add((size_t)n * 4), off_mo = in.add((size_t)(n + 1) * 8, 8), off_delta = in.add((size_t)n_mods * 4), off_prob = in.add((size_t)n_mods);
+    const size_t row_bytes = (size_t)n * sizeof(tps_mod_row), bin_bytes = (size_t)n * (nb0 + nb1) * sizeof(tps_mod_bin);
+    const size_t off_rows = out.add(row_bytes, 16), off_bins = out.add(bin_bytes, 16);
+    if ((rc = c->mod_in.ensure(in.total))) return rc;
+    if ((rc = c->mod_out.ensure(out.total))) return rc;
+    TPS_POISON(c->mod_out);
+    tps::ModArgs a{};
+    set_batch(a, *sl);
+    if ((rc = upload_region(c, c->mod_in, reg, tails, begin, end, n, a))) return rc;
+    a.origin = at<const int32_t>(c->mod_in, off_origin);
+    a.mod_off = at<const int64_t>(c->mod_in, off_mo);
+    a.delta = at<const uint32_t>(c->mod_in, off_delta);
+    a.prob = at<const uint8_t>(c->mod_in, off_prob);
+    HIP_TRY(hipMemcpyAsync((void*)a.origin, origin, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync((void*)a.mod_off, mod_off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    if (n_mods > 0) {
+        HIP_TRY(hipMemcpyAsync((void*)a.delta, delta, (size_t)n_mods * 4, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync((void*)a.prob, prob, (size_t)n_mods, hipMemcpyHostToDevice, c->stream));
+    }
+    a.rows = at<tps_mod_row>(c->mod_out, off_rows);
+    a.bins = at<tps_mod_bin>(c->mod_out, off_bins);
+    a.n_reads = n;
+    a.w = w; a.nb0 = nb0; a.nb1 = nb1; a.hi = hi; a.lo = lo;
+    if ((rc = launch_waves(c, tps::mod_profile_kernel, n, tps::MOD_WPG, a))) return rc;
+    return download(c, {{rows, a.rows, row_bytes}, {bins, a.bins, bin_bytes}});
 }
 
 int tps_batch_set_tails(tps_ctx* c, int32_t slot, const uint8_t* tails) {

@@ -30,6 +30,7 @@
 
 #include "tps_pack.h"
 #include "tps_gzpar.h"
+#include "tps_mods.h"
 
 #include <algorithm>
 #include <cstdint>
@@ -1862,6 +1863,18 @@ int64_t tps_write_bam_fastq_spans_at(int fd, int64_t file_off, const char* text,
     }
     if (!flush()) return -1;
     return total;
+}
+
+// The base-modification calls of the records idx[0 .. n_idx) of a BAM batch (spans of tps_reader_next_nib4): the aux block behind
+// each record's qualities is walked and the first MM group on C+ that lists `code`, with its ML bytes, is appended to delta / prob
+// (tps_mods.h has the walk and the grammar; include/topsicle_io.h the statuses).  Only the records asked for are looked at: the
+// caller passes the reads with a stored boundary.
+int64_t tps_bam_mods_spans(const char* text, int64_t text_len, const int64_t* spans, const int32_t* lens, const int64_t* idx, int64_t n_idx, char code,
+                           int32_t* status, uint8_t* mode, int64_t* mod_off, uint32_t* delta, uint8_t* prob, int64_t mods_cap) {
+    const char* why = "";
+    const int64_t got = tps::mods_spans(text, text_len, spans, lens, idx, n_idx, code, status, mode, mod_off, delta, prob, mods_cap, &why);
+    if (got == -1) g_err = why;
+    return got;
 }
 
 static int64_t write_fastq_spans(int fd, int64_t file_off, const char* text, int64_t text_len, const int64_t* spans, const int32_t* lens, const int64_t* idx, int64_t n) {

@@ -241,6 +241,7 @@ def finish_and_write(args, k, col, filenames, engines):
     except ValueError as e:                        # more reads than one link call takes: said, not hidden; every other output stands
         yield f"{e}; no end groups written for k = {k}"
         return
+    col.read_rows = read_rows                      # (methyl.finish_and_write groups its reads by them)
     yield analyses.write_tables(out, k, "end groups", [("end_reads", READ_HEADER, read_rows), ("ends", GROUP_HEADER, group_rows)])
     yield from summary(col, stats)
     if getattr(args, "anchor", False):

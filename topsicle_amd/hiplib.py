@@ -23,7 +23,7 @@ FOLLOW_MAX_FWD, FOLLOW_WIDE_MAX_FWD, FOLLOW_HIST_MAX = 15, 32, 8      # k-mers t
 EXPORTS = [
     "tps_abi_version", "tps_device_count", "tps_ctx_create", "tps_ctx_destroy", "tps_last_error",
     "tps_set_patterns", "tps_set_patterns_wide", "tps_batch_upload", "tps_batch_upload_packed", "tps_batch_upload_nib4", "tps_batch_share", "tps_host_alloc", "tps_host_free",
-    "tps_batch_download_packed", "tps_batch_kmer_followers", "tps_batch_kmer_followers_wide", "tps_batch_motif_census", "tps_batch_variant_census", "tps_batch_tract_map", "tps_batch_end_sketch", "tps_sketch_links", "tps_batch_end_window", "tps_window_offsets", "tps_window_place", "tps_window_align", "tps_batch_adapter_find", "tps_batch_boundary_refine", "tps_batch_set_tails", "tps_batch_scan", "tps_sync",
+    "tps_batch_download_packed", "tps_batch_kmer_followers", "tps_batch_kmer_followers_wide", "tps_batch_motif_census", "tps_batch_variant_census", "tps_batch_tract_map", "tps_batch_end_sketch", "tps_sketch_links", "tps_batch_end_window", "tps_window_offsets", "tps_window_place", "tps_window_align", "tps_batch_adapter_find", "tps_batch_boundary_refine", "tps_batch_mod_profile", "tps_batch_set_tails", "tps_batch_scan", "tps_sync",
     "tps_batch_results", "tps_batch_window_offsets", "tps_batch_window_sums", "tps_batch_window_raw",
     "tps_batch_raw_to_fd", "tps_batch_trc_counts", "tps_trc_counts", "tps_window_counts", "tps_binseg_l2", "tps_binseg_l2_ties", "tps_batch_read_sums", "tps_window_count",
     "tps_kernel_time_ms", "tps_kernel_time_reset", "tps_device_info", "tps_batch_kernel_info", "tps_ctx_debug_option", "tps_debug_stamps_get",
@@ -79,6 +79,11 @@ REFINE_DTYPE = np.dtype([(f, "<i4") for f in ("pos", "score", "drop", "at_score"
 assert REFINE_DTYPE.itemsize == 32
 # tps_batch_boundary_refine: hit and miss, sep, end - begin (after end is clamped to the read)
 REFINE_WEIGHT_RANGE, REFINE_SEP_RANGE, REFINE_MAX_REGION = (1, 16), (1, 65535), 65536
+MOD_ROW_DTYPE = np.dtype([(f, "<u4") for f in ("c_total", "entries", "beyond", "in_region", "off_context", "cpg", "called", "flags")])      # struct tps_mod_row
+MOD_BIN_DTYPE = np.dtype([("cpg", "<u2"), ("called", "<u2"), ("high", "<u2"), ("low", "<u2"), ("sum", "<u4")])                                    # struct tps_mod_bin
+assert MOD_ROW_DTYPE.itemsize == 32 and MOD_BIN_DTYPE.itemsize == 12
+# tps_batch_mod_profile: the bin width, the bins, end - begin (after end is clamped to the read); tps_mod_row.flags
+MOD_W_RANGE, MOD_MAX_BINS, MOD_MAX_REGION, MOD_BAD = (16, 4096), 64, 16384, 1
 RES_TIE = 1            # TPS_RES_TIE: the exact tournament decided the change-point (candidates within float64 noise of each other)
 
 
@@ -132,6 +137,7 @@ def load_library(path: str | None = None) -> C.CDLL:
         "tps_window_align": (C.c_int, [vp, vp, i64, vp, i64, vp, i64, vp, i32, vp, vp, i32, vp, i64, vp, i64, vp, vp, i32, i64]),
         "tps_batch_adapter_find": (C.c_int, [vp, i32, vp, vp, i32, vp, vp, vp, i64, vp, i64]),
         "tps_batch_boundary_refine": (C.c_int, [vp, i32, C.c_uint64, i32, vp, vp, vp, vp, i64, i32, i32, i32, vp, i64]),
+        "tps_batch_mod_profile": (C.c_int, [vp, i32, vp, vp, vp, vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, i32, vp, i64, vp, i64]),
         "tps_batch_set_tails": (C.c_int, [vp, i32, vp]),
         "tps_batch_scan": (C.c_int, [vp, i32, C.POINTER(Params)]),
         "tps_sync": (C.c_int, [vp]),
@@ -672,6 +678,28 @@ class HipScanner:
         self._check(self.lib.tps_batch_boundary_refine(self._h, slot, code, m, _ptr(tails), _ptr(begin), _ptr(end), _ptr(at), len(tails), hit, miss, sep,
                                                        _ptr(out), out.size))
         return out
+
+    def mod_profile(self, slot: int, tails, begin, end, origin, mod_off, delta, prob, w: int = 500, nb0: int = 2, nb1: int = 8, hi: int = 205, lo: int = 50):
+        """The calls of one base modification (BAM MM / ML tags: seqio.bam_mods gives mod_off / delta / prob) put on the reads of the
+        resident batch and binned against `origin` in the region [begin, end) of every read (tails: 0 = the read, 1 = counted from its
+        far end; at most 16 384 bases, inside the nb0 bins of w bases in front of origin and the nb1 behind it): (MOD_ROW_DTYPE[n],
+        MOD_BIN_DTYPE[n, nb0 + nb1]) -- per read its C's, entries, those beyond the last C, in the region, off a CpG, and per bin the
+        CpGs of the sequence, the calls on them, their prob sum, those >= hi and those <= lo (tps_batch_mod_profile, the rule is in
+        include/topsicle_hip.h; the files: topsicle_amd.methyl).  No pattern table needed; the slot's scan outputs stay as they are."""
+        n = self._n[slot]
+        tails, begin, end = _region(tails, begin, end, "mod_profile")
+        origin = np.ascontiguousarray(origin, dtype=np.int32)
+        mod_off = np.ascontiguousarray(mod_off, dtype=np.int64)
+        delta = np.ascontiguousarray(delta, dtype=np.uint32)
+        prob = np.ascontiguousarray(prob, dtype=np.uint8)
+        if len(origin) != len(tails) or len(mod_off) != len(tails) + 1 or len(delta) != len(prob):
+            raise TopsicleHipError("mod_profile: origin must have one entry per read, mod_off one more, delta and prob the same number")
+        nb = max(int(nb0) + int(nb1), 0)
+        rows = np.zeros(n, dtype=MOD_ROW_DTYPE)
+        bins = np.zeros((n, nb), dtype=MOD_BIN_DTYPE)
+        self._check(self.lib.tps_batch_mod_profile(self._h, slot, _ptr(tails), _ptr(begin), _ptr(end), _ptr(origin), len(tails), _ptr(mod_off), _ptr(delta),
+                                                   _ptr(prob), len(delta), int(w), int(nb0), int(nb1), int(hi), int(lo), _ptr(rows), rows.size, _ptr(bins), bins.size))
+        return rows, bins
 
     def set_tails(self, slot: int, tails: np.ndarray):
         tails = np.ascontiguousarray(tails, dtype=np.uint8)

@@ -20,7 +20,7 @@ from collections import defaultdict
 
 import numpy as np
 
-from . import adapters, allsteps, anchor, batch, consensus, endref, ends, hiplib, motif, rawnpz, refine, seqio, tracts, variants
+from . import adapters, allsteps, anchor, batch, consensus, endref, ends, hiplib, methyl, motif, rawnpz, refine, seqio, tracts, variants
 
 version_number = "1.0.0"
 Topsicle_output_prefix = "Topsicle"
@@ -32,11 +32,11 @@ WRITER_THREADS = 1                # threads that write the passing records (nati
 # its analysis: FLAG (the flag that turns it on = its keyword of batch.Job), cli_check(args, root) -> None or the words after
 # "--flag needs", POWER_NOTE (what it does with a motif that is a power of its root), cli_collector(args, unit, slide),
 # Collector.keep_row (what is kept per read with a stored boundary) and finish_and_write(args, k, col, filenames, engines) -> log lines.
-PER_K_ANALYSES = (variants, ends, adapters, refine)       # one collector per k
+PER_K_ANALYSES = (variants, ends, adapters, refine, methyl)       # one collector per k
 ANALYSES = PER_K_ANALYSES + (tracts,)                     # one for the run: the map of whole reads, with the first k's job
 # ... and what is checked before anything is read or written, in this order (--variants is only checked against the real unit;
 # --anchor and --endref hang on --ends and have nothing else to check)
-EARLY_CHECKS = (tracts, ends, anchor, consensus, endref, adapters, refine)
+EARLY_CHECKS = (tracts, ends, anchor, consensus, endref, adapters, refine, methyl)
 LAST_TIMINGS = {}                 # seconds of the last analysis_run: reads (step 1 + 2 + outputs) / summary (fit + PNG); bench.py's e2e leg reads it
 PLOT_THREADS = []                 # quadratic-fit PNGs being rendered off the critical path (summarize); wait_for_plots() joins them
 
@@ -682,6 +682,16 @@ def build_parser():
     parser.add_argument("--refineminscore", metavar="INT", type=int, default=refine.DEFAULT_MIN_SCORE, help="--refine: a read whose best score is below this is classed no_telomere")
     parser.add_argument("--refinemindrop", metavar="INT", type=int, default=refine.DEFAULT_MIN_DROP, help="--refine: a read whose score falls by less than this up to the end of the region is classed open")
     parser.add_argument("--refineminmargin", metavar="INT", type=int, default=refine.DEFAULT_MIN_MARGIN, help="--refine: a read whose runner-up boundary scores within this of the best is classed ambiguous")
+    parser.add_argument("--methyl", action="store_true",
+                        help="MI355X build, BAM input: CpG methylation of the subtelomere behind every called boundary from the records' MM / ML tags -- one row per "
+                             "read (methyl_{k}.csv: tag status, CpGs, calls, high and low calls, meth_fraction, mean probability), one per bin of distance "
+                             "from the boundary (methyl_profile_{k}.csv) and, with --ends, one per end group (methyl_ends_{k}.csv); no other output changes")
+    parser.add_argument("--methylbin", metavar="INT", type=int, default=methyl.DEFAULT_BIN, help="--methyl: width of a bin in bases (16..4096)")
+    parser.add_argument("--methylbins", metavar="INT", type=int, default=methyl.DEFAULT_BINS, help="--methyl: bins behind the boundary, in the subtelomere")
+    parser.add_argument("--methyltract", metavar="INT", type=int, default=methyl.DEFAULT_TRACT, help="--methyl: bins in front of the boundary, in the tract (64 bins and 16384 bases at most together)")
+    parser.add_argument("--methylhigh", metavar="FLOAT", type=float, default=methyl.DEFAULT_HIGH, help="--methyl: a call with at least this probability counts as methylated")
+    parser.add_argument("--methyllow", metavar="FLOAT", type=float, default=methyl.DEFAULT_LOW, help="--methyl: a call with at most this probability counts as unmethylated")
+    parser.add_argument("--methylcode", metavar="CHAR", type=str, default=methyl.DEFAULT_CODE, help="--methyl: the modification code of the MM tag (m: 5mC, h: 5hmC)")
     parser.add_argument("--adaptersearch", metavar="INT", type=int, default=adapters.DEFAULT_SEARCH, help="--adapters: bases at the telomere end that are searched (16..1024; never beyond maxlengthtelo)")
     parser.add_argument("--adaptererr", metavar="FLOAT", type=float, default=adapters.DEFAULT_ERR, help="--adapters: edits allowed per letter of a sequence (a sequence of m letters: floor(err m) edits)")
     parser.add_argument("--adaptermargin", metavar="INT", type=int, default=adapters.DEFAULT_MARGIN, help="--adapters: edits by which the best sequence must beat every other to name the read")

@@ -229,6 +229,8 @@ IO_EXPORTS = {
     "tps_write_fastq_spans_at": ("c_int64", ["c_int", "c_int64", "c_void_p", "c_int64", "c_void_p", "c_void_p", "c_void_p", "c_int64"]),
     "tps_fastq_spans_bytes": ("c_int64", ["c_void_p", "c_void_p", "c_void_p", "c_int64"]),
     "tps_write_bam_fastq_spans_at": ("c_int64", ["c_int", "c_int64", "c_void_p", "c_int64", "c_void_p", "c_void_p", "c_void_p", "c_int64"]),
+    "tps_bam_mods_spans": ("c_int64", ["c_void_p", "c_int64", "c_void_p", "c_void_p", "c_void_p", "c_int64", "c_char", "c_void_p", "c_void_p", "c_void_p",
+                                       "c_void_p", "c_void_p", "c_int64"]),
     "tps_crc32": ("c_uint32", ["c_uint32", "c_void_p", "c_int64"]),
     "tps_crc32_combine": ("c_uint32", ["c_uint32", "c_uint32", "c_int64"]),
     "tps_io_set_option": ("c_int", ["c_char_p", "c_int64"]),
@@ -248,7 +250,7 @@ def _load_io():
             _io_lib = False
             return None
         lib = C.CDLL(path)
-        ns = {"POINTER": C.POINTER, **{n: getattr(C, n) for n in ("c_char_p", "c_void_p", "c_int", "c_int32", "c_int64", "c_uint32")}}
+        ns = {"POINTER": C.POINTER, **{n: getattr(C, n) for n in ("c_char", "c_char_p", "c_void_p", "c_int", "c_int32", "c_int64", "c_uint32")}}
         for name, (res, args) in IO_EXPORTS.items():
             fn = getattr(lib, name)
             fn.restype = None if res is None else eval(res, ns)
@@ -754,6 +756,67 @@ def _bam_batches(lib, h, filepath, pool, nrec_cap):
         text = _HeldText(lib, tp.value, tl.value, th.value)
         yield PackedBatch(None, None, bs.desc[:n], bs.heads[:int(bs.head_off[n])].copy(), bs.head_off[:n + 1].copy(), "bam",
                           spans=bs.spans[:n].copy(), text=text, bufset=bs, pool=pool, nib=nib[:nb.value], src=src[:n], n_words=nw.value)
+
+
+MODS_STATUS = ("ok", "none", "nogroup", "malformed", "clipped", "untagged")      # tps_bam_mods_spans's status 0 .. 4; 5: a batch that carries no tags
+
+
+class Mods:
+    """The base-modification entries of some reads of a batch: status and mode per read, and the ragged lists (mod_off, delta, prob)
+    as HipScanner.mod_profile takes them.  mods[sel] -- an index array, as batch.run_analysis cuts every per-read array -- gives the
+    same for those reads."""
+
+    def __init__(self, status, mode, mod_off, delta, prob):
+        self.status, self.mode, self.mod_off, self.delta, self.prob = status, mode, mod_off, delta, prob
+
+    def __len__(self):
+        return len(self.status)
+
+    def __getitem__(self, sel):
+        import numpy as np
+        sel = np.asarray(sel, np.int64)
+        n_each = (self.mod_off[1:] - self.mod_off[:-1])[sel]
+        off = np.zeros(len(sel) + 1, np.int64)
+        np.cumsum(n_each, out=off[1:])
+        take = np.repeat(self.mod_off[:-1][sel] - off[:-1], n_each) + np.arange(int(off[-1]), dtype=np.int64)
+        return Mods(self.status[sel], self.mode[sel], off, self.delta[take], self.prob[take])
+
+
+def bam_mods(pb, wanted, code: str = "m") -> Mods:
+    """The MM / ML calls of modification `code` on the reads `wanted` (a boolean array over the batch) of a BAM batch, from the record
+    text the batch still holds (tps_bam_mods_spans): a Mods over the WHOLE batch, empty lists for the reads not asked for.  A batch of
+    any other kind carries no tags: every read asked for gets status 5, `untagged`."""
+    import ctypes as C
+    import numpy as np
+    n = len(pb)
+    wanted = np.asarray(wanted, bool)
+    status = np.zeros(n, np.int32)
+    mode = np.zeros(n, np.uint8)
+    mod_off = np.zeros(n + 1, np.int64)
+    idx = np.ascontiguousarray(np.nonzero(wanted)[0], np.int64)
+    lib = _load_io()
+    if getattr(pb, "fmt", None) != "bam" or getattr(pb, "spans", None) is None or getattr(pb, "text", None) is None or lib is None:
+        status[idx] = 5
+        return Mods(status, mode, mod_off, np.zeros(0, np.uint32), np.zeros(0, np.uint8))
+    text = np.frombuffer(pb.text.buffer() if hasattr(pb.text, "buffer") else pb.text, dtype=np.uint8)
+    spans = np.ascontiguousarray(pb.spans, np.int64)
+    lens = np.ascontiguousarray(pb.desc["len"], np.int32)
+    st, md, off = np.zeros(len(idx), np.int32), np.zeros(len(idx), np.uint8), np.zeros(len(idx) + 1, np.int64)
+    cap = int(lens[idx].sum(dtype=np.int64)) + 1          # (an entry per base is more than any well-formed tag holds; -2 grows it)
+    while True:
+        delta, prob = np.zeros(cap, np.uint32), np.zeros(cap, np.uint8)
+        got = lib.tps_bam_mods_spans(text.ctypes.data, len(text), spans.ctypes.data, lens.ctypes.data, idx.ctypes.data, len(idx), code.encode(),
+                                     st.ctypes.data, md.ctypes.data, off.ctypes.data, delta.ctypes.data, prob.ctypes.data, cap)
+        if got != -2:
+            break
+        cap *= 4
+    if got < 0:
+        raise RuntimeError(lib.tps_io_last_error().decode())
+    status[idx], mode[idx] = st, md
+    n_each = np.zeros(n, np.int64)
+    n_each[idx] = off[1:] - off[:-1]
+    np.cumsum(n_each, out=mod_off[1:])
+    return Mods(status, mode, mod_off, delta[:got].copy(), prob[:got].copy())
 
 
 def shard_ranges(filepath: str, n_shards: int, min_bytes: int = 64 << 20):
